@@ -2,11 +2,21 @@
 """bench.py -- filter-steps/s of the MI355X-native EKF/UKF-SLAM core on synthetic trajectories.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ekf512|ekf64|ukf64|ekf8] [--batch B] [--chunk C]
-                    [--scaling weak|strong --trajectories M] [--no-sub]
+                    [--scaling weak|strong --trajectories M] [--dump-outputs DIR] [--full [--no-sub] [--no-legs] [--cpu-sample S]]
 
 Default workload: BASELINE.json configs[3] -- EKF, 512 landmarks (n = 1027), fp32 MFMA products, 256 trajectories per GPU
-(the north-star configuration; the largest one that fits a single GPU).  On one GPU the same JSON line carries the
-configs[1] (ekf64) and configs[2] (ukf64) measurements as sub-records, each with its own roofline.
+(the north-star configuration; the largest one that fits a single GPU).
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step, the roofline of the timed
+launches).  --full adds what the headline does not need: the check of the ekf512 fp32 filters against the fp64 path
+(`parity_check`), the batch-1 latency and PCIe-inclusive legs, the configs[1] (ekf64) and configs[2] (ukf64) measurements as
+sub-records (one GPU, each with its own roofline) and the CPU-oracle baselines.
+
+--dump-outputs DIR: after the timed steps, what the timed path computed is written as DIR/<name>.npy (float64, at most 64 MB
+in all): `poses` = the pose stream of the last timed step [filters, C, 3], `X` / `Z` = the final state vector and its landmark
+ids per filter, `P` = the final covariance of a seeded sample of filters; `<name>_filters` lists the filters of an array that is
+a sample.  The inputs are generated from --seed, so two runs with the same arguments see the same data.  Under --gpus N > 1
+the dump holds rank 0's filters (trajectories 0 .. B-1).
 
 One bench "step" = one replay launch = `chunk` consecutive callbacks (sensor message + odom message: association, growth
 bookkeeping, predict, update) for each of the `batch` independent trajectories held by a GPU.  The trace is already resident
@@ -18,7 +28,7 @@ in HBM when the timed region starts.
 in total (configs[4]: 8), dealt to the ranks in contiguous blocks.  Either way the only communication is one all_gather of the
 pose streams at the end of the timed region (RCCL over xGMI).
 
-Prints ONE JSON line (rank 0).  The CPU oracle is used for the `cpu_baseline` leg and for nothing else.
+Prints ONE JSON line (rank 0).  The CPU oracle is used for the `cpu_baseline` leg (--full) and for nothing else.
 """
 import argparse
 import json
@@ -175,7 +185,7 @@ def sub_records(seed):
     subs = {}
     for sw, sC, sK, sW in (("ekf64", 500, 4, 1), ("ukf64", 200, 10, 2)):
         cmd = [sys.executable, os.path.abspath(__file__), "--workload", sw, "--chunk", str(sC), "--steps", str(sK), "--warmup", str(sW),
-               "--seed", str(seed), "--cpu-sample", "0", "--no-sub"]
+               "--seed", str(seed), "--full", "--cpu-sample", "0", "--no-sub"]
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1200)
         if r.returncode != 0:
             raise SystemExit(f"bench sub-record {sw} failed:\n{r.stderr[-2000:]}")
@@ -269,9 +279,51 @@ def single_trajectory_latency(workload, seed, C1, local, dev):
             "filter_steps_per_s": C1 / (ms[1] * 1e-3), "steady_state": bool(ok)}
 
 
-def measure(workload, B, C, K, W, seed, first_traj, rank, world, local, dev):
+DUMP_BUDGET = {"poses": 16 << 20, "X": 8 << 20, "Z": 8 << 20, "P": 32 << 20}  # bytes per array, 64 MB in all
+DUMP_SEED = 20260101  # the fixed sample of filters an array is cut to when it exceeds its budget
+
+
+def dump_filters(name, B, row_bytes):
+    """The filters whose rows of array `name` are written: all of them when they fit DUMP_BUDGET[name], else a fixed seeded sample."""
+    import numpy as np
+
+    k = max(1, min(B, DUMP_BUDGET[name] // row_bytes))
+    if k == B:
+        return np.arange(B)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(B, k, replace=False))
+
+
+def dump_outputs(path, core, last_poses, n_full):
+    """--dump-outputs: the last timed step's pose stream and the final filter states, as float64 .npy files under `path`."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    B = last_poses.shape[0]
+    out = {}
+    ids = dump_filters("poses", B, last_poses[0].nbytes)
+    out["poses"] = (last_poses[ids], ids)
+    ids = dump_filters("X", B, 8 * n_full)
+    X, Z = np.full((len(ids), n_full), np.nan), np.full((len(ids), n_full), np.nan)
+    for i, b in enumerate(ids):
+        x, z, _ = core.state(int(b), with_P=False)
+        X[i, :len(x)], Z[i, :len(z)] = x, z
+    out["X"], out["Z"] = (X, ids), (Z, ids)
+    ids = dump_filters("P", B, 8 * n_full * n_full)
+    P = np.full((len(ids), n_full, n_full), np.nan)
+    for i, b in enumerate(ids):
+        p = core.state(int(b))[2]
+        P[i, :p.shape[0], :p.shape[1]] = p
+    out["P"] = (P, ids)
+    for name, (a, ids) in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, np.float64))
+        if len(ids) < B:
+            np.save(os.path.join(path, name + "_filters.npy"), ids.astype(np.float64))
+
+
+def measure(workload, B, C, K, W, seed, first_traj, rank, world, local, dev, full=False, dump=None):
     """W untimed + exactly K timed replay launches of `C` callbacks for this rank's `B` trajectories; barrier + synchronize on
     both sides of the timed region, one all_gather of the pose streams at its end, max over ranks of the elapsed time.
+    full: the ekf512 fp32 filters are checked against the fp64 path afterwards.  dump: directory for --dump-outputs (rank 0).
     Returns (elapsed_s, mean launch duration by HIP events in s, kernel info, trace_gen_s)."""
     import numpy as np
     import torch
@@ -288,7 +340,7 @@ def measure(workload, B, C, K, W, seed, first_traj, rank, world, local, dev):
     core.set_trace(tr)
     # filters whose final state is compared with the fp64 path after the timed region (ekf512): one inside the first stream group, one
     # with an index >= 8 inside a later group, the last one of the batch
-    check_ids = sorted({min(3, B - 1), min(B - 1, B // 4 + 13), B - 1}) if workload == "ekf512" else []
+    check_ids = sorted({min(3, B - 1), min(B - 1, B // 4 + 13), B - 1}) if workload == "ekf512" and full else []
     check_tr = tr.select(check_ids) if check_ids else None
     del tr
     stream = torch.cuda.current_stream().cuda_stream
@@ -328,6 +380,8 @@ def measure(workload, B, C, K, W, seed, first_traj, rank, world, local, dev):
         raise SystemExit(f"bench {workload}: a filter left its steady state (dimension/status/non-finite pose)")
     info = core.kernel_info()
     info["launch"] = core.launch_info()
+    if dump and rank == 0:
+        dump_outputs(dump, core, poses[K - 1].cpu().numpy(), n_full)
     finals = {b: core.state(b) for b in check_ids}
     core.close()
     del poses, scratch, all_poses
@@ -439,10 +493,15 @@ def main():
     ap.add_argument("--scaling", default="weak", choices=("weak", "strong"))
     ap.add_argument("--trajectories", type=int, default=8, help="total trajectories under --scaling strong (configs[4]: 8)")
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--cpu-sample", type=int, default=None, help="callbacks timed on the CPU oracle (0 = skip)")
-    ap.add_argument("--no-sub", action="store_true", help="skip the ekf64 / ukf64 sub-records")
+    ap.add_argument("--full", action="store_true",
+                    help="also the fp32-vs-fp64 parity check, the batch-1 latency and PCIe-inclusive legs, the ekf64 / ukf64 sub-records "
+                         "and the CPU-oracle baselines (a plain run does only what the headline figure needs)")
+    ap.add_argument("--cpu-sample", type=int, default=None, help="with --full: callbacks timed on the CPU oracle (0 = skip)")
+    ap.add_argument("--no-sub", action="store_true", help="with --full: skip the ekf64 / ukf64 sub-records")
     ap.add_argument("--no-legs", action="store_true",
-                    help="skip the batch-1 latency and PCIe-inclusive legs (profiling runs: the timed steps are then the last launches)")
+                    help="with --full: skip the batch-1 latency and PCIe-inclusive legs (the timed steps are then the last launches)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's poses and the final filter states as DIR/<name>.npy (float64, <= 64 MB)")
     args = ap.parse_args()
 
     if args.gpus > 1 and os.environ.get("ASLAM_DIST_BACKEND") != "gloo":
@@ -459,7 +518,7 @@ def main():
         raise SystemExit(spawn_ranks(args.gpus))
 
     subs = None
-    if args.gpus == 1 and args.workload == "ekf512" and args.scaling == "weak" and not args.no_sub:
+    if args.full and args.gpus == 1 and args.workload == "ekf512" and args.scaling == "weak" and not args.no_sub:
         subs = sub_records(args.seed)  # fresh processes, before this one touches the GPU
 
     import torch
@@ -492,7 +551,7 @@ def main():
         B = args.batch if args.batch is not None else 256
     first_traj = rank * B
 
-    el, kernel_s, info, t_gen = measure(wl, B, C, K, W, args.seed, first_traj, rank, world, local, dev)
+    el, kernel_s, info, t_gen = measure(wl, B, C, K, W, args.seed, first_traj, rank, world, local, dev, full=args.full, dump=args.dump_outputs)
 
     if rank == 0:
         total_steps = world * B * C * K
@@ -514,7 +573,7 @@ def main():
             if not info["parity_check"]["ok"]:
                 print(json.dumps(out), flush=True)
                 raise SystemExit("bench: fp32 filters beyond the parity bar against the fp64 path: " + json.dumps(info["parity_check"]))
-        if world == 1:
+        if world == 1 and args.full:
             if not args.no_legs:
                 out["single_trajectory"] = single_trajectory_latency(wl, args.seed, min(C, 200), local, dev)
                 out["pcie_step_batch"] = pcie_step_batch(wl, args.seed, min(B, 256), 10 if large else 100, local, dev)

@@ -61,3 +61,55 @@ def test_more_ranks_than_gpus_is_refused(monkeypatch):
     with pytest.raises(SystemExit) as e:
         bench.main()
     assert "this node has 1 GPU(s)" in str(e.value)
+
+
+@pytest.mark.parametrize("full", [False, True])
+def test_plain_run_does_only_what_the_headline_needs(full, monkeypatch, capsys):
+    """A plain run times the K steps and prints the headline line; the parity check, the batch-1 / PCIe legs, the sub-records and
+    the CPU baselines run only under --full.  The GPU work itself (measure) is replaced by a stand-in."""
+    import json
+
+    import bench
+    from awesomeslam_amd import dist as adist
+
+    called = []
+
+    def fake_measure(wl, B, C, K, W, *a, full=False, dump=None):
+        called.append(("measure", K, W, full, dump))
+        info = {"name": "k", "grid": 256, "block": 768, "lds_bytes": 0, "launch": None, "parity_check": {"ok": True} if full else None}
+        return 0.5, 0.04, info, 0.0
+
+    for name in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        monkeypatch.delenv(name, raising=False)
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
+    monkeypatch.setattr(torch.cuda, "device_count", lambda: 1)
+    monkeypatch.setattr(torch.cuda, "set_device", lambda d: None)
+    monkeypatch.setattr(adist, "finalize", lambda: None)
+    monkeypatch.setattr(bench, "measure", fake_measure)
+    for fn in ("sub_records", "single_trajectory_latency", "pcie_step_batch", "cpu_baseline", "cpu_baseline_all_cores"):
+        monkeypatch.setattr(bench, fn, lambda *a, _fn=fn, **k: called.append(_fn) or {"from": _fn})
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "5", "--warmup", "2"] + (["--full"] if full else []))
+    bench.main()
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert called[0] == ("sub_records" if full else ("measure", 5, 2, False, None))
+    assert ("measure", 5, 2, full, None) in called
+    extras = {"sub_records", "single_trajectory_latency", "pcie_step_batch", "cpu_baseline", "cpu_baseline_all_cores"}
+    assert set(c for c in called if isinstance(c, str)) == (extras if full else set())
+    assert line["steps"] == 5 and line["warmup"] == 2 and abs(line["ms_per_step"] - 100.0) < 1e-9
+    assert line["value"] == 256 * 20 * 5 / 0.5 and line["unit"] == "filter-steps/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f32" and line["metric"] == "EKF/UKF filter-steps/s @ N_landmarks" and "roofline" in line
+    for key in ("parity_check", "sub", "single_trajectory", "pcie_step_batch", "cpu_baseline", "cpu_baseline_all_cores"):
+        assert (key in line) == full, key
+
+
+def test_dump_sample_is_fixed_and_within_64_mb():
+    """--dump-outputs: an array over its budget is cut to a seeded sample of filters, the same one every run; the budgets add up to 64 MB."""
+    import bench
+
+    assert sum(bench.DUMP_BUDGET.values()) <= 64 << 20
+    n = 1027
+    ids = bench.dump_filters("P", 256, 8 * n * n)
+    assert len(ids) == 3 and list(ids) == sorted(set(ids)) and all(0 <= i < 256 for i in ids)
+    assert list(ids) == list(bench.dump_filters("P", 256, 8 * n * n))
+    assert list(bench.dump_filters("X", 256, 8 * n)) == list(range(256))
+    assert len(bench.dump_filters("poses", 4096, 500 * 3 * 8)) * 500 * 3 * 8 <= bench.DUMP_BUDGET["poses"]

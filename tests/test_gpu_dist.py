@@ -87,13 +87,15 @@ def test_two_ranks_share_the_gpu_and_gather_in_global_order(L, T, B, dtype, tol,
 def test_bench_spawns_its_own_ranks(mode, built):
     """`python bench.py --gpus 2` with WORLD_SIZE unset: the parent starts two fresh rank processes and relays rank 0's line.
     "configs4": BASELINE configs[4] as written, on two ranks -- `--workload ekf512 --scaling strong`, one 512-landmark fp32 filter per
-    rank --, whose timed region ends with the bench's own check of the fp32 filters against the fp64 path (`parity_check`)."""
+    rank --, run with --full, whose timed region is followed by the bench's own check of the fp32 filters against the fp64 path
+    (`parity_check`)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "ASLAM_CHOL_RESIDENT")}
     env["ASLAM_DIST_BACKEND"] = "gloo"
     wl, chunk = ("ekf512", 5) if mode == "configs4" else ("ekf8", 50)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", wl, "--steps", "2", "--warmup", "1",
            "--chunk", str(chunk), "--cpu-sample", "0"]
     cmd += ["--batch", "3"] if mode == "weak" else ["--scaling", "strong", "--trajectories", "2" if mode == "configs4" else "4"]
+    cmd += ["--full"] if mode == "configs4" else []  # the parity check is part of the --full run
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     line = json.loads(r.stdout.decode().strip().splitlines()[-1])

@@ -1,11 +1,12 @@
-# full GPU suite + the default bench line + the batch-1 and one-stream-group breakdowns, in one box
+# full GPU suite + the bench line with --full + the batch-1 and one-stream-group breakdowns, in one box
 set -e
 TAG=${1:-r4}
-mkdir -p gpurun_out/$TAG
-timeout -k 10 800 python -m pytest tests -x -q -m gpu > gpurun_out/$TAG/gpu_tests.log 2>&1 || { tail -30 gpurun_out/$TAG/gpu_tests.log; exit 1; }
-tail -2 gpurun_out/$TAG/gpu_tests.log
-timeout -k 10 300 python bench.py > gpurun_out/$TAG/bench_default.json 2> gpurun_out/$TAG/bench_default.err
-python - gpurun_out/$TAG/bench_default.json <<'PY'
+OUT=${OUT_DIR:-runs}/$TAG
+mkdir -p $OUT
+timeout -k 10 800 python -m pytest tests -x -q -m gpu > $OUT/gpu_tests.log 2>&1 || { tail -30 $OUT/gpu_tests.log; exit 1; }
+tail -2 $OUT/gpu_tests.log
+timeout -k 10 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
+python - $OUT/bench_default.json <<'PY'
 import json, sys
 r = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print("ekf512", r["value"], r["roofline"]["frac"], "batch1 us", r.get("single_trajectory", {}).get("us_per_callback"))
