@@ -6,7 +6,7 @@ import pytest
 from awesomeslam_amd import trace as tg
 from oracle.c_oracle import CFilter
 from oracle.np_oracle import NpFilter
-from util import rel_err
+from util import cov_err, rel_err
 
 CASES = [
     ("ekf", 5, 250, dict(seed=1), 30),
@@ -104,3 +104,29 @@ def test_set_state_and_single_slam(built):
             n.slam(np.float32(0.2), np.float32(0.1), np.float32(1.0))
         Xc, _, Pc = c.state()
         assert rel_err(Xc, n.X) < 1e-10 and rel_err(Pc, n.P) < 1e-9
+
+
+def test_numpy_oracle_on_large_marginals(built):
+    """NpFilter is the reference of the GPU tests that step handed-over states of every dimension up to 1087
+    (tests/test_gpu_batch_shapes.py); here it is held against the C++ oracle at those sizes.  Base state: 512 landmarks
+    promoted in one stage (n = 1027), two callbacks at full size -- one growth stage keeps the C++ replay short; its
+    marginals at n = 63, 65, 191, 1027 are SPD states of those dimensions (leading blocks of an SPD P)."""
+    L = 512
+    tr = tg.make_traces(L, 11, B=1, seed=13, stages=1)[0]
+    c = CFilter("ekf", tg.dim_cap(L))
+    _, dims = c.replay(tr)
+    assert dims[-1] == tg.full_dim(L) and (dims == dims[-1]).sum() >= 2
+    X, Z, P = c.state()
+    P = (P + P.T) / 2
+    a00, a10 = c.A()
+    for n in (63, 65, 191, 1027):
+        np.linalg.cholesky(P[:n, :n])
+        cc, nn = CFilter("ekf", L), NpFilter("ekf", L)
+        cc.set_state(n, X[:n], Z[:n], P[:n, :n], a00, a10)
+        nn.set_state(n, X[:n], Z[:n], P[:n, :n], a00, a10)
+        cc.slam(0.2, 0.1, 0.5)
+        nn.slam(np.float32(0.2), np.float32(0.1), np.float32(0.5))
+        Xc, _, Pc = cc.state()
+        assert np.isfinite(Pc).all()
+        print(f"NumPy vs C++ oracle, one slam() at n={n}: rel err X {rel_err(Xc, nn.X):.2e} P {cov_err(Pc, nn.P):.2e}")
+        assert rel_err(Xc, nn.X) < 1e-10 and cov_err(Pc, nn.P) < 1e-9
