@@ -1,4 +1,5 @@
-// aslam_core.hip -- libaslam_core.so: context management + C ABI (include/aslam_core.h) over the gfx950 kernels.
+// aslam_core.hip -- libaslam_core.so: context management + C ABI (include/aslam_core.h) over the gfx950 kernels (the launches of the large-state
+// path: ekf_large_launch.h).
 //
 // Build (see Makefile): hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC
 // No CPU fallback exists: without a HIP device every compute entry point returns ASLAM_ERR_HIP.
@@ -14,11 +15,12 @@
 #include <algorithm>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "ekf_small.h"
 #include "ekf_large.h"
-#include "aslam_large16.h"
+#include "ekf_large_launch.h"
 #include "scan_front.h"
 #if ASLAM_HAVE_UKF
 #include "ukf_small.h"
@@ -55,8 +57,6 @@ struct aslam_ctx
         std::vector<void *> trace_owned;
         hipStream_t last_stream;
         int64_t hbm_bytes;
-        size_t lds_bytes;
-        std::string kernel_name;
 #if ASLAM_HAVE_UKF
         UkfView ukf = {};
 #endif
@@ -67,28 +67,7 @@ struct aslam_ctx
         int *skipped = nullptr;
         float *step_in = nullptr; // [3][batch] vx, az, dt of a batched step
         double *largeP = nullptr; // = lv64.P or lv32.P: the covariance is binary64 in both modes
-        // replay splits the batch into groups that run the launch chain side by side on separate streams: the latency-bound
-        // launches of one group (one-wave diagonal factorisations, the front end, short-K panels) then overlap the GEMMs of
-        // the others
-        static constexpr int LARGE_GROUPS = 8; // capacity; the default below was chosen by measurement (profiles/)
-        int large_groups = 3;                  // ASLAM_LARGE_GROUPS=1..8 overrides (1 = a single stream, for per-kernel profiling); 3: 88 / 88 / 80 of 256 filters --
-                                               // measured best at the end of round 4 (tools/manual/sweep_groups.sh: 37.4 - 38.0 k filter-steps/s against 36.6 - 36.8 k with 4, 36.5 - 37.1 k with 2)
-        // binary32 mode: Cholesky of S as ONE launch with a filter per workgroup (large_chol_resident) when the batch can fill the
-        // chip that way, as 33 multi-workgroup launches (diagonal block + panel per block column) for few filters.
-        // ASLAM_CHOL_RESIDENT=0/1 forces one form.
-        int chol_resident = -1;
-        int right_step = 1;   // binary32 mode below the resident batch: the right-looking one-launch-per-block-column chain (large_right_step); ASLAM_RIGHT_STEP=0: the left-looking chain of rounds 1 - 2 (potrf + panel launches, large_trsm_pipe)
-        int bf16_pipe = 3;    // binary32 mode, resident Cholesky: Cholesky and TRSM on the bf16 matrix pipe (large_chol_bf16 + large_trsm_bf16, ekf_large_trsm16.h); ASLAM_BF16_PIPE=0: the fp32-MFMA kernels
-        int keep_l32 = 0;     // ASLAM_KEEP_L32=1 (tests/manual/large_residuals.py reads L back): large_chol_bf16 also stores the off-diagonal blocks of L in binary32
-        int gs_tiles = 0;     // G, S from the lower block triangle of P (large_build_GS_tiles); ASLAM_GS_TILES=0: the row-pair kernel that reads all of P (large_build_GS) -- bit-identical results
-        int syrk_running = 0; // diagnostic (ASLAM_SYRK_RUNNING=1): round 2's accumulation order in large_syrk_bf16x3 (profiles/r03_experiments.md)
-        static constexpr int CHOL_RESIDENT_MIN_BATCH = 32;
-        hipStream_t aux[LARGE_GROUPS - 1] = {};
-        hipEvent_t ev_fork = nullptr, ev_join[LARGE_GROUPS - 1] = {};
-        // what the LAST launch of this context really did (aslam_get_launch_info: the tests assert on it, not on the configuration)
-        int last_groups = 0;        // stream groups that received work (1 = the caller's stream alone; 0 = single-CU kernel / nothing launched yet)
-        int last_resident = 0;      // 1 = the Cholesky of S ran as large_chol_resident
-        int last_launches = 0;      // kernel launches per callback and stream group
+        LargeHost lh; // knobs, streams of the stream groups, what the last launch did (ekf_large_launch.h)
 };
 
 namespace
@@ -108,21 +87,11 @@ template <typename T> int dev_alloc(aslam_ctx *c, T **p, size_t count, std::vect
 int upload_P(aslam_ctx *c, int traj, int n, const double *P)
 {
         const size_t NP = (size_t)c->NP;
-        if (!c->large)
-        {
-                std::vector<double> v(NP * NP, 0.0);
-                for (int i = 0; i < n; ++i)
-                        std::memcpy(&v[(size_t)i * NP], P + (size_t)i * n, sizeof(double) * n);
-                HIP_TRY(hipMemcpy(c->dv.P + traj * NP * NP, v.data(), sizeof(double) * NP * NP, hipMemcpyHostToDevice));
-        }
-        else
-        {
-                // the large path keeps P in binary64 in both modes (fp32 mode: binary32 G, S, L, V and MFMA products)
-                std::vector<double> v(NP * NP, 0.0);
-                for (int i = 0; i < n; ++i)
-                        std::memcpy(&v[(size_t)i * NP], P + (size_t)i * n, sizeof(double) * n);
-                HIP_TRY(hipMemcpy(c->largeP + traj * NP * NP, v.data(), sizeof(double) * NP * NP, hipMemcpyHostToDevice));
-        }
+        // (the large path keeps P in binary64 in both modes; fp32 mode: binary32 G, S, L, V and MFMA products)
+        std::vector<double> v(NP * NP, 0.0);
+        for (int i = 0; i < n; ++i)
+                std::memcpy(&v[(size_t)i * NP], P + (size_t)i * n, sizeof(double) * n);
+        HIP_TRY(hipMemcpy((c->large ? c->largeP : c->dv.P) + traj * NP * NP, v.data(), sizeof(double) * NP * NP, hipMemcpyHostToDevice));
         return ASLAM_OK;
 }
 
@@ -163,6 +132,23 @@ int sync_ctx(aslam_ctx *c)
         return ASLAM_OK;
 }
 
+/// the context's typed large-state view (binary32 or binary64 work matrices) handed to f
+template <typename F> int with_large_view(aslam_ctx *c, F &&f)
+{
+        return c->cfg.dtype == ASLAM_F32 ? f(c->lv32) : f(c->lv64);
+}
+
+/// P = Identity * KP_ROBOT_POSE on the 3 pose entries of every filter (P zeroed by the caller)
+int seed_pose_block(double *P, size_t B, size_t NP)
+{
+        std::vector<double> blk(3 * NP, 0.0);
+        for (int i = 0; i < 3; ++i)
+                blk[(size_t)i * NP + i] = (double)KP_ROBOT_POSE;
+        for (size_t b = 0; b < B; ++b)
+                HIP_TRY(hipMemcpy(P + b * NP * NP, blk.data(), sizeof(double) * blk.size(), hipMemcpyHostToDevice));
+        return ASLAM_OK;
+}
+
 template <typename T> int init_P_large(aslam_ctx *c, LargeView<T> &lv)
 {
         const size_t B = c->cfg.batch, NP = c->NP;
@@ -171,17 +157,7 @@ template <typename T> int init_P_large(aslam_ctx *c, LargeView<T> &lv)
         HIP_TRY(hipMemset(lv.S, 0, sizeof(T) * B * NP * NP));
         if (lv.Vw)
                 HIP_TRY(hipMemset(lv.Vw, 0, sizeof(T) * B * NP * NP));
-        std::vector<double> blk(3 * NP, 0.0);
-        for (int i = 0; i < 3; ++i)
-                blk[(size_t)i * NP + i] = (double)KP_ROBOT_POSE;
-        for (size_t b = 0; b < B; ++b)
-                HIP_TRY(hipMemcpy(lv.P + b * NP * NP, blk.data(), sizeof(double) * blk.size(), hipMemcpyHostToDevice));
-        return ASLAM_OK;
-}
-
-int init_state_large(aslam_ctx *c)
-{
-        return c->cfg.dtype == ASLAM_F32 ? init_P_large(c, c->lv32) : init_P_large(c, c->lv64);
+        return seed_pose_block(lv.P, B, NP);
 }
 
 /// initialize() for the whole batch: ekf.cpp:49-71 / ukf.cpp:49-67
@@ -197,17 +173,14 @@ int init_state(aslam_ctx *c)
         HIP_TRY(hipMemset(d.sens_n, 0, sizeof(int) * B));
         HIP_TRY(hipMemset(d.wait_n, 0, sizeof(int) * B));
         std::vector<int> n(B, 3), fl(B, FLAG_INIT_X | FLAG_INIT_Z);
-        std::vector<double> A(2 * (size_t)B);
+        std::vector<double> A(2 * (size_t)B, 0.0);
         for (int b = 0; b < B; ++b)
-        {
                 A[2 * b] = 1.0; // A = Identity
-                A[2 * b + 1] = 0.0;
-        }
         HIP_TRY(hipMemcpy(d.n, n.data(), sizeof(int) * B, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d.flags, fl.data(), sizeof(int) * B, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d.A, A.data(), sizeof(double) * 2 * B, hipMemcpyHostToDevice));
         if (c->large)
-                return init_state_large(c);
+                return with_large_view(c, [&](auto &lv) { return init_P_large(c, lv); });
 #if ASLAM_HAVE_UKF
         if (c->ukf.D)
         { // a reset context is a fresh one: the scratch too (ukf_alloc zeroes it; the kernels rely on never-written padding staying zero)
@@ -218,14 +191,7 @@ int init_state(aslam_ctx *c)
                 HIP_TRY(hipMemset(c->ukf.K, 0, sizeof(double) * (size_t)B * NP * NP));
         }
 #endif
-        // P = Identity * KP_ROBOT_POSE on the 3 pose entries
-        const double p0 = (double)KP_ROBOT_POSE;
-        std::vector<double> blk((size_t)3 * NP, 0.0);
-        for (int i = 0; i < 3; ++i)
-                blk[(size_t)i * NP + i] = p0;
-        for (int b = 0; b < B; ++b)
-                HIP_TRY(hipMemcpy(d.P + (size_t)b * NP * NP, blk.data(), sizeof(double) * blk.size(), hipMemcpyHostToDevice));
-        return ASLAM_OK;
+        return seed_pose_block(d.P, B, NP);
 }
 
 template <int NT, int MODE>
@@ -268,220 +234,52 @@ int launch_ukf(aslam_ctx *c, int grid, int64_t t0, int nsteps, double *poses, in
 }
 #endif
 
-/// one callback of the large-state EKF: front end + predict, G, S, blocked factorisation of [S; G; Y^T], P -= V V^T, X += V q
-template <typename T, int MODE>
-int launch_large_T(aslam_ctx *c, LargeView<T> &lv, int grid, int64_t t0, int nsteps, double *poses, int32_t *dims, StepArgs sa,
-                   hipStream_t st)
+/// f(std::integral_constant<int, NT>) for the tile count of a single-CU context: the small kernels are instantiated for 2, 5 and 9 tiles
+template <typename F> auto with_NT(int NT, F &&f)
 {
-        const int NP = c->NP, NB = NP / LB;
-        const size_t lds = LargeLds::bytes(NP);
-        auto fk = large_frontend_kernel<T, MODE>;
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(fk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        const int Bz = (MODE == MODE_STEP && sa.traj >= 0) ? 1 : c->cfg.batch; // sa.traj < 0: the batched step
-        (void)grid;
-        // the kernels index the filter through blockIdx: a group of filters starting at b0 gets views shifted to b0
-        struct Group
-        {
-                DevView dv;
-                LargeView<T> v;
-                int *skip;
-                double *poses;
-                int32_t *dims;
-                int nb;
-                hipStream_t st;
-        };
-        auto make_group = [&](int b0, int nb, hipStream_t gst) {
-                Group g = {c->dv, lv, c->skipped, poses, dims, nb, gst};
-                const size_t b = (size_t)b0, np = (size_t)NP, T_ = (size_t)c->dv.T;
-                g.dv.X += b * np;
-                g.dv.Z += b * np;
-                g.dv.A += 2 * b;
-                g.dv.n += b;
-                g.dv.flags += b;
-                g.dv.status += b;
-                g.dv.sens += b * (size_t)c->dv.max_obs * 2;
-                g.dv.sens_n += b;
-                g.dv.wait_rb += b * (size_t)c->dv.max_wait * 2;
-                g.dv.wait_cnt += b * (size_t)c->dv.max_wait;
-                g.dv.wait_n += b;
-                g.dv.step_in += b; // [3][B]: the stride stays the whole batch
-                if (MODE == MODE_REPLAY && b0 > 0)
-                {
-                        g.dv.tr_pose += 2 * b * T_;
-                        g.dv.tr_yaw += b * T_;
-                        g.dv.tr_twist += 2 * b * T_;
-                        g.dv.tr_dt += b * T_;
-                        g.dv.tr_new += b * T_;
-                        g.dv.tr_nobs += b * T_;
-                        g.dv.tr_obs += b * T_ * (size_t)c->dv.max_obs * 2;
-                        if (g.poses)
-                                g.poses += b * (size_t)nsteps * 3;
-                        if (g.dims)
-                                g.dims += b * (size_t)nsteps;
-                }
-                g.v.P += b * np * np;
-                g.v.G += b * np * np;
-                g.v.S += b * np * np;
-                g.v.Hc += b * (np / 2) * 4;
-                g.v.Linv += b * LARGE_NB_MAX * LB * LB;
-                if constexpr (sizeof(T) == 4)
-                {
-                        if (g.v.Lpl)
-                                g.v.Lpl += b * LPlanes::per_filter((int)np);
-                        if (g.v.Vw)
-                                g.v.Vw += b * np * np;
-                }
-                g.v.Y += b * np;
-                g.skip += b;
-                return g;
-        };
-        const bool resident = c->chol_resident >= 0 ? c->chol_resident != 0 : Bz >= aslam_ctx::CHOL_RESIDENT_MIN_BATCH;
-        auto chain = [&](const Group &g, int s) {
-                const int gb = g.nb;
-                hipLaunchKernelGGL(fk, dim3(gb), dim3(SMALL_WG), lds, g.st, g.dv, g.v, t0 + s, s, nsteps, g.poses, g.dims, sa, g.skip);
-                if (c->gs_tiles)
-                        hipLaunchKernelGGL(large_build_GS_tiles<T>, dim3(NB * (NB + 1) / 2, gb), dim3(256), 0, g.st, g.dv, g.v, g.skip);
-                else
-                        hipLaunchKernelGGL(large_build_GS<T>, dim3(1 + (NP / 2 + GS_ROW_PAIRS - 1) / GS_ROW_PAIRS, gb), dim3(256), 0, g.st, g.dv, g.v, g.skip);
-                const int ntile = (NP + 127) / 128;
-                const dim3 syrk_grid(8 * (ntile * (ntile + 1) / 2) * ((gb + 7) / 8));
-                LargeView<T> vv = g.v; // what the consumers of V read
-                if constexpr (sizeof(T) == 4)
-                {
-                        // binary32: from 32 filters on the resident kernels (one launch each: Cholesky of S with a filter per workgroup, then V = G L^-T with
-                        // the solved columns in registers); below that one right-looking launch per block column that factors S and solves the rows of G
-                        // together (large_right_step; ASLAM_RIGHT_STEP=0: rounds 1 - 2's 17 x {diagonal block, panel of S} + large_trsm_pipe); then
-                        // P -= V V^T into the fp64 covariance
-                        const bool right = !resident && c->right_step && g.v.Vw != nullptr;
-                        const bool pipe16 = resident && g.v.Lpl != nullptr && (c->bf16_pipe & 1), chol16 = resident && g.v.Lpl != nullptr && (c->bf16_pipe & 2);
-                        if (chol16)
-                                launch_chol_bf16(g.dv, g.v, gb, g.skip, g.st, !pipe16 || c->keep_l32); // (the bf16 TRSM reads L through its planes only)
-                        else if (resident)
-                                hipLaunchKernelGGL(large_chol_resident<LARGE_NB_MAX>, dim3(gb), dim3(256), 0, g.st, g.dv, g.v, g.skip);
-                        else if (right)
-                        {
-                                hipLaunchKernelGGL(large_potrf_inv_tiles<T>, dim3(gb), dim3(256), 0, g.st, g.dv, g.v, 0, g.skip);
-                                for (int k = 0; k < NB; ++k)
-                                {
-                                        const int M = NB - k - 1;
-                                        hipLaunchKernelGGL(large_right_step<0>, dim3(M * (M + 1) / 2 + NB * M + NB, 1, gb), dim3(256), 0, g.st, g.dv, g.v, k, g.skip);
-                                }
-                                vv.G = g.v.Vw; // V is there, row n = q included
-                        }
-                        else
-                                for (int k = 0; k < NB; ++k)
-                                {
-                                        hipLaunchKernelGGL(large_potrf_inv_tiles<T>, dim3(gb), dim3(256), 0, g.st, g.dv, g.v, k, g.skip);
-                                        if (k + 1 < NB)
-                                                hipLaunchKernelGGL(large_update_panel<T>, dim3((NB - k) / 2, 1, gb), dim3(256), 0, g.st, g.dv, g.v, k, 1, g.skip);
-                                }
-                        if (pipe16)
-                                launch_trsm_bf16(g.dv, g.v, gb, g.skip, g.st);
-                        else if (!right) // (large_right_step has solved the rows of G on its way)
-                                hipLaunchKernelGGL(large_trsm_pipe<LARGE_NB_MAX>, dim3(8 * ((gb + 7) / 8) * NB), dim3(256), 0, g.st, g.dv, g.v, gb, g.skip);
-                        if (c->syrk_running)
-                                hipLaunchKernelGGL((large_syrk_bf16x3<2>), syrk_grid, dim3(256), 0, g.st, g.dv, vv, LPlanes{nullptr}, gb, g.skip);
-                        else
-                                hipLaunchKernelGGL((large_syrk_bf16x3<0>), syrk_grid, dim3(256), 0, g.st, g.dv, vv, LPlanes{nullptr}, gb, g.skip);
-                        // X += V q (+ the diagonal and the pose columns of V V^T in binary64) BEHIND the syrk on the same stream.  Round 4 tried the two ways of
-                        // running it next to the syrk -- its workgroups inside the syrk launch, and on a side stream of its own (the two write disjoint entries
-                        // of P) -- and both were slower: 2436 us against 1997 + 324 per 256 filters, and 31.7 k against 36.4 k filter-steps/s
-                        // (profiles/r04_experiments.md section 1)
-                        hipLaunchKernelGGL((large_x_update_rows<MODE>), dim3((NP + 4 * XU_ROWS - 1) / (4 * XU_ROWS), gb), dim3(256), 0, g.st, g.dv, vv, s, nsteps, g.poses,
-                                           g.dims, g.skip);
-                }
-                else
-                {
-                        for (int k = 0; k < NB; ++k)
-                        {
-                                hipLaunchKernelGGL(large_potrf_inv_tiles<T>, dim3(gb), dim3(256), 0, g.st, g.dv, g.v, k, g.skip);
-                                hipLaunchKernelGGL(large_update_panel<T>, dim3((2 * NB - k) / 2, 1, gb), dim3(256), 0, g.st, g.dv, g.v, k, 0, g.skip);
-                        }
-                        hipLaunchKernelGGL(large_syrk<T>, syrk_grid, dim3(256), 0, g.st, g.dv, g.v, gb, g.skip);
-                }
-                if constexpr (sizeof(T) == 8)
-                        hipLaunchKernelGGL((large_x_update<T, MODE, false>), dim3((NP + 3) / 4, gb), dim3(256), 0, g.st, g.dv, g.v, s, nsteps, g.poses, g.dims,
-                                           g.skip);
-        };
-        const int NG = c->large_groups;
-        c->last_resident = (sizeof(T) == 4 && resident) ? 1 : 0;
-        c->last_launches = sizeof(T) == 4 ? (resident ? 6 : (c->right_step && c->lv32.Vw ? 5 + NB : 4 + 2 * NB)) : 4 + 2 * NB;
-        c->last_groups = 1;
-        if (MODE == MODE_STEP && sa.traj >= 0)
-        {
-                Group g = make_group(sa.traj, 1, st);
-                sa.traj = 0;
-                for (int s = 0; s < nsteps; ++s)
-                        chain(g, s);
-        }
-        else if (Bz < std::max(32, 8 * NG)) // (one group below 32 filters, as with the former default of four groups)
-        {
-                Group g = make_group(0, Bz, st);
-                for (int s = 0; s < nsteps; ++s)
-                        chain(g, s);
-        }
-        else
-        {
-                Group g[aslam_ctx::LARGE_GROUPS];
-                const int per = ((Bz + NG - 1) / NG + 7) & ~7; // multiples of 8: large_syrk deals filters to the 8 XCDs
-                for (int q = 0; q < NG; ++q)
-                {
-                        const int b0 = min(q * per, Bz);
-                        g[q] = make_group(b0, min(per, Bz - b0), q == 0 ? st : c->aux[q - 1]);
-                }
-                c->last_groups = 0;
-                for (int q = 0; q < NG; ++q)
-                        c->last_groups += g[q].nb > 0;
-                HIP_TRY(hipEventRecord(c->ev_fork, st));
-                for (int q = 1; q < NG; ++q)
-                        HIP_TRY(hipStreamWaitEvent(c->aux[q - 1], c->ev_fork, 0));
-                for (int s = 0; s < nsteps; ++s)
-                        for (int q = 0; q < NG; ++q)
-                                if (g[q].nb > 0)
-                                        chain(g[q], s);
-                for (int q = 1; q < NG; ++q)
-                {
-                        HIP_TRY(hipEventRecord(c->ev_join[q - 1], c->aux[q - 1]));
-                        HIP_TRY(hipStreamWaitEvent(st, c->ev_join[q - 1], 0));
-                }
-        }
-        HIP_TRY(hipGetLastError());
-        return ASLAM_OK;
+        return NT == 2 ? f(std::integral_constant<int, 2>{}) : NT == 5 ? f(std::integral_constant<int, 5>{}) : f(std::integral_constant<int, 9>{});
 }
 
 template <int MODE>
 int launch(aslam_ctx *c, int grid, int64_t t0, int nsteps, double *poses, int32_t *dims, StepArgs sa, hipStream_t st)
 {
         if (c->large)
-                return c->cfg.dtype == ASLAM_F32 ? launch_large_T<float, MODE>(c, c->lv32, grid, t0, nsteps, poses, dims, sa, st)
-                                                 : launch_large_T<double, MODE>(c, c->lv64, grid, t0, nsteps, poses, dims, sa, st);
+                return with_large_view(c, [&](auto &lv) -> int {
+                        HIP_TRY(launch_large<MODE>(c->lh, c->dv, lv, c->skipped, t0, nsteps, poses, dims, sa, st));
+                        return ASLAM_OK;
+                });
         if (c->cfg.filter == ASLAM_EKF)
-        {
-                switch (c->NT)
-                {
-                case 2:
-                        return launch_ekf<2, MODE>(c, grid, t0, nsteps, poses, dims, sa, st);
-                case 5:
-                        return launch_ekf<5, MODE>(c, grid, t0, nsteps, poses, dims, sa, st);
-                case 9:
-                        return launch_ekf<9, MODE>(c, grid, t0, nsteps, poses, dims, sa, st);
-                }
-        }
+                return with_NT(c->NT, [&](auto nt) { return launch_ekf<decltype(nt)::value, MODE>(c, grid, t0, nsteps, poses, dims, sa, st); });
 #if ASLAM_HAVE_UKF
         if (c->cfg.filter == ASLAM_UKF)
-        {
-                switch (c->NT)
-                {
-                case 2:
-                        return launch_ukf<2, MODE>(c, grid, t0, nsteps, poses, dims, sa, st);
-                case 5:
-                        return launch_ukf<5, MODE>(c, grid, t0, nsteps, poses, dims, sa, st);
-                case 9:
-                        return launch_ukf<9, MODE>(c, grid, t0, nsteps, poses, dims, sa, st);
-                }
-        }
+                return with_NT(c->NT, [&](auto nt) { return launch_ukf<decltype(nt)::value, MODE>(c, grid, t0, nsteps, poses, dims, sa, st); });
 #endif
         return fail(ASLAM_ERR_UNSUPPORTED, "no kernel for this filter/size");
+}
+
+/// the typed buffers of a large-state context, in this order (addresses follow from it)
+template <typename T> int alloc_large(aslam_ctx *c, LargeView<T> &lv)
+{
+        const size_t B = (size_t)c->cfg.batch, NP = (size_t)c->NP;
+        const LargePlan plan = large_plan(sizeof(T) == 4, c->NP, c->cfg.batch, c->cfg.batch, c->lh.knobs);
+        int rc = ASLAM_OK;
+        auto A_ = [&](int r) {
+                if (rc == ASLAM_OK)
+                        rc = r;
+        };
+        lv.NP = c->NP;
+        A_(dev_alloc(c, &lv.P, B * NP * NP, c->owned));
+        c->largeP = lv.P;
+        A_(dev_alloc(c, &lv.G, B * NP * NP, c->owned));
+        A_(dev_alloc(c, &lv.S, B * NP * NP, c->owned));
+        A_(dev_alloc(c, &lv.Hc, B * (NP / 2) * 4, c->owned));
+        A_(dev_alloc(c, &lv.Y, B * NP, c->owned));
+        A_(dev_alloc(c, &lv.Linv, B * LARGE_NB_MAX * LB * LB, c->owned));
+        if (plan.need_Lpl)
+                A_(dev_alloc(c, &lv.Lpl, B * LPlanes::per_filter((int)NP), c->owned));
+        if (plan.need_Vw)
+                A_(dev_alloc(c, &lv.Vw, B * NP * NP, c->owned));
+        return rc;
 }
 } // namespace
 
@@ -510,15 +308,10 @@ int aslam_create(const aslam_config *cfg, aslam_ctx **out)
                 return fail(ASLAM_ERR_ARG, "dtype must be ASLAM_F64 or ASLAM_F32");
         const int n_max = cfg->max_landmark_count - 1; // growth is refused at N >= MAX_LANDMARK_COUNT
         const int need = (n_max + 15) / 16;
-        int NT = 0;
-        for (int cand : {2, 5, 9})
-        {
+        int NT = 0; // the smallest instantiated tile count that holds the state
+        for (int cand : {9, 5, 2})
                 if (cand >= need)
-                {
                         NT = cand;
-                        break;
-                }
-        }
         const bool large = (NT == 0) || cfg->dtype == ASLAM_F32; // fp32 exists on the multi-workgroup path only
         if (large)
         {
@@ -565,55 +358,16 @@ int aslam_create(const aslam_config *cfg, aslam_ctx **out)
         else
         {
                 A_(dev_alloc(c, &c->skipped, B, c->owned));
-                if (const char *e = std::getenv("ASLAM_LARGE_GROUPS"))
-                        c->large_groups = std::max(1, std::min((int)aslam_ctx::LARGE_GROUPS, std::atoi(e)));
-                if (const char *e = std::getenv("ASLAM_CHOL_RESIDENT"))
-                        c->chol_resident = std::atoi(e) != 0;
-                if (const char *e = std::getenv("ASLAM_KEEP_L32"))
-                        c->keep_l32 = std::atoi(e) != 0;
-                if (const char *e = std::getenv("ASLAM_GS_TILES"))
-                        c->gs_tiles = std::atoi(e) != 0;
-                if (const char *e = std::getenv("ASLAM_SYRK_RUNNING"))
-                        c->syrk_running = std::atoi(e) != 0;
-                if (const char *e = std::getenv("ASLAM_RIGHT_STEP"))
-                        c->right_step = std::atoi(e) != 0;
-                if (const char *e = std::getenv("ASLAM_BF16_PIPE"))
-                        c->bf16_pipe = std::atoi(e) & 3; // bit 0: the TRSM, bit 1: the Cholesky (diagnostics: 1 = large_chol_resident writes the planes, 2 = large_trsm_pipe solves)
-                for (hipStream_t &q : c->aux)
+                c->lh.knobs = large_knobs_from_env();
+                for (hipStream_t &q : c->lh.aux)
                         if (hipStreamCreateWithFlags(&q, hipStreamNonBlocking) != hipSuccess)
                                 rc = ASLAM_ERR_HIP;
-                if (hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess)
+                if (hipEventCreateWithFlags(&c->lh.ev_fork, hipEventDisableTiming) != hipSuccess)
                         rc = ASLAM_ERR_HIP;
-                for (hipEvent_t &e : c->ev_join)
+                for (hipEvent_t &e : c->lh.ev_join)
                         if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess)
                                 rc = ASLAM_ERR_HIP;
-                if (cfg->dtype == ASLAM_F32)
-                {
-                        c->lv32.NP = c->NP;
-                        A_(dev_alloc(c, &c->lv32.P, B * NP * NP, c->owned));
-                        c->largeP = c->lv32.P;
-                        A_(dev_alloc(c, &c->lv32.G, B * NP * NP, c->owned));
-                        A_(dev_alloc(c, &c->lv32.S, B * NP * NP, c->owned));
-                        A_(dev_alloc(c, &c->lv32.Hc, B * (NP / 2) * 4, c->owned));
-                        A_(dev_alloc(c, &c->lv32.Y, B * NP, c->owned));
-                        A_(dev_alloc(c, &c->lv32.Linv, B * LARGE_NB_MAX * LB * LB, c->owned));
-                        if (c->bf16_pipe)
-                                A_(dev_alloc(c, &c->lv32.Lpl, B * LPlanes::per_filter((int)NP), c->owned));
-                        const bool may_be_resident = c->chol_resident >= 0 ? c->chol_resident != 0 : cfg->batch >= aslam_ctx::CHOL_RESIDENT_MIN_BATCH;
-                        if (c->right_step && !may_be_resident)
-                                A_(dev_alloc(c, &c->lv32.Vw, B * NP * NP, c->owned));
-                }
-                else
-                {
-                        c->lv64.NP = c->NP;
-                        A_(dev_alloc(c, &c->lv64.P, B * NP * NP, c->owned));
-                        c->largeP = c->lv64.P;
-                        A_(dev_alloc(c, &c->lv64.G, B * NP * NP, c->owned));
-                        A_(dev_alloc(c, &c->lv64.S, B * NP * NP, c->owned));
-                        A_(dev_alloc(c, &c->lv64.Hc, B * (NP / 2) * 4, c->owned));
-                        A_(dev_alloc(c, &c->lv64.Y, B * NP, c->owned));
-                        A_(dev_alloc(c, &c->lv64.Linv, B * LARGE_NB_MAX * LB * LB, c->owned));
-                }
+                A_(with_large_view(c, [&](auto &lv) { return alloc_large(c, lv); }));
         }
         A_(dev_alloc(c, &d.A, B * 2, c->owned));
         A_(dev_alloc(c, &c->step_in, B * 3, c->owned));
@@ -657,12 +411,12 @@ int aslam_destroy(aslam_ctx *c)
                 (void)hipFree(p);
         for (void *p : c->trace_owned)
                 (void)hipFree(p);
-        for (hipStream_t q : c->aux)
+        for (hipStream_t q : c->lh.aux)
                 if (q)
                         (void)hipStreamDestroy(q);
-        if (c->ev_fork)
-                (void)hipEventDestroy(c->ev_fork);
-        for (hipEvent_t e : c->ev_join)
+        if (c->lh.ev_fork)
+                (void)hipEventDestroy(c->lh.ev_fork);
+        for (hipEvent_t e : c->lh.ev_join)
                 if (e)
                         (void)hipEventDestroy(e);
         delete c;
@@ -691,24 +445,17 @@ int aslam_set_state(aslam_ctx *c, int traj, int n, const double *X, const double
                 return rc;
         const size_t NP = (size_t)c->NP;
         DevView &d = c->dv;
-        if (X)
-        {
-                std::vector<double> v(NP, 0.0);
-                std::memcpy(v.data(), X, sizeof(double) * n);
-                HIP_TRY(hipMemcpy(d.X + traj * NP, v.data(), sizeof(double) * NP, hipMemcpyHostToDevice));
-        }
-        if (Z)
-        {
-                std::vector<double> v(NP, 0.0);
-                std::memcpy(v.data(), Z, sizeof(double) * n);
-                HIP_TRY(hipMemcpy(d.Z + traj * NP, v.data(), sizeof(double) * NP, hipMemcpyHostToDevice));
-        }
-        if (P)
-        {
-                rc = upload_P(c, traj, n, P);
-                if (rc != ASLAM_OK)
-                        return rc;
-        }
+        const double *src[2] = {X, Z};
+        double *dst[2] = {d.X, d.Z};
+        for (int i = 0; i < 2; ++i)
+                if (src[i])
+                {
+                        std::vector<double> v(NP, 0.0);
+                        std::memcpy(v.data(), src[i], sizeof(double) * n);
+                        HIP_TRY(hipMemcpy(dst[i] + traj * NP, v.data(), sizeof(double) * NP, hipMemcpyHostToDevice));
+                }
+        if (P && (rc = upload_P(c, traj, n, P)) != ASLAM_OK)
+                return rc;
         const int fl = 0; // a filter whose state was handed over is past both init flags
         HIP_TRY(hipMemcpy(d.n + traj, &n, sizeof(int), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d.flags + traj, &fl, sizeof(int), hipMemcpyHostToDevice));
@@ -749,14 +496,16 @@ int aslam_grow(aslam_ctx *c, int traj, int n_new, const double *x_seed, const do
         return ASLAM_OK;
 }
 
-int aslam_ekf_step(aslam_ctx *c, int traj, float vx, float az, float dt, const double *Z, double a00, double a10,
-                   double *X_out, void *stream)
+namespace
+{
+/// one callback of one trajectory: Z (and the EKF's A) to the device, the launch, optional read-back of X (synchronises then)
+int step_one(aslam_ctx *c, int filter, int traj, float vx, float az, float dt, const double *Z, const double *A, double *X_out, void *stream)
 {
         int rc = check_traj(c, traj);
         if (rc != ASLAM_OK)
                 return rc;
-        if (c->cfg.filter != ASLAM_EKF)
-                return fail(ASLAM_ERR_STATE, "context was created for the UKF");
+        if (c->cfg.filter != filter)
+                return fail(ASLAM_ERR_STATE, filter == ASLAM_EKF ? "context was created for the UKF" : "context was created for the EKF");
         if (!Z)
                 return fail(ASLAM_ERR_ARG, "Z is required");
         hipStream_t st = static_cast<hipStream_t>(stream);
@@ -766,9 +515,9 @@ int aslam_ekf_step(aslam_ctx *c, int traj, float vx, float az, float dt, const d
         HIP_TRY(hipMemcpyAsync(&n, d.n + traj, sizeof(int), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         const size_t NP = (size_t)c->NP;
-        const double A[2] = {a00, a10};
         HIP_TRY(hipMemcpyAsync(d.Z + traj * NP, Z, sizeof(double) * n, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d.A + 2 * traj, A, sizeof(A), hipMemcpyHostToDevice, st));
+        if (A)
+                HIP_TRY(hipMemcpyAsync(d.A + 2 * traj, A, 2 * sizeof(double), hipMemcpyHostToDevice, st));
         StepArgs sa{traj, vx, az, dt};
         rc = launch<MODE_STEP>(c, 1, 0, 1, nullptr, nullptr, sa, st);
         if (rc != ASLAM_OK)
@@ -780,34 +529,18 @@ int aslam_ekf_step(aslam_ctx *c, int traj, float vx, float az, float dt, const d
         }
         return ASLAM_OK;
 }
+} // namespace
+
+int aslam_ekf_step(aslam_ctx *c, int traj, float vx, float az, float dt, const double *Z, double a00, double a10,
+                   double *X_out, void *stream)
+{
+        const double A[2] = {a00, a10};
+        return step_one(c, ASLAM_EKF, traj, vx, az, dt, Z, A, X_out, stream);
+}
 
 int aslam_ukf_step(aslam_ctx *c, int traj, float vx, float az, float dt, const double *Z, double *X_out, void *stream)
 {
-        int rc = check_traj(c, traj);
-        if (rc != ASLAM_OK)
-                return rc;
-        if (c->cfg.filter != ASLAM_UKF)
-                return fail(ASLAM_ERR_STATE, "context was created for the EKF");
-        if (!Z)
-                return fail(ASLAM_ERR_ARG, "Z is required");
-        hipStream_t st = static_cast<hipStream_t>(stream);
-        c->last_stream = st;
-        DevView &d = c->dv;
-        int n = 0;
-        HIP_TRY(hipMemcpyAsync(&n, d.n + traj, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        const size_t NP = (size_t)c->NP;
-        HIP_TRY(hipMemcpyAsync(d.Z + traj * NP, Z, sizeof(double) * n, hipMemcpyHostToDevice, st));
-        StepArgs sa{traj, vx, az, dt};
-        rc = launch<MODE_STEP>(c, 1, 0, 1, nullptr, nullptr, sa, st);
-        if (rc != ASLAM_OK)
-                return rc;
-        if (X_out)
-        {
-                HIP_TRY(hipMemcpyAsync(X_out, d.X + traj * NP, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
-        }
-        return ASLAM_OK;
+        return step_one(c, ASLAM_UKF, traj, vx, az, dt, Z, nullptr, X_out, stream);
 }
 
 namespace
@@ -1070,28 +803,19 @@ int aslam_debug_large(aslam_ctx *c, int traj, int which, double *out, int64_t ca
         const size_t cnt = which < 2 ? NP * NP : which == 2 ? (size_t)LARGE_NB_MAX * LB * LB : NP;
         if ((int64_t)cnt > cap)
                 return fail(ASLAM_ERR_ARG, "aslam_debug_large: buffer too small");
-        if (which == 3)
-        {
-                const double *src = (c->cfg.dtype == ASLAM_F32 ? c->lv32.Y : c->lv64.Y) + traj * NP;
-                HIP_TRY(hipMemcpy(out, src, cnt * sizeof(double), hipMemcpyDeviceToHost));
+        return with_large_view(c, [&](auto &lv) -> int {
+                using T = std::remove_reference_t<decltype(*lv.G)>;
+                if (which == 3)
+                {
+                        HIP_TRY(hipMemcpy(out, lv.Y + traj * NP, cnt * sizeof(double), hipMemcpyDeviceToHost));
+                        return ASLAM_OK;
+                }
+                const T *src = which == 0 ? lv.G + traj * NP * NP : which == 1 ? lv.S + traj * NP * NP : lv.Linv + traj * cnt;
+                std::vector<T> tmp(cnt);
+                HIP_TRY(hipMemcpy(tmp.data(), src, cnt * sizeof(T), hipMemcpyDeviceToHost));
+                std::copy(tmp.begin(), tmp.end(), out);
                 return ASLAM_OK;
-        }
-        if (c->cfg.dtype == ASLAM_F32)
-        {
-                const float *src = which == 0 ? c->lv32.G + traj * NP * NP : which == 1 ? c->lv32.S + traj * NP * NP
-                                                                                      : c->lv32.Linv + traj * cnt;
-                std::vector<float> tmp(cnt);
-                HIP_TRY(hipMemcpy(tmp.data(), src, cnt * sizeof(float), hipMemcpyDeviceToHost));
-                for (size_t i = 0; i < cnt; ++i)
-                        out[i] = (double)tmp[i];
-        }
-        else
-        {
-                const double *src = which == 0 ? c->lv64.G + traj * NP * NP : which == 1 ? c->lv64.S + traj * NP * NP
-                                                                                       : c->lv64.Linv + traj * cnt;
-                HIP_TRY(hipMemcpy(out, src, cnt * sizeof(double), hipMemcpyDeviceToHost));
-        }
-        return ASLAM_OK;
+        });
 }
 
 #if defined(ASLAM_STAMPS) && ASLAM_HAVE_UKF
@@ -1259,11 +983,11 @@ int aslam_get_launch_info(aslam_ctx *c, int *stream_groups, int *chol_resident, 
         if (!c)
                 return fail(ASLAM_ERR_ARG, "null context");
         if (stream_groups)
-                *stream_groups = c->large ? c->last_groups : 0;
+                *stream_groups = c->large ? c->lh.last_groups : 0;
         if (chol_resident)
-                *chol_resident = c->large ? c->last_resident : 0;
+                *chol_resident = c->large && c->lh.last_plan.chain == LargeChain::F32_RESIDENT;
         if (launches_per_callback)
-                *launches_per_callback = c->large ? c->last_launches : 1;
+                *launches_per_callback = c->large ? c->lh.last_plan.launches : 1;
         return ASLAM_OK;
 }
 
@@ -1275,35 +999,31 @@ int aslam_kernel_info(aslam_ctx *c, char *name, int name_cap, int *grid, int *bl
         size_t lds = 0;
         if (c->large)
         {
-                const bool resident = c->chol_resident >= 0 ? c->chol_resident != 0 : c->cfg.batch >= aslam_ctx::CHOL_RESIDENT_MIN_BATCH;
-                if (c->cfg.dtype == ASLAM_F32 && resident)
-                {
-                        // the names say which pipe each kernel's products run on (bench.py prices them from this string): bit 1 of bf16_pipe = the
-                        // Cholesky, bit 0 = the TRSM on the bf16 matrix pipe; the X update rides in the syrk launch
-                        const bool chol16 = c->lv32.Lpl && (c->bf16_pipe & 2), trsm16 = c->lv32.Lpl && (c->bf16_pipe & 1);
-                        std::snprintf(buf, sizeof(buf), "%s + %s + large_syrk_bf16x3 (6-launch chain per callback, %d stream groups)",
-                                      chol16 ? "large_chol_bf16" : "large_chol_resident", trsm16 ? "large_trsm_bf16" : "large_trsm_pipe<17>", c->large_groups);
-                }
-                else if (c->cfg.dtype == ASLAM_F32 && c->right_step && c->lv32.Vw)
-                        std::snprintf(buf, sizeof(buf), "large_right_step + large_syrk_bf16x3 (%d-launch chain per callback: one right-looking launch per block column)", 5 + c->NP / LB);
-                else if (c->cfg.dtype == ASLAM_F32)
-                        std::snprintf(buf, sizeof(buf), "large_trsm_pipe<%d> + large_syrk_bf16x3 (%d-launch chain per callback: multi-workgroup Cholesky)",
-                                      (int)LARGE_NB_MAX, 4 + 2 * (c->NP / LB));
+                // the plan of a launch over the whole batch.  The names say which pipe each kernel's products run on (bench.py prices them from
+                // this string and looks the chain up in profiles/pmc_traffic.json by it)
+                const LargePlan plan = large_plan(c->cfg.dtype == ASLAM_F32, c->NP, c->cfg.batch, c->cfg.batch, c->lh.knobs);
+                if (plan.chain == LargeChain::F32_RESIDENT) // (launches 3 - 5 are named; the X update is launch 6)
+                        std::snprintf(buf, sizeof(buf), "%s + %s + large_syrk_bf16x3 (%d-launch chain per callback, %d stream groups)",
+                                      plan.chol16 ? "large_chol_bf16" : "large_chol_resident", plan.trsm16 ? "large_trsm_bf16" : "large_trsm_pipe<17>",
+                                      plan.launches, c->lh.knobs.groups);
+                else if (plan.chain == LargeChain::F32_RIGHT)
+                        std::snprintf(buf, sizeof(buf), "large_right_step + large_syrk_bf16x3 (%d-launch chain per callback: one right-looking launch per block column)", plan.launches);
+                else if (plan.chain == LargeChain::F32_LEFT)
+                        std::snprintf(buf, sizeof(buf), "large_trsm_pipe<17> + large_syrk_bf16x3 (%d-launch chain per callback: multi-workgroup Cholesky)", plan.launches);
                 else
-                        std::snprintf(buf, sizeof(buf), "large_update_panel<double> (%d-launch chain per callback, %d stream groups)",
-                                      4 + 2 * (c->NP / LB), c->large_groups);
+                        std::snprintf(buf, sizeof(buf), "large_update_panel<double> (%d-launch chain per callback, %d stream groups)", plan.launches, c->lh.knobs.groups);
                 lds = LargeLds::bytes(c->NP);
         }
         else if (c->cfg.filter == ASLAM_EKF)
         {
                 std::snprintf(buf, sizeof(buf), "ekf_small_kernel<%d,0>", c->NT);
-                lds = c->NT == 2 ? SmallLayout<2>::total : c->NT == 5 ? SmallLayout<5>::total : SmallLayout<9>::total;
+                lds = with_NT(c->NT, [](auto nt) -> size_t { return SmallLayout<decltype(nt)::value>::total; });
         }
 #if ASLAM_HAVE_UKF
         else
         {
                 std::snprintf(buf, sizeof(buf), "ukf_small_kernel<%d,0>", c->NT);
-                lds = c->NT == 2 ? UkfLayout<2>::total : c->NT == 5 ? UkfLayout<5>::total : UkfLayout<9>::total;
+                lds = with_NT(c->NT, [](auto nt) -> size_t { return UkfLayout<decltype(nt)::value>::total; });
         }
 #endif
         if (name && name_cap > 0)

@@ -1073,7 +1073,8 @@ __global__ __launch_bounds__(256) void large_syrk(DevView d, LargeView<T> lv, in
 #endif
 constexpr int XU_ROWS = ASLAM_XU_ROWS; // (rows per wave of large_x_update_rows; 4 and 16 measured in round 4: profiles/r04_experiments.md)
 ///
-/// PL = 1 (round 4; the default chain): V arrives ALREADY SPLIT -- large_trsm_bf16 stores the three bf16 planes of every solved block next to the binary32 V
+/// PL = 1 (round 4; NOT integrated: the library always launches PL = 0 with LPlanes{nullptr}, and no kernel of the library writes V's planes; PL = 1 is
+/// instantiated by tools/ubench/syrk_bench.hip only): V arrives ALREADY SPLIT -- its producer would store the three bf16 planes of every solved block next to the binary32 V
 /// (`vpl`: [B][3][NP][NP], the columns of every 64-block permuted as in LPlanes; the permutation stays inside a 32-column half, and a slab's contraction
 /// order is the same for both operands) -- and a slab goes global -> LDS by LDS-DMA (twelve 1-KiB pieces per wave: 16 rows x 64 bytes each, the k-group
 /// swizzle applied on the source side): no staging registers, no VALU split (176 instructions per thread and slab: each element of V was split ~ 17 times,

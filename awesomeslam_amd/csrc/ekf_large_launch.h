@@ -1,0 +1,278 @@
+// ekf_large_launch.h -- host side of the large-state EKF (n > 143, or fp32), included by aslam_core.hip: the environment knobs, the launch
+// plan (which of the four kernel chains a callback runs: large_plan() is the ONE place that decides it -- aslam_create, the launcher and
+// aslam_kernel_info read its result), views shifted to a group of filters, the chain launcher and the split of a batch into stream groups.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+
+#include "ekf_large.h"
+#include "aslam_large16.h"
+
+namespace aslam
+{
+constexpr int LARGE_GROUPS_MAX = 8;         // capacity of LargeHost's streams; the default number of groups was chosen by measurement (profiles/)
+constexpr int CHOL_RESIDENT_MIN_BATCH = 32; // filters in a launch from which a filter per workgroup fills the chip
+
+/// environment knobs (diagnostics / A-B runs; the defaults are what bench.py measures), read once per large-state context in aslam_create
+struct LargeKnobs
+{
+        // replay splits the batch into groups that run the launch chain side by side on separate streams: the latency-bound launches of one
+        // group (one-wave diagonal factorisations, the front end, short-K panels) then overlap the GEMMs of the others.
+        // ASLAM_LARGE_GROUPS=1..8 (1 = a single stream, for per-kernel profiling); 3: 88 / 88 / 80 of 256 filters -- measured best at the end of
+        // round 4 (tools/manual/sweep_groups.sh: 37.4 - 38.0 k filter-steps/s against 36.6 - 36.8 k with 4, 36.5 - 37.1 k with 2)
+        int groups = 3;
+        // binary32 mode: Cholesky of S as ONE launch with a filter per workgroup (the resident kernels) when the filters of the launch can fill
+        // the chip that way (CHOL_RESIDENT_MIN_BATCH), as multi-workgroup launches per block column for few filters.  ASLAM_CHOL_RESIDENT=0/1
+        // forces one form
+        int chol_resident = -1;
+        int right_step = 1;   // binary32 mode below the resident batch: the right-looking one-launch-per-block-column chain (large_right_step); ASLAM_RIGHT_STEP=0: the left-looking chain of rounds 1 - 2 (potrf + panel launches, large_trsm_pipe)
+        int bf16_pipe = 3;    // binary32 mode, resident chain: bit 0 the TRSM, bit 1 the Cholesky on the bf16 matrix pipe (large_trsm_bf16, large_chol_bf16: ekf_large_trsm16.h); ASLAM_BF16_PIPE=0: the fp32-MFMA pair (diagnostics: 1 = large_chol_resident writes the planes, 2 = large_trsm_pipe solves)
+        int keep_l32 = 0;     // ASLAM_KEEP_L32=1 (tests/manual/large_residuals.py reads L back): large_chol_bf16 also stores the off-diagonal blocks of L in binary32
+        int gs_tiles = 0;     // G, S by the row-pair kernel that reads all of P (large_build_GS); ASLAM_GS_TILES=1: from the lower block triangle of P (large_build_GS_tiles) -- bit-identical results, slower, kept for its test
+        int syrk_running = 0; // diagnostic (ASLAM_SYRK_RUNNING=1): round 2's accumulation order in large_syrk_bf16x3 (profiles/r03_experiments.md)
+};
+
+inline LargeKnobs large_knobs_from_env()
+{
+        LargeKnobs k;
+        auto flag = [](const char *name, int &v) { if (const char *e = std::getenv(name)) v = std::atoi(e) != 0; };
+        if (const char *e = std::getenv("ASLAM_LARGE_GROUPS"))
+                k.groups = std::max(1, std::min(LARGE_GROUPS_MAX, std::atoi(e)));
+        if (const char *e = std::getenv("ASLAM_BF16_PIPE"))
+                k.bf16_pipe = std::atoi(e) & 3;
+        flag("ASLAM_CHOL_RESIDENT", k.chol_resident);
+        flag("ASLAM_RIGHT_STEP", k.right_step);
+        flag("ASLAM_KEEP_L32", k.keep_l32);
+        flag("ASLAM_GS_TILES", k.gs_tiles);
+        flag("ASLAM_SYRK_RUNNING", k.syrk_running);
+        return k;
+}
+
+/// the launches of one callback and stream group, in order (NB = NP / 64 block columns); every chain starts with the front end and G, S
+enum class LargeChain
+{
+        F64_LEFT,     // NB x {large_potrf_inv_tiles, large_update_panel over S, G and Y^T}, large_syrk, large_x_update: 4 + 2 NB launches
+        F32_RESIDENT, // Cholesky and TRSM as one launch each with the factor resident (bf16 pipe or fp32 MFMA), large_syrk_bf16x3, large_x_update_rows: 6
+        F32_RIGHT,    // large_potrf_inv_tiles(0), NB x large_right_step (factors S and solves the rows of G into Vw together), syrk, X update: 5 + NB
+        F32_LEFT      // NB x {large_potrf_inv_tiles, large_update_panel over S}, large_trsm_pipe, syrk, X update: 4 + 2 NB
+};
+
+struct LargePlan
+{
+        LargeChain chain;
+        bool chol16, trsm16;         // F32_RESIDENT: large_chol_bf16 for large_chol_resident, large_trsm_bf16 for large_trsm_pipe
+        bool chol_f32out;            // large_chol_bf16 also stores the off-diagonal blocks of L in binary32 (the bf16 TRSM reads L through its planes only)
+        bool gs_tiles, syrk_running; // large_build_GS_tiles for large_build_GS; large_syrk_bf16x3<2> for <0>
+        int launches;                // kernel launches per callback and stream group
+        bool need_Lpl, need_Vw;      // buffers a context of `batch` filters owns besides P, G, S, Hc, Y, Linv
+};
+
+/// the plan of a launch over `filters` filters (1 for a step of one trajectory) of a context created for `batch` filters
+inline LargePlan large_plan(bool f32, int NP, int batch, int filters, const LargeKnobs &k)
+{
+        const int NB = NP / LB;
+        auto resident = [&k](int nf) { return k.chol_resident >= 0 ? k.chol_resident != 0 : nf >= CHOL_RESIDENT_MIN_BATCH; };
+        LargePlan p = {};
+        p.gs_tiles = k.gs_tiles != 0;
+        p.syrk_running = k.syrk_running != 0;
+        p.need_Lpl = f32 && k.bf16_pipe != 0;
+        p.need_Vw = f32 && k.right_step && !resident(batch); // (a one-trajectory step on a context that is resident as a whole finds no Vw: F32_LEFT)
+        if (!f32)
+                p.chain = LargeChain::F64_LEFT, p.launches = 4 + 2 * NB;
+        else if (resident(filters))
+        {
+                p.chain = LargeChain::F32_RESIDENT, p.launches = 6;
+                p.chol16 = (k.bf16_pipe & 2) != 0;
+                p.trsm16 = (k.bf16_pipe & 1) != 0;
+                p.chol_f32out = !p.trsm16 || k.keep_l32;
+        }
+        else if (p.need_Vw)
+                p.chain = LargeChain::F32_RIGHT, p.launches = 5 + NB;
+        else
+                p.chain = LargeChain::F32_LEFT, p.launches = 4 + 2 * NB;
+        return p;
+}
+
+/// what a large-state context owns on the host side: its knobs, the streams and events of the stream groups, and what its LAST launch really
+/// did (aslam_get_launch_info: the tests assert on it, not on the configuration)
+struct LargeHost
+{
+        LargeKnobs knobs;
+        hipStream_t aux[LARGE_GROUPS_MAX - 1] = {};
+        hipEvent_t ev_fork = nullptr, ev_join[LARGE_GROUPS_MAX - 1] = {};
+        int last_groups = 0;     // stream groups that received work (1 = the caller's stream alone; 0 = nothing launched yet)
+        LargePlan last_plan = {}; // the plan of that launch
+};
+
+// the kernels index the filter through blockIdx: a group of filters starting at b0 gets views shifted to b0
+inline DevView shifted(DevView d, size_t b, bool trace)
+{
+        const size_t np = (size_t)d.NP, T_ = (size_t)d.T;
+        d.X += b * np;
+        d.Z += b * np;
+        d.A += 2 * b;
+        d.n += b;
+        d.flags += b;
+        d.status += b;
+        d.sens += b * (size_t)d.max_obs * 2;
+        d.sens_n += b;
+        d.wait_rb += b * (size_t)d.max_wait * 2;
+        d.wait_cnt += b * (size_t)d.max_wait;
+        d.wait_n += b;
+        d.step_in += b; // [3][B]: the stride stays the whole batch
+        if (trace)
+        {
+                d.tr_pose += 2 * b * T_;
+                d.tr_yaw += b * T_;
+                d.tr_twist += 2 * b * T_;
+                d.tr_dt += b * T_;
+                d.tr_new += b * T_;
+                d.tr_nobs += b * T_;
+                d.tr_obs += b * T_ * (size_t)d.max_obs * 2;
+        }
+        return d;
+}
+
+template <typename T> LargeView<T> shifted(LargeView<T> v, size_t b)
+{
+        const size_t np = (size_t)v.NP;
+        v.P += b * np * np;
+        v.G += b * np * np;
+        v.S += b * np * np;
+        v.Hc += b * (np / 2) * 4;
+        v.Linv += b * LARGE_NB_MAX * LB * LB;
+        if (v.Lpl)
+                v.Lpl += b * LPlanes::per_filter((int)np);
+        if (v.Vw)
+                v.Vw += b * np * np;
+        v.Y += b * np;
+        return v;
+}
+
+template <typename T> struct LargeGroup
+{
+        DevView dv;
+        LargeView<T> v;
+        int *skip;
+        double *poses;
+        int32_t *dims;
+        int nb;
+        hipStream_t st;
+};
+
+/// callback s of one group: front end + predict, G, S, blocked factorisation of [S; G; Y^T], P -= V V^T, X += V q
+template <typename T, int MODE>
+void launch_large_chain(const LargePlan &plan, const LargeGroup<T> &g, size_t lds, int64_t t0, int s, int nsteps, StepArgs sa)
+{
+        const int NP = g.v.NP, NB = NP / LB, gb = g.nb;
+        hipLaunchKernelGGL((large_frontend_kernel<T, MODE>), dim3(gb), dim3(SMALL_WG), lds, g.st, g.dv, g.v, t0 + s, s, nsteps, g.poses, g.dims, sa, g.skip);
+        if (plan.gs_tiles)
+                hipLaunchKernelGGL(large_build_GS_tiles<T>, dim3(NB * (NB + 1) / 2, gb), dim3(256), 0, g.st, g.dv, g.v, g.skip);
+        else
+                hipLaunchKernelGGL(large_build_GS<T>, dim3(1 + (NP / 2 + GS_ROW_PAIRS - 1) / GS_ROW_PAIRS, gb), dim3(256), 0, g.st, g.dv, g.v, g.skip);
+        const int ntile = (NP + 127) / 128;
+        const dim3 syrk_grid(8 * (ntile * (ntile + 1) / 2) * ((gb + 7) / 8));
+        if constexpr (sizeof(T) == 8)
+        { // F64_LEFT
+                for (int k = 0; k < NB; ++k)
+                {
+                        hipLaunchKernelGGL(large_potrf_inv_tiles<T>, dim3(gb), dim3(256), 0, g.st, g.dv, g.v, k, g.skip);
+                        hipLaunchKernelGGL(large_update_panel<T>, dim3((2 * NB - k) / 2, 1, gb), dim3(256), 0, g.st, g.dv, g.v, k, 0, g.skip);
+                }
+                hipLaunchKernelGGL(large_syrk<T>, syrk_grid, dim3(256), 0, g.st, g.dv, g.v, gb, g.skip);
+                hipLaunchKernelGGL((large_x_update<T, MODE, false>), dim3((NP + 3) / 4, gb), dim3(256), 0, g.st, g.dv, g.v, s, nsteps, g.poses, g.dims, g.skip);
+        }
+        else
+        {
+                LargeView<T> vv = g.v; // what the consumers of V read
+                switch (plan.chain)
+                {
+                case LargeChain::F32_RESIDENT:
+                        if (plan.chol16)
+                                launch_chol_bf16(g.dv, g.v, gb, g.skip, g.st, plan.chol_f32out);
+                        else
+                                hipLaunchKernelGGL(large_chol_resident<LARGE_NB_MAX>, dim3(gb), dim3(256), 0, g.st, g.dv, g.v, g.skip);
+                        if (plan.trsm16)
+                                launch_trsm_bf16(g.dv, g.v, gb, g.skip, g.st);
+                        else
+                                hipLaunchKernelGGL(large_trsm_pipe<LARGE_NB_MAX>, dim3(8 * ((gb + 7) / 8) * NB), dim3(256), 0, g.st, g.dv, g.v, gb, g.skip);
+                        break;
+                case LargeChain::F32_RIGHT:
+                        hipLaunchKernelGGL(large_potrf_inv_tiles<T>, dim3(gb), dim3(256), 0, g.st, g.dv, g.v, 0, g.skip);
+                        for (int k = 0; k < NB; ++k)
+                        {
+                                const int M = NB - k - 1;
+                                hipLaunchKernelGGL(large_right_step<0>, dim3(M * (M + 1) / 2 + NB * M + NB, 1, gb), dim3(256), 0, g.st, g.dv, g.v, k, g.skip);
+                        }
+                        vv.G = g.v.Vw; // V is there, row n = q included (large_right_step has solved the rows of G on its way)
+                        break;
+                default: // F32_LEFT
+                        for (int k = 0; k < NB; ++k)
+                        {
+                                hipLaunchKernelGGL(large_potrf_inv_tiles<T>, dim3(gb), dim3(256), 0, g.st, g.dv, g.v, k, g.skip);
+                                if (k + 1 < NB)
+                                        hipLaunchKernelGGL(large_update_panel<T>, dim3((NB - k) / 2, 1, gb), dim3(256), 0, g.st, g.dv, g.v, k, 1, g.skip);
+                        }
+                        hipLaunchKernelGGL(large_trsm_pipe<LARGE_NB_MAX>, dim3(8 * ((gb + 7) / 8) * NB), dim3(256), 0, g.st, g.dv, g.v, gb, g.skip);
+                }
+                if (plan.syrk_running)
+                        hipLaunchKernelGGL((large_syrk_bf16x3<2>), syrk_grid, dim3(256), 0, g.st, g.dv, vv, LPlanes{nullptr}, gb, g.skip);
+                else
+                        hipLaunchKernelGGL((large_syrk_bf16x3<0>), syrk_grid, dim3(256), 0, g.st, g.dv, vv, LPlanes{nullptr}, gb, g.skip);
+                // X += V q (+ the diagonal and the pose columns of V V^T in binary64) BEHIND the syrk on the same stream.  Round 4 tried the two ways of
+                // running it next to the syrk -- its workgroups inside the syrk launch, and on a side stream of its own (the two write disjoint entries
+                // of P) -- and both were slower: 2436 us against 1997 + 324 per 256 filters, and 31.7 k against 36.4 k filter-steps/s
+                // (profiles/r04_experiments.md section 1)
+                hipLaunchKernelGGL((large_x_update_rows<MODE>), dim3((NP + 4 * XU_ROWS - 1) / (4 * XU_ROWS), gb), dim3(256), 0, g.st, g.dv, vv, s, nsteps, g.poses,
+                                   g.dims, g.skip);
+        }
+}
+
+/// `nsteps` callbacks of a large-state context: one trajectory (MODE_STEP with sa.traj >= 0) or the whole batch, which from max(32, 8 x groups)
+/// filters on is split into stream groups.  The enqueue order (callbacks outermost, groups innermost) is what the rates were measured with
+template <int MODE, typename T>
+hipError_t launch_large(LargeHost &h, const DevView &dv, const LargeView<T> &lv, int *skipped, int64_t t0, int nsteps, double *poses, int32_t *dims,
+                        StepArgs sa, hipStream_t st)
+{
+        const size_t lds = LargeLds::bytes(dv.NP);
+        if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(large_frontend_kernel<T, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
+                return e;
+        const bool one = MODE == MODE_STEP && sa.traj >= 0; // sa.traj < 0: the batched step
+        const int first = one ? sa.traj : 0, Bz = one ? 1 : dv.B;
+        sa.traj = one ? 0 : sa.traj; // (the views of the group start at the trajectory)
+        const LargePlan plan = large_plan(sizeof(T) == 4, dv.NP, dv.B, Bz, h.knobs);
+        const bool split = Bz >= std::max(32, 8 * h.knobs.groups); // (one group below 32 filters, as with the former default of four groups)
+        const int NG = split ? h.knobs.groups : 1;
+        const int per = split ? ((Bz + NG - 1) / NG + 7) & ~7 : Bz; // multiples of 8: large_syrk deals filters to the 8 XCDs
+        LargeGroup<T> g[LARGE_GROUPS_MAX];
+        h.last_plan = plan;
+        h.last_groups = 0;
+        for (int q = 0; q < NG; ++q)
+        {
+                const int o = std::min(q * per, Bz);
+                const size_t b0 = (size_t)(first + o);
+                g[q] = {shifted(dv, b0, MODE == MODE_REPLAY), shifted(lv, b0), skipped + b0, poses, dims, std::min(per, Bz - o), q == 0 ? st : h.aux[q - 1]};
+                if (MODE == MODE_REPLAY && poses)
+                        g[q].poses += b0 * (size_t)nsteps * 3;
+                if (MODE == MODE_REPLAY && dims)
+                        g[q].dims += b0 * (size_t)nsteps;
+                h.last_groups += g[q].nb > 0;
+        }
+        hipError_t e = split ? hipEventRecord(h.ev_fork, st) : hipSuccess;
+        for (int q = 1; q < NG && e == hipSuccess; ++q)
+                e = hipStreamWaitEvent(h.aux[q - 1], h.ev_fork, 0);
+        if (e != hipSuccess)
+                return e;
+        for (int s = 0; s < nsteps; ++s)
+                for (int q = 0; q < NG; ++q)
+                        if (g[q].nb > 0)
+                                launch_large_chain<T, MODE>(plan, g[q], lds, t0, s, nsteps, sa);
+        for (int q = 1; q < NG && e == hipSuccess; ++q)
+                if ((e = hipEventRecord(h.ev_join[q - 1], h.aux[q - 1])) == hipSuccess)
+                        e = hipStreamWaitEvent(st, h.ev_join[q - 1], 0);
+        return e != hipSuccess ? e : hipGetLastError();
+}
+} // namespace aslam

@@ -36,7 +36,7 @@ def _sync():
 
 
 def expected_launch(dtype, B):
-    """(stream groups, resident Cholesky) the library must report for `B` filters of chain `dtype` (aslam_core.hip: one group below 32 filters)"""
+    """(stream groups, resident Cholesky) the library must report for `B` filters of chain `dtype` (ekf_large_launch.h: one group below 32 filters)"""
     return (1 if B < 32 else 3), (dtype.startswith("f32") and "-resident" in dtype)
 
 

@@ -107,7 +107,7 @@ def test_replay_parity(L, T, kw, dtype, built, monkeypatch):
     from awesomeslam_amd.core import Core, F32, F64
     from oracle.c_oracle import CFilter
 
-    dtype = chol_mode(dtype, monkeypatch)
+    param, dtype = dtype, chol_mode(dtype, monkeypatch)
     tr = tg.make_traces(L, T, B=2, **kw)
     core = Core("ekf", tg.dim_cap(L), batch=2, max_obs=tr.max_obs, max_wait=2048, dtype=F32 if dtype == "f32" else F64)
     core.set_trace(tr)
@@ -132,13 +132,22 @@ def test_replay_parity(L, T, kw, dtype, built, monkeypatch):
         errs = rel_err(poses.cpu().numpy()[b], po), rel_err(X, Xo), cov_err(P, Po)
         print(f"large replay L={L} {dtype} b={b} N={core.dim(b)}: rel err pose/X/P = {errs[0]:.2e} {errs[1]:.2e} {errs[2]:.2e}")
         assert max(errs) < tol and core.status(b) == 0
+    # the launch chain each spelling selects: what the last replay really launched (two filters: one stream group), and the kernels the context names
+    NB = core.layout()[0] // 64
+    want = {"f64": 4 + 2 * NB, "f32": 5 + NB, "f32-left": 4 + 2 * NB}.get(param, 6)
+    info = core.launch_info()
+    assert info["launches_per_callback"] == want and info["stream_groups"] == 1 and info["chol_resident"] == ("-resident" in param)
+    name = core.kernel_info()["name"]
+    for kernel, spellings in (("large_chol_bf16", ("f32-resident", "f32-resident-pipe2")), ("large_trsm_bf16", ("f32-resident", "f32-resident-pipe1")),
+                              ("large_right_step", ("f32",)), ("large_update_panel<double>", ("f64",))):
+        assert (kernel in name) == (param in spellings), (param, name)
 
 
 def test_replay_parity_stream_groups(built, monkeypatch):
     """A batch of 35 is replayed as groups of filters on separate streams (16 / 16 / 3: uneven, the last group short, the fourth
     empty): trajectories of every group, including the first and last of each, must match the oracle, and poses and dimensions
     must land in the caller's buffers at the right rows.  (Round 2 ran this with 19 filters, which stayed below the 8 x groups
-    threshold of aslam_core.hip and never left the single stream: the launch shape is now asserted, not assumed.)"""
+    threshold of ekf_large_launch.h and never left the single stream: the launch shape is now asserted, not assumed.)"""
     import torch
     from awesomeslam_amd.core import Core, F64
     from oracle.c_oracle import CFilter
