@@ -18,6 +18,7 @@ F64, F32 = 0, 1
 FILTERS = {"ekf": EKF, "ukf": UKF}
 
 ST_GROWTH_REFUSED, ST_WAIT_OVERFLOW, ST_NOT_PD, ST_OBS_OVERFLOW, ST_INTERNAL = 1, 2, 4, 8, 16
+CFG_UKF_LARGE = 1  # aslam_config.flags: a UKF context beyond the single-CU kernels (state dimension 144 .. 1085), fp64 launch chain
 
 # every symbol include/aslam_core.h declares (tests check the library exports them all)
 CORE_SYMBOLS = (
@@ -43,7 +44,7 @@ class AslamError(RuntimeError):
 
 class Config(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int32) for k in
-                ("filter", "dtype", "max_landmark_count", "batch", "max_obs", "max_wait", "device", "reserved")]
+                ("filter", "dtype", "max_landmark_count", "batch", "max_obs", "max_wait", "device", "flags")]
 
 
 class TraceView(ctypes.Structure):
@@ -303,12 +304,12 @@ def narrow_odom(odom):
 class Core:
     """One libaslam_core context: `batch` independent filters resident on one GPU."""
 
-    def __init__(self, filter="ekf", max_landmark_count=30, batch=1, max_obs=16, max_wait=128, device=0, dtype=F64):
+    def __init__(self, filter="ekf", max_landmark_count=30, batch=1, max_obs=16, max_wait=128, device=0, dtype=F64, flags=0):
         self.filter = filter
         self.batch = int(batch)
         self.max_obs = int(max_obs)
         cfg = Config(FILTERS[filter], dtype, int(max_landmark_count), int(batch), int(max_obs), int(max_wait),
-                     int(device), 0)
+                     int(device), int(flags))
         h = ctypes.c_void_p()
         _chk(core_lib().aslam_create(ctypes.byref(cfg), ctypes.byref(h)))
         self._h = h

@@ -1,5 +1,5 @@
 // aslam_core.hip -- libaslam_core.so: context management + C ABI (include/aslam_core.h) over the gfx950 kernels (the launches of the large-state
-// path: ekf_large_launch.h).
+// paths: ekf_large_launch.h, ukf_large_launch.h).
 //
 // Build (see Makefile): hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC
 // No CPU fallback exists: without a HIP device every compute entry point returns ASLAM_ERR_HIP.
@@ -24,6 +24,8 @@
 #include "scan_front.h"
 #if ASLAM_HAVE_UKF
 #include "ukf_small.h"
+#include "ukf_large.h"
+#include "ukf_large_launch.h"
 #endif
 
 using namespace aslam;
@@ -59,6 +61,7 @@ struct aslam_ctx
         int64_t hbm_bytes;
 #if ASLAM_HAVE_UKF
         UkfView ukf = {};
+        UkfLargeView ukfl = {}; // large-state UKF (ASLAM_CFG_UKF_LARGE): D, DZ and the small vectors of ukf_large.h
 #endif
         // large-state path (n > 143): typed covariance buffers, one launch chain per callback
         bool large = false;
@@ -243,6 +246,13 @@ template <typename F> auto with_NT(int NT, F &&f)
 template <int MODE>
 int launch(aslam_ctx *c, int grid, int64_t t0, int nsteps, double *poses, int32_t *dims, StepArgs sa, hipStream_t st)
 {
+#if ASLAM_HAVE_UKF
+        if (c->large && c->cfg.filter == ASLAM_UKF)
+        {
+                HIP_TRY(launch_ukf_large<MODE>(c->lh, c->dv, c->lv64, c->ukfl, c->skipped, t0, nsteps, poses, dims, sa, st));
+                return ASLAM_OK;
+        }
+#endif
         if (c->large)
                 return with_large_view(c, [&](auto &lv) -> int {
                         HIP_TRY(launch_large<MODE>(c->lh, c->dv, lv, c->skipped, t0, nsteps, poses, dims, sa, st));
@@ -268,6 +278,7 @@ template <typename T> int alloc_large(aslam_ctx *c, LargeView<T> &lv)
                         rc = r;
         };
         lv.NP = c->NP;
+        lv.xrows = c->cfg.filter == ASLAM_UKF ? 2 : 1; // vector rows behind the state rows of G: Y^T / z^T and the innovation (ukf_large.h)
         A_(dev_alloc(c, &lv.P, B * NP * NP, c->owned));
         c->largeP = lv.P;
         A_(dev_alloc(c, &lv.G, B * NP * NP, c->owned));
@@ -281,6 +292,27 @@ template <typename T> int alloc_large(aslam_ctx *c, LargeView<T> &lv)
                 A_(dev_alloc(c, &lv.Vw, B * NP * NP, c->owned));
         return rc;
 }
+
+#if ASLAM_HAVE_UKF
+/// HBM scratch of the large-state UKF chain: D, DZ ([NP][MP]), the propagated poses, the predicted mean and a few scalars per filter
+int ukf_large_alloc(aslam_ctx *c)
+{
+        const size_t B = (size_t)c->cfg.batch, NP = (size_t)c->NP;
+        const size_t MP = 2 * NP + 16; // >= 2 n + 5 rounded up to 16 for every n <= NP - 2
+        UkfLargeView &u = c->ukfl;
+        u.MP = (int)MP;
+        int rc = dev_alloc(c, &u.D, B * NP * MP, c->owned);
+        if (rc == ASLAM_OK)
+                rc = dev_alloc(c, &u.DZ, B * NP * MP, c->owned);
+        if (rc == ASLAM_OK)
+                rc = dev_alloc(c, &u.XP, B * 3 * MP, c->owned);
+        if (rc == ASLAM_OK)
+                rc = dev_alloc(c, &u.Xbar, B * NP, c->owned);
+        if (rc == ASLAM_OK)
+                rc = dev_alloc(c, &u.sc, B * 8, c->owned);
+        return rc;
+}
+#endif
 } // namespace
 
 extern "C" {
@@ -306,6 +338,8 @@ int aslam_create(const aslam_config *cfg, aslam_ctx **out)
                 return fail(ASLAM_ERR_ARG, "batch, max_landmark_count, max_obs, max_wait must be positive");
         if (cfg->dtype != ASLAM_F64 && cfg->dtype != ASLAM_F32)
                 return fail(ASLAM_ERR_ARG, "dtype must be ASLAM_F64 or ASLAM_F32");
+        if (cfg->flags & ~(int32_t)ASLAM_CFG_UKF_LARGE)
+                return fail(ASLAM_ERR_ARG, "unknown bit in flags");
         const int n_max = cfg->max_landmark_count - 1; // growth is refused at N >= MAX_LANDMARK_COUNT
         const int need = (n_max + 15) / 16;
         int NT = 0; // the smallest instantiated tile count that holds the state
@@ -313,12 +347,16 @@ int aslam_create(const aslam_config *cfg, aslam_ctx **out)
                 if (cand >= need)
                         NT = cand;
         const bool large = (NT == 0) || cfg->dtype == ASLAM_F32; // fp32 exists on the multi-workgroup path only
+        // rows of G behind the state rows: Y^T (EKF) / z^T and the innovation (UKF); they need room inside the padded dimension
+        const int xrows = cfg->filter == ASLAM_UKF ? 2 : 1;
         if (large)
         {
-                if (cfg->filter != ASLAM_EKF)
-                        return fail(ASLAM_ERR_UNSUPPORTED, "the UKF is limited to state dimensions up to 143 (single-CU kernels) and fp64");
-                if (n_max + 1 > LARGE_NP_MAX)
-                        return fail(ASLAM_ERR_UNSUPPORTED, "state dimension above 1087 is not supported");
+                if (cfg->filter != ASLAM_EKF && (!(cfg->flags & ASLAM_CFG_UKF_LARGE) || cfg->dtype != ASLAM_F64 || !ASLAM_HAVE_UKF))
+                        return fail(ASLAM_ERR_UNSUPPORTED, "the UKF is limited to state dimensions up to 143 (single-CU kernels) and fp64; "
+                                                           "ASLAM_CFG_UKF_LARGE opts in to the fp64 launch chain beyond that");
+                if (n_max + xrows > LARGE_NP_MAX)
+                        return fail(ASLAM_ERR_UNSUPPORTED, cfg->filter == ASLAM_EKF ? "state dimension above 1087 is not supported"
+                                                                                    : "UKF state dimension above 1085 (max_landmark_count above 1087) is not supported");
                 if (cfg->max_obs > LARGE_OBS_CAP || cfg->max_wait > LARGE_WAIT_CAP)
                         return fail(ASLAM_ERR_UNSUPPORTED, "max_obs above 1024 / max_wait above 2048 are not supported");
         }
@@ -335,7 +373,7 @@ int aslam_create(const aslam_config *cfg, aslam_ctx **out)
         c->cfg = *cfg;
         c->large = large;
         c->NT = large ? 0 : NT;
-        c->NP = large ? ((n_max + 1 + LB - 1) / LB) * LB : 16 * NT; // the large path needs one spare row (Y^T rides in G)
+        c->NP = large ? ((n_max + xrows + LB - 1) / LB) * LB : 16 * NT; // the large path needs spare rows (Y^T / z^T and the innovation ride in G)
         c->last_stream = nullptr;
         c->hbm_bytes = 0;
         std::memset(&c->dv, 0, sizeof(c->dv));
@@ -385,7 +423,7 @@ int aslam_create(const aslam_config *cfg, aslam_ctx **out)
 #endif
 #if ASLAM_HAVE_UKF
         if (rc == ASLAM_OK && cfg->filter == ASLAM_UKF)
-                rc = ukf_alloc(c);
+                rc = large ? ukf_large_alloc(c) : ukf_alloc(c);
 #else
         if (rc == ASLAM_OK && cfg->filter == ASLAM_UKF)
                 rc = fail(ASLAM_ERR_UNSUPPORTED, "library built without the UKF kernels");
@@ -1002,6 +1040,12 @@ int aslam_kernel_info(aslam_ctx *c, char *name, int name_cap, int *grid, int *bl
                 // the plan of a launch over the whole batch.  The names say which pipe each kernel's products run on (bench.py prices them from
                 // this string and looks the chain up in profiles/pmc_traffic.json by it)
                 const LargePlan plan = large_plan(c->cfg.dtype == ASLAM_F32, c->NP, c->cfg.batch, c->cfg.batch, c->lh.knobs);
+#if ASLAM_HAVE_UKF
+                if (c->cfg.filter == ASLAM_UKF)
+                        std::snprintf(buf, sizeof(buf), "ukf_large_wabt + large_update_panel<double> + large_syrk<double> (%d-launch chain per callback, 1 stream)",
+                                      ukf_large_plan(c->NP).launches);
+                else
+#endif
                 if (plan.chain == LargeChain::F32_RESIDENT) // (launches 3 - 5 are named; the X update is launch 6)
                         std::snprintf(buf, sizeof(buf), "%s + %s + large_syrk_bf16x3 (%d-launch chain per callback, %d stream groups)",
                                       plan.chol16 ? "large_chol_bf16" : "large_chol_resident", plan.trsm16 ? "large_trsm_bf16" : "large_trsm_pipe<17>",

@@ -48,6 +48,7 @@ template <typename T> struct LargeView
         T *Linv;    // [B][LARGE_NB_MAX][LB][LB]  inverses of the diagonal blocks of L
         T *Vw;      // [B][NP][NP]  binary32 mode, few-filter chain (large_right_step): V is written HERE, not over G (every block of G is read by many workgroups of a launch); else nullptr
         unsigned short *Lpl; // binary32 mode with the bf16-pipe TRSM: LPlanes::base (bf16 planes of L and of the inverses, written by large_chol_resident), else nullptr
+        int xrows;  // vector rows that ride in G behind the n state rows through the factorisation: 1 (EKF: Y^T), 2 (large-state UKF: z^T and the innovation, ukf_large.h)
 };
 
 // ---- MFMA traits -------------------------------------------------------------------------------------------------
@@ -127,10 +128,10 @@ __host__ __device__ __forceinline__ int lplane_pos(int c)
         return 32 * (c >> 5) + 8 * ((c >> 2) & 3) + 4 * ((c >> 4) & 1) + (c & 3);
 }
 
-/// number of active 64-blocks: the n state rows plus the Y^T row
-__device__ __forceinline__ int large_blocks(int n)
+/// number of active 64-blocks: the n state rows plus the vector rows that ride in G (LargeView::xrows; the EKF's one row, Y^T, where no view is at hand)
+__host__ __device__ __forceinline__ int large_blocks(int n, int xrows = 1)
 {
-        return (n + 1 + LB - 1) / LB;
+        return (n + xrows + LB - 1) / LB;
 }
 
 // ---- LDS layout of the front-end workgroup (runtime NP) -----------------------------------------------------------
@@ -720,7 +721,7 @@ __global__ __launch_bounds__(256) void large_update_panel(DevView d, LargeView<T
         if (skipped[b])
                 return;
         const int n = d.n[b], NP = lv.NP;
-        const int nb = large_blocks(n), na = nb * LB;
+        const int nb = large_blocks(n, lv.xrows), na = nb * LB;
         const int rt0 = k0 + 1 + 2 * blockIdx.x; // first virtual 64-row block: S rows below the diagonal block, then all of G
         const int vlim = s_only ? nb : 2 * nb;    // s_only: the rows of G are solved by large_trsm_pipe instead
         if (k0 >= nb || rt0 >= vlim)
@@ -922,7 +923,7 @@ __global__ __launch_bounds__(256) void large_syrk(DevView d, LargeView<T> lv, in
         if (b >= nfilters || skipped[b])
                 return;
         const int n = d.n[b], NP = lv.NP;
-        const int na = large_blocks(n) * LB;
+        const int na = large_blocks(n, lv.xrows) * LB;
         const int tl = slot % nlow;
         int rt = (int)((sqrtf(8.0f * (float)tl + 1.0f) - 1.0f) * 0.5f);
         while ((rt + 1) * (rt + 2) / 2 <= tl)

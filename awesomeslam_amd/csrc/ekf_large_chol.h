@@ -249,7 +249,7 @@ template <typename T> __global__ __launch_bounds__(256) void large_potrf_inv_til
         if (skipped[b])
                 return;
         const int n = d.n[b], NP = lv.NP;
-        if (k >= large_blocks(n))
+        if (k >= large_blocks(n, lv.xrows))
                 return;
         T *S = lv.S + (size_t)b * NP * NP + (size_t)k * LB * NP + k * LB;
         T *Li = lv.Linv + ((size_t)b * LARGE_NB_MAX + k) * LB * LB;

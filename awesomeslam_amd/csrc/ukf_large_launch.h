@@ -1,0 +1,112 @@
+// ukf_large_launch.h -- host side of the large-state UKF (ukf_large.h), included by aslam_core.hip: the launch plan (ukf_large_plan() is the ONE
+// place that says how many launches a callback is -- the launcher walks it, aslam_get_launch_info and aslam_kernel_info report it), views
+// shifted to a trajectory, and the chain launcher.  One stream: the caller's (no stream groups on this path).
+#pragma once
+
+#include "ekf_large_launch.h"
+#include "ukf_large.h"
+
+namespace aslam
+{
+/// the launches of one callback, in order (NB = NP / 64 block columns)
+struct UkfLargePlan
+{
+        int NB;
+        int frontend;  // ukf_large_frontend_kernel                                                             1
+        int chol_p;    // NB x large_potrf_inv_tiles + (NB - 1) x large_update_panel(s_only) over the copy of P  2 NB - 1
+        int sigma;     // ukf_large_sigma_pose, ukf_large_points                                                 2
+        int products;  // ukf_large_wabt: P, S+, Tc                                                              3
+        int solve;     // NB x {large_potrf_inv_tiles, large_update_panel} over [S+; Tc; z^T; (Z - Zpred)^T]     2 NB
+        int update;    // ukf_large_gain, large_syrk, ukf_large_rank1                                            3
+        int launches;  // 4 NB + 8
+};
+
+inline UkfLargePlan ukf_large_plan(int NP)
+{
+        UkfLargePlan p = {};
+        p.NB = NP / LB;
+        p.frontend = 1;
+        p.chol_p = 2 * p.NB - 1;
+        p.sigma = 2;
+        p.products = 3;
+        p.solve = 2 * p.NB;
+        p.update = 3;
+        p.launches = p.frontend + p.chol_p + p.sigma + p.products + p.solve + p.update;
+        return p;
+}
+
+inline UkfLargeView shifted(UkfLargeView v, size_t b, int NP)
+{
+        const size_t np = (size_t)NP, mp = (size_t)v.MP;
+        v.D += b * np * mp;
+        v.DZ += b * np * mp;
+        v.XP += b * 3 * mp;
+        v.Xbar += b * np;
+        v.sc += b * 8;
+        return v;
+}
+
+/// `nsteps` callbacks of a large-state UKF context: one trajectory (MODE_STEP with sa.traj >= 0) or the whole batch
+template <int MODE>
+hipError_t launch_ukf_large(LargeHost &h, const DevView &dv0, const LargeView<double> &lv0, const UkfLargeView &uv0, int *skipped0, int64_t t0, int nsteps,
+                            double *poses, int32_t *dims, StepArgs sa, hipStream_t st)
+{
+        const int NP = dv0.NP;
+        const size_t lds = LargeLds::bytes(NP);
+        if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(ukf_large_frontend_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
+                return e;
+        const bool one = MODE == MODE_STEP && sa.traj >= 0; // sa.traj < 0: the batched step
+        const size_t first = one ? (size_t)sa.traj : 0;
+        const int gb = one ? 1 : dv0.B;
+        sa.traj = one ? 0 : sa.traj; // (the views start at the trajectory)
+        const DevView dv = shifted(dv0, first, MODE == MODE_REPLAY);
+        const LargeView<double> lv = shifted(lv0, first);
+        const UkfLargeView uv = shifted(uv0, first, NP);
+        int *skip = skipped0 + first;
+        const UkfLargePlan plan = ukf_large_plan(NP);
+        const int NB = plan.NB;
+        const int ntile = (NP + 127) / 128;
+        const int fgroups = (gb + 7) / 8; // ukf_large_wabt and large_syrk deal filters to the 8 XCDs
+        h.last_plan = {};
+        h.last_plan.chain = LargeChain::F64_LEFT;
+        h.last_plan.launches = plan.launches;
+        h.last_groups = 1;
+        for (int s = 0; s < nsteps; ++s)
+        {
+                int count = 0;
+                hipLaunchKernelGGL((ukf_large_frontend_kernel<MODE>), dim3(gb), dim3(SMALL_WG), lds, st, dv, lv, uv, t0 + s, s, nsteps, poses, dims, sa, skip);
+                count += plan.frontend;
+                for (int k = 0; k < NB; ++k) // L = chol(P) in S
+                {
+                        hipLaunchKernelGGL(large_potrf_inv_tiles<double>, dim3(gb), dim3(256), 0, st, dv, lv, k, skip);
+                        ++count;
+                        if (k + 1 < NB)
+                        {
+                                hipLaunchKernelGGL(large_update_panel<double>, dim3((NB - k) / 2, 1, gb), dim3(256), 0, st, dv, lv, k, 1, skip);
+                                ++count;
+                        }
+                }
+                hipLaunchKernelGGL(ukf_large_sigma_pose, dim3(gb), dim3(256), 0, st, dv, lv, uv, skip);
+                hipLaunchKernelGGL(ukf_large_points, dim3(NP / 2, gb), dim3(256), 0, st, dv, lv, uv, skip);
+                count += plan.sigma;
+                for (int mode : {WABT_P, WABT_S, WABT_TC})
+                {
+                        hipLaunchKernelGGL(ukf_large_wabt, dim3(8 * ukf_wabt_tiles(NP, mode) * fgroups), dim3(256), 0, st, dv, lv, uv, mode, gb, skip);
+                        ++count;
+                }
+                for (int k = 0; k < NB; ++k) // S+ = L L^T, W = Tc L^-T, q = L^-1 z, t = L^-1 (Z - Zpred)
+                {
+                        hipLaunchKernelGGL(large_potrf_inv_tiles<double>, dim3(gb), dim3(256), 0, st, dv, lv, k, skip);
+                        hipLaunchKernelGGL(large_update_panel<double>, dim3((2 * NB - k) / 2, 1, gb), dim3(256), 0, st, dv, lv, k, 0, skip);
+                        count += 2;
+                }
+                hipLaunchKernelGGL((ukf_large_gain<MODE>), dim3((NP + 3) / 4, gb), dim3(256), 0, st, dv, lv, uv, s, nsteps, poses, dims, skip);
+                hipLaunchKernelGGL(large_syrk<double>, dim3(8 * (ntile * (ntile + 1) / 2) * fgroups), dim3(256), 0, st, dv, lv, gb, skip);
+                hipLaunchKernelGGL(ukf_large_rank1, dim3((NP + 3) / 4, gb), dim3(256), 0, st, dv, lv, uv, skip);
+                count += plan.update;
+                if (count != plan.launches)
+                        return hipErrorAssert; // the plan and the launcher disagree: a bug, not a run-time condition
+        }
+        return hipGetLastError();
+}
+} // namespace aslam

@@ -12,7 +12,8 @@
  * error, text via aslam_last_error()); no exceptions cross the seam.  A context owns all filter state
  * for `batch` independent filters ("trajectories") in HBM; matrices are row-major.  One HIP stream per
  * call (the `stream` argument is a hipStream_t passed as void*, NULL = the default stream); a context
- * is not re-entrant.  Everything is fp64 unless the context was created with ASLAM_F32.
+ * is not re-entrant.  Everything is fp64 unless the context was created with ASLAM_F32 (EKF only: the UKF is
+ * fp64 at every size -- the single-CU kernels up to N = 143, the ASLAM_CFG_UKF_LARGE launch chain beyond).
  */
 #ifndef ASLAM_CORE_H
 #define ASLAM_CORE_H
@@ -57,6 +58,13 @@ enum
                                         this filter's state is invalid from that callback on */
 };
 
+/* aslam_config.flags */
+enum
+{
+        ASLAM_CFG_UKF_LARGE = 1 /* accept a UKF context beyond the single-CU kernels (144 <= N): fp64 launch chain.
+                                   The reference's central weight is (1-N)/3: see DESIGN.md before running long horizons */
+};
+
 typedef struct aslam_ctx aslam_ctx;
 
 typedef struct
@@ -69,7 +77,9 @@ typedef struct
         int32_t max_obs;            /* capacity of the stored sensor message (sensor_landmark, ekf.h:102) */
         int32_t max_wait;           /* capacity of new_landmark_wait (ekf.h:105); the reference's is unbounded */
         int32_t device;             /* HIP device ordinal */
-        int32_t reserved;
+        int32_t flags;              /* 0 or ASLAM_CFG_* bits; any other bit is ASLAM_ERR_ARG.  ASLAM_CFG_UKF_LARGE: with filter = UKF,
+                                       dtype = F64 and a max_landmark_count of 145 .. 1087 a large-state UKF context instead of
+                                       ASLAM_ERR_UNSUPPORTED; no effect on smaller UKF contexts and on the EKF */
 } aslam_config;
 
 /* A recorded input stream for `batch` filters x T callbacks, already narrowed the way the node's

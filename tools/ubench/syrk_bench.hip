@@ -91,6 +91,7 @@ int main(int argc, char **argv)
         d.B = B, d.NP = NP, d.n = dn;
         LargeView<float> lv = {};
         lv.NP = NP, lv.P = dP, lv.G = dG;
+        lv.xrows = 1;
         const int ntile = (NP + 127) / 128;
         const dim3 grid(8 * (ntile * (ntile + 1) / 2) * ((B + 7) / 8));
         // ---- correctness: one launch on P = 0 -> P = -V V^T (lower + mirror), filters 0 and B - 1

@@ -138,6 +138,7 @@ int main(int argc, char **argv)
         d.n = dn;
         LargeView<float> lv = {};
         lv.NP = NP;
+        lv.xrows = 1;
         lv.P = dP;
         lv.G = dG;
         lv.S = dS;
