@@ -26,11 +26,12 @@ CORE_SYMBOLS = (
     "aslam_grow", "aslam_ekf_step", "aslam_ukf_step", "aslam_ekf_step_batch", "aslam_ukf_step_batch", "aslam_set_trace", "aslam_replay", "aslam_get_dim",
     "aslam_get_state", "aslam_get_A", "aslam_get_landmarks", "aslam_get_wait", "aslam_get_status",
     "aslam_get_layout", "aslam_kernel_info", "aslam_get_launch_info",
+    "aslam_replay_stats", "aslam_innovation_enable", "aslam_get_innovation",
 )
 NODE_SYMBOLS = (
     "aslam_node_create", "aslam_node_create_at", "aslam_node_destroy", "aslam_node_error", "aslam_node_sensor", "aslam_node_odom",
     "aslam_node_odom_now", "aslam_node_dim", "aslam_node_get", "aslam_node_wait", "aslam_node_core",
-    "aslam_host_narrow_odom",
+    "aslam_host_narrow_odom", "aslam_node_enable_innovation", "aslam_node_innovation",
 )
 TRACE_FILE_SYMBOLS = (
     "aslam_trace_file_open", "aslam_trace_file_close", "aslam_trace_file_error", "aslam_trace_file_dims",
@@ -133,6 +134,9 @@ def core_lib():
         L.aslam_ukf_step_batch.argtypes = [vp, pf, pf, pf, pd, ci, pd, ci, vp]
         L.aslam_set_trace.argtypes = [vp, ctypes.POINTER(TraceView)]
         L.aslam_replay.argtypes = [vp, ctypes.c_int64, ctypes.c_int64, vp, vp, vp]
+        L.aslam_replay_stats.argtypes = [vp, ctypes.c_int64, ctypes.c_int64, vp, vp, vp, vp, vp, vp]
+        L.aslam_innovation_enable.argtypes = [vp, ci]
+        L.aslam_get_innovation.argtypes = [vp, ci, pd, pd]
         L.aslam_get_dim.argtypes = [vp, ci, pi]
         L.aslam_get_state.argtypes = [vp, ci, pd, pd, pd]
         L.aslam_get_A.argtypes = [vp, ci, pd, pd]
@@ -170,6 +174,8 @@ def node_lib():
         L.aslam_node_core.restype = vp
         L.aslam_node_core.argtypes = [vp]
         L.aslam_host_narrow_odom.argtypes = [ctypes.c_int64, pd, pd, pf, pd]
+        L.aslam_node_enable_innovation.argtypes = [vp, ci]
+        L.aslam_node_innovation.argtypes = [vp, pd, pd]
         # include/aslam_trace_file.h
         L.aslam_trace_file_error.restype = ctypes.c_char_p
         L.aslam_trace_file_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
@@ -405,6 +411,22 @@ class Core:
         """Asynchronous.  poses_ptr / dims_ptr: raw device pointers ([batch][nsteps][3] f64, [batch][nsteps] i32)."""
         _chk(core_lib().aslam_replay(self._h, int(t0), int(nsteps), poses_ptr, dims_ptr, stream))
 
+    def replay_stats(self, t0, nsteps, poses_ptr=None, dims_ptr=None, nis_ptr=None, logdet_ptr=None, pose_cov_ptr=None, stream=None):
+        """replay() with the innovation statistics of every callback (aslam_replay_stats).  Raw device pointers, all optional:
+        nis_ptr, logdet_ptr [batch][nsteps] f64 (y^T S^-1 y, ln|det S|), pose_cov_ptr [batch][nsteps][6] f64 (the lower triangle of the
+        pose block of P after the update).  NaN where slam() did not run."""
+        _chk(core_lib().aslam_replay_stats(self._h, int(t0), int(nsteps), poses_ptr, dims_ptr, nis_ptr, logdet_ptr, pose_cov_ptr, stream))
+
+    def enable_innovation(self, on=True):
+        """Keep (nis, logdet) of every filter's last callback for innovation() (aslam_innovation_enable); off by default."""
+        _chk(core_lib().aslam_innovation_enable(self._h, 1 if on else 0))
+
+    def innovation(self, traj=0):
+        """(nis, logdet) of filter `traj`'s last callback; synchronises.  AslamError (ASLAM_ERR_STATE) unless enable_innovation() was called."""
+        a, b = ctypes.c_double(), ctypes.c_double()
+        _chk(core_lib().aslam_get_innovation(self._h, traj, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
     # ---- read-back
     def dim(self, traj=0):
         n = ctypes.c_int()
@@ -514,6 +536,18 @@ class Node:
         core = ctypes.c_void_p(node_lib().aslam_node_core(self._h))
         _chk(core_lib().aslam_get_state(core, 0, None, None, _ptr(P, ctypes.c_double)))
         return P
+
+    def enable_innovation(self, on=True):
+        """Keep (nis, logdet) of the last callback (aslam_node_enable_innovation); off by default."""
+        if node_lib().aslam_node_enable_innovation(self._h, 1 if on else 0) != 0:
+            raise AslamError(node_lib().aslam_node_error().decode())
+
+    def innovation(self):
+        """(nis, logdet) of the last odometry callback: NaN when slam() did not run in it."""
+        a, b = ctypes.c_double(), ctypes.c_double()
+        if node_lib().aslam_node_innovation(self._h, ctypes.byref(a), ctypes.byref(b)) != 0:
+            raise AslamError(node_lib().aslam_node_error().decode())
+        return a.value, b.value
 
     def wait_list(self, cap=4096):
         r, b, c = np.empty(cap, np.float32), np.empty(cap, np.float32), np.empty(cap, np.uint32)

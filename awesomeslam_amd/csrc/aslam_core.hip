@@ -71,6 +71,9 @@ struct aslam_ctx
         float *step_in = nullptr; // [3][batch] vx, az, dt of a batched step
         double *largeP = nullptr; // = lv64.P or lv32.P: the covariance is binary64 in both modes
         LargeHost lh; // knobs, streams of the stream groups, what the last launch did (ekf_large_launch.h)
+        // aslam_innovation_enable: [batch][2] (nis, logdet) of every filter's last callback, allocated by the first enable; off by default
+        double *innov = nullptr;
+        bool innov_on = false;
 };
 
 namespace
@@ -197,13 +200,13 @@ int init_state(aslam_ctx *c)
         return seed_pose_block(d.P, B, NP);
 }
 
-template <int NT, int MODE>
-int launch_ekf(aslam_ctx *c, int grid, int64_t t0, int nsteps, double *poses, int32_t *dims, StepArgs sa, hipStream_t st)
+template <int NT, int MODE, bool STATS>
+int launch_ekf(aslam_ctx *c, int grid, int64_t t0, int nsteps, double *poses, int32_t *dims, StepArgs sa, hipStream_t st, StatsView sv)
 {
-        auto kern = ekf_small_kernel<NT, MODE>;
+        auto kern = ekf_small_kernel<NT, MODE, STATS>;
         const size_t lds = SmallLayout<NT>::total;
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(SMALL_WG), lds, st, c->dv, t0, nsteps, poses, dims, sa);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(SMALL_WG), lds, st, c->dv, t0, nsteps, poses, dims, sa, sv);
         HIP_TRY(hipGetLastError());
         return ASLAM_OK;
 }
@@ -225,13 +228,13 @@ int ukf_alloc(aslam_ctx *c)
         return rc;
 }
 
-template <int NT, int MODE>
-int launch_ukf(aslam_ctx *c, int grid, int64_t t0, int nsteps, double *poses, int32_t *dims, StepArgs sa, hipStream_t st)
+template <int NT, int MODE, bool STATS>
+int launch_ukf(aslam_ctx *c, int grid, int64_t t0, int nsteps, double *poses, int32_t *dims, StepArgs sa, hipStream_t st, StatsView sv)
 {
-        auto kern = ukf_small_kernel<NT, MODE>;
+        auto kern = ukf_small_kernel<NT, MODE, STATS>;
         const size_t lds = UkfLayout<NT>::total;
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(SMALL_WG), lds, st, c->dv, c->ukf, t0, nsteps, poses, dims, sa);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(SMALL_WG), lds, st, c->dv, c->ukf, t0, nsteps, poses, dims, sa, sv);
         HIP_TRY(hipGetLastError());
         return ASLAM_OK;
 }
@@ -243,28 +246,52 @@ template <typename F> auto with_NT(int NT, F &&f)
         return NT == 2 ? f(std::integral_constant<int, 2>{}) : NT == 5 ? f(std::integral_constant<int, 5>{}) : f(std::integral_constant<int, 9>{});
 }
 
+/// `sv`: the statistics this launch writes (all null: none).  The single-CU kernels have an instantiation of their own for it, the large-state
+/// chains one more launch per callback (large_stats); without statistics both run exactly what they ran before.
 template <int MODE>
-int launch(aslam_ctx *c, int grid, int64_t t0, int nsteps, double *poses, int32_t *dims, StepArgs sa, hipStream_t st)
+int launch(aslam_ctx *c, int grid, int64_t t0, int nsteps, double *poses, int32_t *dims, StepArgs sa, hipStream_t st, StatsView sv = {})
 {
 #if ASLAM_HAVE_UKF
         if (c->large && c->cfg.filter == ASLAM_UKF)
         {
-                HIP_TRY(launch_ukf_large<MODE>(c->lh, c->dv, c->lv64, c->ukfl, c->skipped, t0, nsteps, poses, dims, sa, st));
+                HIP_TRY(launch_ukf_large<MODE>(c->lh, c->dv, c->lv64, c->ukfl, c->skipped, t0, nsteps, poses, dims, sa, st, sv));
                 return ASLAM_OK;
         }
 #endif
         if (c->large)
                 return with_large_view(c, [&](auto &lv) -> int {
-                        HIP_TRY(launch_large<MODE>(c->lh, c->dv, lv, c->skipped, t0, nsteps, poses, dims, sa, st));
+                        HIP_TRY(launch_large<MODE>(c->lh, c->dv, lv, c->skipped, t0, nsteps, poses, dims, sa, st, sv));
                         return ASLAM_OK;
                 });
         if (c->cfg.filter == ASLAM_EKF)
-                return with_NT(c->NT, [&](auto nt) { return launch_ekf<decltype(nt)::value, MODE>(c, grid, t0, nsteps, poses, dims, sa, st); });
+                return with_NT(c->NT, [&](auto nt) {
+                        return sv.any() ? launch_ekf<decltype(nt)::value, MODE, true>(c, grid, t0, nsteps, poses, dims, sa, st, sv)
+                                        : launch_ekf<decltype(nt)::value, MODE, false>(c, grid, t0, nsteps, poses, dims, sa, st, sv);
+                });
 #if ASLAM_HAVE_UKF
         if (c->cfg.filter == ASLAM_UKF)
-                return with_NT(c->NT, [&](auto nt) { return launch_ukf<decltype(nt)::value, MODE>(c, grid, t0, nsteps, poses, dims, sa, st); });
+                return with_NT(c->NT, [&](auto nt) {
+                        return sv.any() ? launch_ukf<decltype(nt)::value, MODE, true>(c, grid, t0, nsteps, poses, dims, sa, st, sv)
+                                        : launch_ukf<decltype(nt)::value, MODE, false>(c, grid, t0, nsteps, poses, dims, sa, st, sv);
+                });
 #endif
         return fail(ASLAM_ERR_UNSUPPORTED, "no kernel for this filter/size");
+}
+
+/// what the per-callback seams and aslam_replay write besides their own outputs: the last-callback record when it is switched on
+StatsView innovation_view(const aslam_ctx *c)
+{
+        return StatsView{nullptr, nullptr, nullptr, c->innov_on ? c->innov : nullptr};
+}
+
+/// the record of every filter to NaN ("no callback yet")
+int clear_innovation(aslam_ctx *c)
+{
+        if (!c->innov)
+                return ASLAM_OK;
+        const std::vector<double> nan(2 * (size_t)c->cfg.batch, std::nan(""));
+        HIP_TRY(hipMemcpy(c->innov, nan.data(), sizeof(double) * nan.size(), hipMemcpyHostToDevice));
+        return ASLAM_OK;
 }
 
 /// the typed buffers of a large-state context, in this order (addresses follow from it)
@@ -468,7 +495,8 @@ int aslam_reset(aslam_ctx *c)
         int rc = sync_ctx(c);
         if (rc != ASLAM_OK)
                 return rc;
-        return init_state(c);
+        rc = init_state(c);
+        return rc != ASLAM_OK ? rc : clear_innovation(c); // (the setting of aslam_innovation_enable stays)
 }
 
 int aslam_set_state(aslam_ctx *c, int traj, int n, const double *X, const double *Z, const double *P)
@@ -557,7 +585,7 @@ int step_one(aslam_ctx *c, int filter, int traj, float vx, float az, float dt, c
         if (A)
                 HIP_TRY(hipMemcpyAsync(d.A + 2 * traj, A, 2 * sizeof(double), hipMemcpyHostToDevice, st));
         StepArgs sa{traj, vx, az, dt};
-        rc = launch<MODE_STEP>(c, 1, 0, 1, nullptr, nullptr, sa, st);
+        rc = launch<MODE_STEP>(c, 1, 0, 1, nullptr, nullptr, sa, st, innovation_view(c));
         if (rc != ASLAM_OK)
                 return rc;
         if (X_out)
@@ -611,7 +639,7 @@ int step_batch(aslam_ctx *c, int filter, const float *vx, const float *az, const
                 HIP_TRY(hipMemcpy2DAsync(d.A + 1, 2 * sizeof(double), a10, sizeof(double), sizeof(double), B, hipMemcpyHostToDevice, st));
         }
         StepArgs sa{-1, 0.f, 0.f, 0.f};
-        int rc = launch<MODE_STEP>(c, B, 0, 1, nullptr, nullptr, sa, st);
+        int rc = launch<MODE_STEP>(c, B, 0, 1, nullptr, nullptr, sa, st, innovation_view(c));
         if (rc != ASLAM_OK)
                 return rc;
         if (X_out)
@@ -688,6 +716,12 @@ int aslam_set_trace(aslam_ctx *c, const aslam_trace *tr)
 
 int aslam_replay(aslam_ctx *c, int64_t t0, int64_t nsteps, double *poses_out, int32_t *dims_out, void *stream)
 {
+        return aslam_replay_stats(c, t0, nsteps, poses_out, dims_out, nullptr, nullptr, nullptr, stream);
+}
+
+int aslam_replay_stats(aslam_ctx *c, int64_t t0, int64_t nsteps, double *poses_out, int32_t *dims_out, double *nis_out, double *logdet_out,
+                       double *pose_cov_out, void *stream)
+{
         if (!c)
                 return fail(ASLAM_ERR_ARG, "null context");
         if (!c->dv.tr_pose)
@@ -697,7 +731,44 @@ int aslam_replay(aslam_ctx *c, int64_t t0, int64_t nsteps, double *poses_out, in
         hipStream_t st = static_cast<hipStream_t>(stream);
         c->last_stream = st;
         StepArgs sa{0, 0.f, 0.f, 0.f};
-        return launch<MODE_REPLAY>(c, c->cfg.batch, t0, (int)nsteps, poses_out, dims_out, sa, st);
+        StatsView sv = innovation_view(c);
+        sv.nis = nis_out, sv.logdet = logdet_out, sv.pcov = pose_cov_out;
+        return launch<MODE_REPLAY>(c, c->cfg.batch, t0, (int)nsteps, poses_out, dims_out, sa, st, sv);
+}
+
+int aslam_innovation_enable(aslam_ctx *c, int on)
+{
+        if (!c)
+                return fail(ASLAM_ERR_ARG, "null context");
+        int rc = sync_ctx(c);
+        if (rc != ASLAM_OK)
+                return rc;
+        if (on && !c->innov && (rc = dev_alloc(c, &c->innov, 2 * (size_t)c->cfg.batch, c->owned)) != ASLAM_OK)
+                return rc;
+        // every switch from off to on starts from NaN: what a callback before the switch left behind is not "the last callback"
+        if (on && !c->innov_on && (rc = clear_innovation(c)) != ASLAM_OK)
+                return rc;
+        c->innov_on = on != 0;
+        return ASLAM_OK;
+}
+
+int aslam_get_innovation(aslam_ctx *c, int traj, double *nis, double *logdet)
+{
+        int rc = check_traj(c, traj);
+        if (rc != ASLAM_OK)
+                return rc;
+        if (!c->innov_on)
+                return fail(ASLAM_ERR_STATE, "the innovation record is off (aslam_innovation_enable)");
+        rc = sync_ctx(c);
+        if (rc != ASLAM_OK)
+                return rc;
+        double v[2];
+        HIP_TRY(hipMemcpy(v, c->innov + 2 * (size_t)traj, sizeof(v), hipMemcpyDeviceToHost));
+        if (nis)
+                *nis = v[0];
+        if (logdet)
+                *logdet = v[1];
+        return ASLAM_OK;
 }
 
 int aslam_get_dim(aslam_ctx *c, int traj, int *n)

@@ -1617,6 +1617,63 @@ __global__ __launch_bounds__(256) void large_x_update_rows(DevView d, LargeView<
                 return;
         x_update_rows_body<MODE>(sh, d, lv, b, (int)blockIdx.x, d.n[b], s, nsteps, poses_out, dims_out);
 }
+
+/// The statistics of a callback (StatsView), launched behind the chain only when somebody asks for them: every chain leaves what they need.
+///   EKF: row n of G (lv.G as the consumers of V see it) is q = (L^-1 Y)^T:  Y^T S^-1 Y = q.q
+///   UKF (lv.xrows == 2): rows n, n + 1 are q = L^-1 z and t = L^-1 (Z - Zpred) for S = S+ - z z^T, S+ = L L^T (ukf_large.h):
+///        NIS = t.t + (q.t)^2 / (1 - q.q),   det S = det S+ (1 - q.q)
+///   ln det L L^T = -2 sum ln Linv_ii: the inverted diagonal blocks exist in T in every chain (the bf16-pipe Cholesky writes them too)
+/// Every entry is widened to binary64 before it is multiplied; the sums are binary64.  grid (B), 256 threads.
+template <typename T>
+__global__ __launch_bounds__(256) void large_stats(DevView d, LargeView<T> lv, int s, int nsteps, StatsView sv, const int *skipped)
+{
+        __shared__ double red[4][4];
+        const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+        if (skipped[b])
+        {
+                stats_skip(sv, b, s, nsteps, tid);
+                return;
+        }
+        const int n = d.n[b], NP = lv.NP;
+        const bool ukf = lv.xrows == 2;
+        const T *q = lv.G + ((size_t)b * NP + n) * NP, *t = q + NP;
+        const T *Li = lv.Linv + (size_t)b * LARGE_NB_MAX * LB * LB;
+        double tt = 0.0, qq = 0.0, qt = 0.0, ld = 0.0;
+        for (int j0 = 0; j0 < NP; j0 += 256) // (the same trip count in every lane: the DPP sums below need the whole wave)
+        {
+                const int j = j0 + tid;
+                const bool in = j < n;
+                const int jc = in ? j : 0;
+                const double qv = in ? (double)q[jc] : 0.0;
+                const double tv = (in && ukf) ? (double)t[jc] : 0.0;
+                const double di = in ? (double)Li[(size_t)(jc >> 6) * LB * LB + (jc & (LB - 1)) * (LB + 1)] : 1.0;
+                qq = fma(qv, qv, qq);
+                qt = fma(qv, tv, qt);
+                tt = fma(tv, tv, tt);
+                ld += log(di);
+        }
+        qq = wave_sum_dpp(qq), qt = wave_sum_dpp(qt), tt = wave_sum_dpp(tt), ld = wave_sum_dpp(ld);
+        if (lane == 63)
+                red[tid >> 6][0] = qq, red[tid >> 6][1] = qt, red[tid >> 6][2] = tt, red[tid >> 6][3] = ld;
+        __syncthreads();
+        if (tid == 0)
+        {
+                double r[4];
+                for (int k = 0; k < 4; ++k)
+                        r[k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+                const double den = 1.0 - r[0];
+                double nis = ukf ? r[2] + r[1] * r[1] / den : r[0];
+                double logdet = ukf ? -2.0 * r[3] + log(fabs(den)) : -2.0 * r[3];
+                if (d.status[b] & 4u) // ASLAM_ST_NOT_PD (sticky): no statistics from a factor that does not exist
+                        nis = logdet = __builtin_nan("");
+                stats_put(sv, b, s, nsteps, nis, logdet);
+        }
+        if (tid < 6)
+        {
+                const int r = tid < 1 ? 0 : tid < 3 ? 1 : 2;
+                stats_put_pcov(sv, b, s, nsteps, tid, lv.P[(size_t)b * NP * NP + (size_t)r * NP + tid - r * (r + 1) / 2]);
+        }
+}
 } // namespace aslam
 
 #include "ekf_large_trsm.h"

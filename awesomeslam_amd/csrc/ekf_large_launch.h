@@ -152,6 +152,20 @@ template <typename T> LargeView<T> shifted(LargeView<T> v, size_t b)
         return v;
 }
 
+/// the per-callback arrays are [B][nsteps]-shaped, the last-callback record [B][2]
+inline StatsView shifted(StatsView sv, size_t b, int nsteps)
+{
+        if (sv.nis)
+                sv.nis += b * (size_t)nsteps;
+        if (sv.logdet)
+                sv.logdet += b * (size_t)nsteps;
+        if (sv.pcov)
+                sv.pcov += b * (size_t)nsteps * 6;
+        if (sv.last)
+                sv.last += 2 * b;
+        return sv;
+}
+
 template <typename T> struct LargeGroup
 {
         DevView dv;
@@ -161,6 +175,7 @@ template <typename T> struct LargeGroup
         int32_t *dims;
         int nb;
         hipStream_t st;
+        StatsView sv; // statistics asked for with this launch (all null: none, and no large_stats launch)
 };
 
 /// callback s of one group: front end + predict, G, S, blocked factorisation of [S; G; Y^T], P -= V V^T, X += V q
@@ -184,6 +199,8 @@ void launch_large_chain(const LargePlan &plan, const LargeGroup<T> &g, size_t ld
                 }
                 hipLaunchKernelGGL(large_syrk<T>, syrk_grid, dim3(256), 0, g.st, g.dv, g.v, gb, g.skip);
                 hipLaunchKernelGGL((large_x_update<T, MODE, false>), dim3((NP + 3) / 4, gb), dim3(256), 0, g.st, g.dv, g.v, s, nsteps, g.poses, g.dims, g.skip);
+                if (g.sv.any())
+                        hipLaunchKernelGGL(large_stats<T>, dim3(gb), dim3(256), 0, g.st, g.dv, g.v, s, nsteps, g.sv, g.skip);
         }
         else
         {
@@ -228,14 +245,17 @@ void launch_large_chain(const LargePlan &plan, const LargeGroup<T> &g, size_t ld
                 // (profiles/r04_experiments.md section 1)
                 hipLaunchKernelGGL((large_x_update_rows<MODE>), dim3((NP + 4 * XU_ROWS - 1) / (4 * XU_ROWS), gb), dim3(256), 0, g.st, g.dv, vv, s, nsteps, g.poses,
                                    g.dims, g.skip);
+                if (g.sv.any())
+                        hipLaunchKernelGGL(large_stats<T>, dim3(gb), dim3(256), 0, g.st, g.dv, vv, s, nsteps, g.sv, g.skip);
         }
 }
 
 /// `nsteps` callbacks of a large-state context: one trajectory (MODE_STEP with sa.traj >= 0) or the whole batch, which from max(32, 8 x groups)
-/// filters on is split into stream groups.  The enqueue order (callbacks outermost, groups innermost) is what the rates were measured with
+/// filters on is split into stream groups.  The enqueue order (callbacks outermost, groups innermost) is what the rates were measured with.
+/// `sv`: statistics to write (one launch more per callback, reported in last_plan.launches), all null for none
 template <int MODE, typename T>
 hipError_t launch_large(LargeHost &h, const DevView &dv, const LargeView<T> &lv, int *skipped, int64_t t0, int nsteps, double *poses, int32_t *dims,
-                        StepArgs sa, hipStream_t st)
+                        StepArgs sa, hipStream_t st, StatsView sv = {})
 {
         const size_t lds = LargeLds::bytes(dv.NP);
         if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(large_frontend_kernel<T, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
@@ -249,12 +269,13 @@ hipError_t launch_large(LargeHost &h, const DevView &dv, const LargeView<T> &lv,
         const int per = split ? ((Bz + NG - 1) / NG + 7) & ~7 : Bz; // multiples of 8: large_syrk deals filters to the 8 XCDs
         LargeGroup<T> g[LARGE_GROUPS_MAX];
         h.last_plan = plan;
+        h.last_plan.launches += sv.any() ? 1 : 0; // large_stats
         h.last_groups = 0;
         for (int q = 0; q < NG; ++q)
         {
                 const int o = std::min(q * per, Bz);
                 const size_t b0 = (size_t)(first + o);
-                g[q] = {shifted(dv, b0, MODE == MODE_REPLAY), shifted(lv, b0), skipped + b0, poses, dims, std::min(per, Bz - o), q == 0 ? st : h.aux[q - 1]};
+                g[q] = {shifted(dv, b0, MODE == MODE_REPLAY), shifted(lv, b0), skipped + b0, poses, dims, std::min(per, Bz - o), q == 0 ? st : h.aux[q - 1], shifted(sv, b0, nsteps)};
                 if (MODE == MODE_REPLAY && poses)
                         g[q].poses += b0 * (size_t)nsteps * 3;
                 if (MODE == MODE_REPLAY && dims)

@@ -131,9 +131,10 @@ template <bool FWD> __device__ __forceinline__ void congruence_tiles(double *Lt,
         __syncthreads();
 }
 
-template <int NT, int MODE>
+/// STATS: also the innovation statistics of every callback and the pose block of P (StatsView); the STATS = false instantiations do not read `sv`.
+template <int NT, int MODE, bool STATS = false>
 __global__ __launch_bounds__(SMALL_WG) void ekf_small_kernel(DevView d, int64_t t0, int nsteps, double *poses_out,
-                                                              int32_t *dims_out, StepArgs sa)
+                                                              int32_t *dims_out, StepArgs sa, StatsView sv)
 {
         typedef SmallLayout<NT> LY;
         constexpr int NP = LY::NP, NLM = NP / 2;
@@ -178,7 +179,11 @@ __global__ __launch_bounds__(SMALL_WG) void ekf_small_kernel(DevView d, int64_t 
                 if (MODE == MODE_REPLAY)
                 {
                         if (small_frontend<true, SMALL_OBS_CAP, SMALL_WAIT_CAP, NP / 2, double>(d, L, Pg, NP, b, t, s, nsteps, poses_out, dims_out, tid, Lt))
+                        {
+                                if constexpr (STATS)
+                                        stats_skip(sv, b, s, nsteps, tid);
                                 continue;
+                        }
                 }
                 else
                 {
@@ -294,6 +299,34 @@ __global__ __launch_bounds__(SMALL_WG) void ekf_small_kernel(DevView d, int64_t 
                 ASLAM_STAMP(5);
                 __syncthreads();
                 ASLAM_STAMP(6);
+                if constexpr (STATS)
+                {
+                        // NIS = Y^T S^-1 Y = |t|^2 with t = L^-1 Y (the scratch vector of the solve), ln det S = -2 sum ln (1 / L_ii) from the inverted
+                        // diagonal tiles: both are still in LDS here (the congruence below takes the tile area over, behind the barrier of the X update).
+                        // The last wave has no landmark in the X update; a scalar branch, so the DPP sums run with the whole wave active.
+                        if (__builtin_amdgcn_readfirstlane(tid_launch) >= SMALL_WG - 64)
+                        {
+                                const int lane = tid & 63;
+                                double tt = 0.0, dprod = 1.0; // (at most three diagonal entries per lane, each within a few powers of two of 1: one log of their product)
+#pragma unroll
+                                for (int k = 0; k < (NP + 63) / 64; ++k)
+                                {
+                                        const int j = lane + 64 * k, jc = min(j, NP - 1);
+                                        // (loaded by every lane, then masked: a load under `j < n` is a divergent region with spill code in it)
+                                        const double tv0 = L.sTv[jc], di0 = Dinv[(jc >> 4) * TSZ + (jc & 15) * (TLD + 1)];
+                                        const double tv = j < n ? tv0 : 0.0, di = j < n ? di0 : 1.0;
+                                        tt = fma(tv, tv, tt);
+                                        dprod *= di;
+                                }
+                                double ld = log(dprod);
+                                tt = wave_sum_dpp(tt), ld = wave_sum_dpp(ld);
+                                if (lane == 63)
+                                {
+                                        const bool pd = !(sm.status & 4u); // ASLAM_ST_NOT_PD (sticky): no statistics from a factor that does not exist
+                                        stats_put(sv, b, s, nsteps, pd ? tt : __builtin_nan(""), pd ? -2.0 * ld : __builtin_nan(""));
+                                }
+                        }
+                }
                 // X = X + K Y = X + H^-1 u (ekf.cpp:309)
                 {
                         const double u0 = sU[0], u1 = sU[1], u2 = sU[2];
@@ -319,6 +352,16 @@ __global__ __launch_bounds__(SMALL_WG) void ekf_small_kernel(DevView d, int64_t 
                                 poses_out[((size_t)b * nsteps + s) * 3 + tid] = sX[tid];
                         if (tid == 0 && dims_out)
                                 dims_out[(size_t)b * nsteps + s] = n;
+                }
+                if constexpr (STATS)
+                {
+                        // the pose block of P after the update, from the tiles (tile 0, rows 0 .. 2)
+                        if (tid < 6)
+                        {
+                                const int r = tid < 1 ? 0 : tid < 3 ? 1 : 2;
+                                stats_put_pcov(sv, b, s, nsteps, tid, Lt[r * TLD + tid - r * (r + 1) / 2]);
+                        }
+                        __syncthreads(); // (the next callback's growth writes the tiles)
                 }
         }
 

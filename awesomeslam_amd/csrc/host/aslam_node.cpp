@@ -65,7 +65,7 @@ float quat2euler(float w, float x, float y, float z)
 FilterNode::FilterNode(int filter_, int max_landmark_count, int device, double now_init)
     : filter(filter_), MAX_LANDMARK_COUNT(max_landmark_count), ctx(nullptr), N(3), init_z(true), init_x(true),
       last_time((float)now_init), // ekf.cpp:54: last_time = ros::Time::now().toSec(), a float member (ekf.h:98)
-      growth_refused(false), param_X(3, 0.0), param_Z(3, 0.0), a00(1.0), a10(0.0)
+      growth_refused(false), slam_ran(false), param_X(3, 0.0), param_Z(3, 0.0), a00(1.0), a10(0.0)
 {
         aslam_config cfg = {};
         cfg.filter = filter;
@@ -96,6 +96,7 @@ void FilterNode::cbSensorLandmark(const Landmarks &msg)
 
 bool FilterNode::cbOdom(const Odometry &msg, double now)
 {
+        slam_ran = false;
         if (init_z)
                 return false;
         // ekf.cpp:80-81: last_time is a float member
@@ -106,6 +107,7 @@ bool FilterNode::cbOdom(const Odometry &msg, double now)
 
 bool FilterNode::cbOdomDt(const Odometry &msg, float delta_time)
 {
+        slam_ran = false;
         if (init_z)
                 return false;
         updateZ(msg, delta_time);
@@ -116,7 +118,31 @@ bool FilterNode::cbOdomDt(const Odometry &msg, float delta_time)
                 check(aslam_set_state(ctx, 0, (int)N, param_X.data(), nullptr, nullptr), "aslam_set_state");
         }
         slam(msg.vx, msg.wz, delta_time);
+        slam_ran = true;
         return true;
+}
+
+// The innovation record is the one part of the core's ABI this file binds weakly: a stand-in core without it (the oracle-backed one of
+// tests/sanitize/) still links, and the record is then refused like any other call sequence error.
+extern "C" {
+int aslam_innovation_enable(aslam_ctx *, int) __attribute__((weak));
+int aslam_get_innovation(aslam_ctx *, int, double *, double *) __attribute__((weak));
+}
+
+void FilterNode::enableInnovation(bool on)
+{
+        if (!aslam_innovation_enable || !aslam_get_innovation)
+                throw std::runtime_error("this core has no innovation record");
+        check(aslam_innovation_enable(ctx, on ? 1 : 0), "aslam_innovation_enable");
+}
+
+void FilterNode::innovation(double &nis, double &logdet) const
+{
+        if (!aslam_get_innovation)
+                throw std::runtime_error("this core has no innovation record");
+        check(aslam_get_innovation(ctx, 0, &nis, &logdet), "aslam_get_innovation"); // (fails while the record is off)
+        if (!slam_ran)
+                nis = logdet = std::nan(""); // the core still holds the callback before
 }
 
 Landmarks FilterNode::landmarks() const
@@ -380,6 +406,39 @@ int aslam_node_wait(const aslam_node *n, float *range, float *bearing, uint32_t 
 aslam_ctx *aslam_node_core(const aslam_node *n)
 {
         return n->impl->core();
+}
+
+int aslam_node_enable_innovation(aslam_node *n, int on)
+{
+        try
+        {
+                n->impl->enableInnovation(on != 0);
+                return 0;
+        }
+        catch (const std::exception &e)
+        {
+                g_node_err = e.what();
+                return -1;
+        }
+}
+
+int aslam_node_innovation(const aslam_node *n, double *nis, double *logdet)
+{
+        try
+        {
+                double a = 0.0, b = 0.0;
+                n->impl->innovation(a, b);
+                if (nis)
+                        *nis = a;
+                if (logdet)
+                        *logdet = b;
+                return 0;
+        }
+        catch (const std::exception &e)
+        {
+                g_node_err = e.what();
+                return -1;
+        }
 }
 
 void aslam_host_narrow_odom(int64_t count, const double *odom, double *pose, float *yaw, double *twist)

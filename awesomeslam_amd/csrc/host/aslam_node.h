@@ -96,6 +96,13 @@ class FilterNode
         {
                 return growth_refused;
         }
+        /// the innovation statistics of the last odometry callback (aslam_innovation_enable / aslam_get_innovation of the core): y^T S^-1 y and
+        /// ln |det S| of its slam(), NaN when the callback returned before slam().  Off by default; innovation() throws while it is off.
+        /// A deliberate trade-off: aslam_node.cpp binds these two entry points of the core WEAKLY, so that the mirror still links against a
+        /// stand-in core without them (the oracle-backed one of tests/sanitize/); the price is that a core library lacking them is refused
+        /// here, at run time ("this core has no innovation record"), not by the linker.
+        void enableInnovation(bool on);
+        void innovation(double &nis, double &logdet) const;
 
       private:
         int filter;
@@ -107,6 +114,7 @@ class FilterNode
         bool init_x;
         float last_time;
         bool growth_refused;
+        bool slam_ran; // in the last odometry callback
         std::vector<LaserData> sensor_landmark;
         std::vector<std::pair<LaserData, uint32_t>> new_landmark_wait;
         std::vector<double> param_X, param_Z; // host copies; P and the authoritative X are device-resident
@@ -153,6 +161,11 @@ int aslam_node_dim(const aslam_node *n);
 int aslam_node_get(const aslam_node *n, double *X, double *Z, double *a00, double *a10);
 int aslam_node_wait(const aslam_node *n, float *range, float *bearing, uint32_t *count, int cap);
 aslam_ctx *aslam_node_core(const aslam_node *n);
+/* Switch the record of the last callback's innovation statistics on or off (off by default); 0, or -1 with aslam_node_error(). */
+int aslam_node_enable_innovation(aslam_node *n, int on);
+/* y^T S^-1 y and ln |det S| of the last odometry callback's slam() (NaN when that callback returned early, or before the first one);
+ * -1 with aslam_node_error() while the record is off. */
+int aslam_node_innovation(const aslam_node *n, double *nis, double *logdet);
 /* Narrow `count` recorded odometry messages ([count][8]: px,py,qw,qx,qy,qz,vx,wz) the way cbOdom/updateZandA do
  * (ekf.cpp:139-142): pose[count][2], yaw[count] = quat2euler(...) as binary32, twist[count][2]. */
 void aslam_host_narrow_odom(int64_t count, const double *odom, double *pose, float *yaw, double *twist);

@@ -186,6 +186,45 @@ __device__ __forceinline__ double wave_sum_dpp(double x)
         return x;
 }
 
+/// Optional per-callback outputs of a launch (aslam_replay_stats, aslam_innovation_enable): the innovation statistics of slam() and the pose
+/// block of P behind the update.  Every pointer may be null.  A kernel instantiated with STATS = false never looks at it: the instantiations
+/// that run without statistics only carry it as an unused argument.
+struct StatsView
+{
+        double *nis;    // [B][nsteps]    y^T S^-1 y
+        double *logdet; // [B][nsteps]    ln |det S|
+        double *pcov;   // [B][nsteps][6] P(0,0) P(1,0) P(1,1) P(2,0) P(2,1) P(2,2)
+        double *last;   // [B][2]         (nis, logdet) of the filter's last callback
+        __host__ __device__ bool any() const { return nis || logdet || pcov || last; }
+};
+
+/// one lane: the statistics of callback s of filter b
+__device__ __forceinline__ void stats_put(const StatsView &sv, int b, int s, int nsteps, double nis, double logdet)
+{
+        const size_t i = (size_t)b * nsteps + s;
+        if (sv.nis)
+                sv.nis[i] = nis;
+        if (sv.logdet)
+                sv.logdet[i] = logdet;
+        if (sv.last)
+                sv.last[2 * b] = nis, sv.last[2 * b + 1] = logdet;
+}
+/// lanes 0 .. 5 (k) of one wave: entry k of the pose block
+__device__ __forceinline__ void stats_put_pcov(const StatsView &sv, int b, int s, int nsteps, int k, double v)
+{
+        if (sv.pcov)
+                sv.pcov[((size_t)b * nsteps + s) * 6 + k] = v;
+}
+/// a callback in which slam() did not run: NaN everywhere (threads 0 .. 5 of the workgroup)
+__device__ __forceinline__ void stats_skip(const StatsView &sv, int b, int s, int nsteps, int tid)
+{
+        const double nan = __builtin_nan("");
+        if (tid == 0)
+                stats_put(sv, b, s, nsteps, nan, nan);
+        if (tid < 6)
+                stats_put_pcov(sv, b, s, nsteps, tid, nan);
+}
+
 // 16x16 tiles live in LDS with a row stride of 17 doubles: with 16 the MFMA operand pattern [l&15][k] puts the 16
 // lanes of a ds_read2_b64 lane group on ONE bank pair (row stride 128 B = 32 dwords): a 16-way conflict that made
 // LDS, not the MFMA pipe, the bound of the factorisation (measured; profiles/r01_phase_stamps.txt)

@@ -49,7 +49,7 @@ inline UkfLargeView shifted(UkfLargeView v, size_t b, int NP)
 /// `nsteps` callbacks of a large-state UKF context: one trajectory (MODE_STEP with sa.traj >= 0) or the whole batch
 template <int MODE>
 hipError_t launch_ukf_large(LargeHost &h, const DevView &dv0, const LargeView<double> &lv0, const UkfLargeView &uv0, int *skipped0, int64_t t0, int nsteps,
-                            double *poses, int32_t *dims, StepArgs sa, hipStream_t st)
+                            double *poses, int32_t *dims, StepArgs sa, hipStream_t st, StatsView sv0 = {})
 {
         const int NP = dv0.NP;
         const size_t lds = LargeLds::bytes(NP);
@@ -63,13 +63,14 @@ hipError_t launch_ukf_large(LargeHost &h, const DevView &dv0, const LargeView<do
         const LargeView<double> lv = shifted(lv0, first);
         const UkfLargeView uv = shifted(uv0, first, NP);
         int *skip = skipped0 + first;
+        const StatsView sv = shifted(sv0, first, nsteps); // statistics to write (large_stats: one launch more per callback), all null for none
         const UkfLargePlan plan = ukf_large_plan(NP);
         const int NB = plan.NB;
         const int ntile = (NP + 127) / 128;
         const int fgroups = (gb + 7) / 8; // ukf_large_wabt and large_syrk deal filters to the 8 XCDs
         h.last_plan = {};
         h.last_plan.chain = LargeChain::F64_LEFT;
-        h.last_plan.launches = plan.launches;
+        h.last_plan.launches = plan.launches + (sv.any() ? 1 : 0);
         h.last_groups = 1;
         for (int s = 0; s < nsteps; ++s)
         {
@@ -106,6 +107,8 @@ hipError_t launch_ukf_large(LargeHost &h, const DevView &dv0, const LargeView<do
                 count += plan.update;
                 if (count != plan.launches)
                         return hipErrorAssert; // the plan and the launcher disagree: a bug, not a run-time condition
+                if (sv.any())
+                        hipLaunchKernelGGL(large_stats<double>, dim3(gb), dim3(256), 0, st, dv, lv, s, nsteps, sv, skip);
         }
         return hipGetLastError();
 }

@@ -335,9 +335,10 @@ __device__ __forceinline__ void gemm_l_et(const double *Lt, const double *ETg, i
 }
 
 // ------------------------------------------------------------------------------------------------------
-template <int NT, int MODE>
+/// STATS: also the innovation statistics of every callback and the pose block of P (StatsView); the STATS = false instantiations do not read `sv`.
+template <int NT, int MODE, bool STATS = false>
 __global__ __launch_bounds__(SMALL_WG) void ukf_small_kernel(DevView d, UkfView uv, int64_t t0, int nsteps, double *poses_out,
-                                                              int32_t *dims_out, StepArgs sa)
+                                                              int32_t *dims_out, StepArgs sa, StatsView sv)
 {
         typedef SmallLayout<NT> LY;
         typedef UkfLayout<NT> UL;
@@ -380,7 +381,11 @@ __global__ __launch_bounds__(SMALL_WG) void ukf_small_kernel(DevView d, UkfView 
                 if (MODE == MODE_REPLAY)
                 {
                         if (small_frontend<false, SMALL_OBS_CAP, SMALL_WAIT_CAP, NP / 2, double>(d, L, Pg, NP, b, t, s, nsteps, poses_out, dims_out, tid))
+                        {
+                                if constexpr (STATS)
+                                        stats_skip(sv, b, s, nsteps, tid);
                                 continue;
+                        }
                 }
                 else
                 {
@@ -869,6 +874,38 @@ __global__ __launch_bounds__(SMALL_WG) void ukf_small_kernel(DevView d, UkfView 
                 cholesky_forward_rows<NT>(Tcg, Kg, Lt, Dinv, nt, sY, sU, tid, &sm.status, sT, sQ, sGv, n);
 #endif
                 ASLAM_STAMP(8);
+                if constexpr (STATS)
+                {
+                        // The statistics of the full S = S+ - z z^T from the factor of S+ (Sherman-Morrison, as the update itself):
+                        //   Zdiff^T S^-1 Zdiff = t.t + (q.t)^2 / (1 - q.q),   det S = det S+ (1 - q.q),   det S+ = prod L_ii^2
+                        // t, q and the tiles of L are still in LDS here (sT is overwritten behind the barrier below).  One wave, under a scalar
+                        // branch, so the DPP sums run with the whole wave active.
+                        if (__builtin_amdgcn_readfirstlane(tid_launch) >= SMALL_WG - 64)
+                        {
+                                const int lane = tid & 63;
+                                double tt = 0.0, qq = 0.0, qt = 0.0, dprod = 1.0; // (at most three diagonal entries per lane: one log of their product)
+#pragma unroll
+                                for (int k = 0; k < (NP + 63) / 64; ++k)
+                                {
+                                        const int j = lane + 64 * k, jc = min(j, NP - 1);
+                                        // (loaded by every lane, then masked: a load under `j < n` is a divergent region with spill code in it)
+                                        const double tv0 = sT[jc], qv0 = sQ[jc], l0 = *tile_elem(Lt, jc, jc);
+                                        const double tv = j < n ? tv0 : 0.0, qv = j < n ? qv0 : 0.0, lii = j < n ? l0 : 1.0;
+                                        tt = fma(tv, tv, tt);
+                                        qq = fma(qv, qv, qq);
+                                        qt = fma(qv, tv, qt);
+                                        dprod *= lii;
+                                }
+                                double ld = log(dprod);
+                                tt = wave_sum_dpp(tt), qq = wave_sum_dpp(qq), qt = wave_sum_dpp(qt), ld = wave_sum_dpp(ld);
+                                if (lane == 63)
+                                {
+                                        const bool pd = !(sm.status & 4u); // ASLAM_ST_NOT_PD (sticky): no statistics from a factor that does not exist
+                                        const double den = 1.0 - qq;
+                                        stats_put(sv, b, s, nsteps, pd ? tt + qt * qt / den : __builtin_nan(""), pd ? 2.0 * ld + log(fabs(den)) : __builtin_nan(""));
+                                }
+                        }
+                }
                 {
                         // q.q and q.t: the same sums in every wave
                         double qq = 0.0, qt = 0.0;
@@ -916,6 +953,15 @@ __global__ __launch_bounds__(SMALL_WG) void ukf_small_kernel(DevView d, UkfView 
                                 poses_out[((size_t)b * nsteps + s) * 3 + tid] = sX[tid];
                         if (tid == 0 && dims_out)
                                 dims_out[(size_t)b * nsteps + s] = n;
+                }
+                if constexpr (STATS)
+                {
+                        // the pose block of P after the update, from where the update has written it (gemm_wabt ends with a barrier)
+                        if (tid < 6)
+                        {
+                                const int r = tid < 1 ? 0 : tid < 3 ? 1 : 2;
+                                stats_put_pcov(sv, b, s, nsteps, tid, Pg[(size_t)r * NP + tid - r * (r + 1) / 2]);
+                        }
                 }
                 __syncthreads();
         }

@@ -149,6 +149,23 @@ int aslam_set_trace(aslam_ctx *ctx, const aslam_trace *trace);
  * [batch][nsteps][3] f64, may be NULL) receives X(0..2) after each callback; dims_out (device memory,
  * [batch][nsteps] i32, may be NULL) the state dimension N. */
 int aslam_replay(aslam_ctx *ctx, int64_t t0, int64_t nsteps, double *poses_out, int32_t *dims_out, void *stream);
+/* aslam_replay with the innovation statistics of every callback's slam() and the pose covariance behind it (device memory, f64; any of the
+ * three may be NULL, with all three NULL this IS aslam_replay):
+ *   nis_out      [batch][nsteps]     y^T S^-1 y, y the wrapped innovation the filter applies (Y, ekf.cpp:302-307; Zdiff, ukf.cpp:381-388) and
+ *                                    S the filter's own S -- the UKF's full S, central-weight term included: the signed quadratic form
+ *   logdet_out   [batch][nsteps]     ln |det S|
+ *   pose_cov_out [batch][nsteps][6]  P(0,0), P(1,0), P(1,1), P(2,0), P(2,1), P(2,2) after the update
+ * A callback in which slam() did not run (no sensor message yet, ekf.cpp:84-92) has NaN in all three and pose 0.0; a filter whose
+ * ASLAM_ST_NOT_PD bit is set has NaN in nis and logdet.  The large-state paths take one launch more per callback (aslam_get_launch_info)
+ * when a statistic is asked for; the filter itself computes bit for bit what it computes without. */
+int aslam_replay_stats(aslam_ctx *ctx, int64_t t0, int64_t nsteps, double *poses_out, int32_t *dims_out, double *nis_out,
+                       double *logdet_out, double *pose_cov_out, void *stream);
+/* Switch the per-filter record of the LAST callback's (nis, logdet) on or off for aslam_*_step, aslam_*_step_batch and aslam_replay (off by
+ * default; synchronises).  Switching it on (from off) and aslam_reset clear the record to NaN; aslam_reset keeps the setting. */
+int aslam_innovation_enable(aslam_ctx *ctx, int on);
+/* the record of filter `traj` (synchronises like the getters below); ASLAM_ERR_STATE when the record is off; NaN before the first callback
+ * and after a callback in which slam() did not run */
+int aslam_get_innovation(aslam_ctx *ctx, int traj, double *nis, double *logdet);
 
 /* ---- read-back (synchronises the context's last stream) ------------------------------------------- */
 int aslam_get_dim(aslam_ctx *ctx, int traj, int *n);
