@@ -146,6 +146,13 @@ def core_lib():
         L.aslam_get_layout.argtypes = [vp, pi, ctypes.POINTER(ctypes.c_int64)]
         L.aslam_kernel_info.argtypes = [vp, ctypes.c_char_p, ci, pi, pi, pi]
         L.aslam_get_launch_info.argtypes = [vp, pi, pi, pi]
+        # include/aslam_snapshot.h
+        p32, p64 = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)
+        L.aslam_snapshot_record_bytes.restype = ctypes.c_int64
+        L.aslam_snapshot_record_bytes.argtypes = [ci, ci, ci]
+        L.aslam_snapshot_check.argtypes = [vp, ctypes.c_int64, p32, p32]
+        L.aslam_snapshot.argtypes = [vp, p32, ci, vp, ctypes.c_int64, ci, p64, vp]
+        L.aslam_restore.argtypes = [vp, p32, p32, ci, vp, ctypes.c_int64, ci, vp]
         _core = L
     return _core
 
@@ -201,6 +208,8 @@ def _chk(rc):
 
 
 SCAN_SYMBOLS = ("aslam_scan_landmarks",)
+# every symbol include/aslam_snapshot.h declares
+SNAPSHOT_SYMBOLS = ("aslam_snapshot_record_bytes", "aslam_snapshot_check", "aslam_snapshot", "aslam_restore")
 SCAN_BEAMS = 360
 SCAN_REF_ABORT, SCAN_OVERFLOW = 1, 2
 
@@ -464,6 +473,56 @@ class Core:
         s = ctypes.c_uint32()
         _chk(core_lib().aslam_get_status(self._h, traj, ctypes.byref(s)))
         return s.value
+
+    # ---- snapshot / restore (include/aslam_snapshot.h)
+    def snapshot_bytes(self, trajs=None):
+        """Exact size of snapshot(trajs) in bytes (synchronises)."""
+        t = None if trajs is None else np.ascontiguousarray(trajs, np.int32)
+        need = ctypes.c_int64()
+        _chk(core_lib().aslam_snapshot(self._h, _ptr(t, ctypes.c_int32), 0 if t is None else len(t), None, 0, 0, ctypes.byref(need), None))
+        return need.value
+
+    def snapshot(self, trajs=None, out=None, stream=None):
+        """Everything filters `trajs` (default: the whole batch) are, as one blob.  Without `out`: a host uint8 array, complete on return.
+        With `out`, a uint8 torch tensor on the context's device that is large enough (snapshot_bytes): one pack launch on `stream`, the
+        tensor is complete when the stream is; returns `out[:size]`."""
+        t = None if trajs is None else np.ascontiguousarray(trajs, np.int32)
+        cnt = 0 if t is None else len(t)
+        need = ctypes.c_int64()
+        if out is not None:
+            _chk(core_lib().aslam_snapshot(self._h, _ptr(t, ctypes.c_int32), cnt, out.data_ptr(), out.numel(), 1, ctypes.byref(need), stream))
+            return out[: need.value]
+        blob = np.empty(self.snapshot_bytes(trajs), np.uint8)
+        _chk(core_lib().aslam_snapshot(self._h, _ptr(t, ctypes.c_int32), cnt, blob.ctypes.data, blob.size, 0, ctypes.byref(need), stream))
+        return blob
+
+    def restore(self, blob, records=None, trajs=None, stream=None):
+        """Record records[i] of `blob` (default i) into slot trajs[i] (default i).  `blob`: a host uint8 array (bytes-like) or a uint8 torch
+        tensor on the device.  Without both lists every record of the blob is restored, record i into slot i.  A refused call (AslamError)
+        leaves the context unchanged.  Asynchronous on `stream` for a device blob, which must stay alive until the stream has passed."""
+        r = None if records is None else np.ascontiguousarray(records, np.int32)
+        t = None if trajs is None else np.ascontiguousarray(trajs, np.int32)
+        dev = hasattr(blob, "data_ptr")
+        if not dev:
+            blob = np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else np.ascontiguousarray(blob, np.uint8)
+        ptr, size = (blob.data_ptr(), blob.numel()) if dev else (blob.ctypes.data, blob.size)
+        if r is not None or t is not None:
+            cnt = len(r if r is not None else t)
+        elif dev:
+            raise ValueError("name the records or the slots of a device blob (its count is on the device)")
+        else:
+            from . import snapshot as snapfmt
+
+            cnt = snapfmt.blob_info(blob)[1]
+        _chk(core_lib().aslam_restore(self._h, _ptr(r, ctypes.c_int32), _ptr(t, ctypes.c_int32), cnt, ptr, size, 1 if dev else 0, stream))
+
+    def save(self, path, trajs=None):
+        """snapshot() to a file: the file IS the blob."""
+        self.snapshot(trajs).tofile(path)
+
+    def load(self, path, records=None, trajs=None):
+        """restore() from a file written by save()."""
+        self.restore(np.fromfile(path, np.uint8), records, trajs)
 
     def layout(self):
         npad, nbytes = ctypes.c_int(), ctypes.c_int64()

@@ -5,6 +5,7 @@
 // No CPU fallback exists: without a HIP device every compute entry point returns ASLAM_ERR_HIP.
 #include "../../include/aslam_core.h"
 #include "../../include/aslam_scan.h"
+#include "../../include/aslam_snapshot.h"
 
 #include <hip/hip_runtime.h>
 
@@ -22,6 +23,7 @@
 #include "ekf_large.h"
 #include "ekf_large_launch.h"
 #include "scan_front.h"
+#include "snapshot.h"
 #if ASLAM_HAVE_UKF
 #include "ukf_small.h"
 #include "ukf_large.h"
@@ -74,6 +76,11 @@ struct aslam_ctx
         // aslam_innovation_enable: [batch][2] (nis, logdet) of every filter's last callback, allocated by the first enable; off by default
         double *innov = nullptr;
         bool innov_on = false;
+        // aslam_snapshot / aslam_restore: descriptors, gathered headers and the staged copy of a host blob (grown on demand, not state)
+        char *snap_dev = nullptr;
+        size_t snap_cap = 0;
+        int snap_count = 0, snap_nmax = 0; // the last pack launch (aslam_debug_snapshot_rate repeats it)
+        int64_t snap_total = 0;
 };
 
 namespace
@@ -476,6 +483,8 @@ int aslam_destroy(aslam_ctx *c)
                 (void)hipFree(p);
         for (void *p : c->trace_owned)
                 (void)hipFree(p);
+        if (c->snap_dev)
+                (void)hipFree(c->snap_dev);
         for (hipStream_t q : c->lh.aux)
                 if (q)
                         (void)hipStreamDestroy(q);
@@ -895,6 +904,325 @@ int aslam_get_layout(aslam_ctx *c, int *padded_dim, int64_t *hbm_bytes)
                 *padded_dim = c->NP;
         if (hbm_bytes)
                 *hbm_bytes = c->hbm_bytes;
+        return ASLAM_OK;
+}
+
+/* ---- include/aslam_snapshot.h ------------------------------------------------------------------------------------- */
+namespace
+{
+/// at least `bytes` of device staging for a snapshot call (the context is synchronised: nothing reads the old block)
+int snap_reserve(aslam_ctx *c, size_t bytes)
+{
+        if (bytes <= c->snap_cap)
+                return ASLAM_OK;
+        if (c->snap_dev)
+                (void)hipFree(c->snap_dev);
+        c->snap_dev = nullptr;
+        c->snap_cap = 0;
+        void *q = nullptr;
+        HIP_TRY(hipMalloc(&q, bytes));
+        c->snap_dev = static_cast<char *>(q);
+        c->snap_cap = bytes;
+        return ASLAM_OK;
+}
+
+/// the context side of a pack / unpack launch.  clear[]: the slot-wise scratch aslam_reset zeroes (init_state, init_P_large) -- G, S, Vw of
+/// the large path, D, DZ, Tc, K of the single-CU UKF -- and D, DZ of the large-state UKF, whose padding columns the weighted products read
+SnapCtx snap_ctx(aslam_ctx *c)
+{
+        const DevView &d = c->dv;
+        SnapCtx s = {};
+        s.NP = c->NP, s.max_obs = d.max_obs, s.max_wait = d.max_wait;
+        s.X = d.X, s.Z = d.Z, s.P = c->large ? c->largeP : d.P, s.A = d.A;
+        s.n = d.n, s.flags = d.flags, s.status = d.status;
+        s.sens = d.sens, s.sens_n = d.sens_n, s.wait_rb = d.wait_rb, s.wait_cnt = d.wait_cnt, s.wait_n = d.wait_n;
+        s.innov = c->innov;
+        const size_t NP = (size_t)c->NP;
+        int k = 0;
+        auto add = [&](void *p, size_t bytes) {
+                if (p)
+                        s.clear[k] = static_cast<char *>(p), s.clear_bytes[k] = bytes, ++k;
+        };
+        if (c->large)
+                with_large_view(c, [&](auto &lv) {
+                        const size_t e = sizeof(*lv.G);
+                        add(lv.G, NP * NP * e), add(lv.S, NP * NP * e), add(lv.Vw, NP * NP * e);
+                        return 0;
+                });
+#if ASLAM_HAVE_UKF
+        if (c->ukf.D)
+        {
+                const size_t MP = (size_t)c->ukf.MP;
+                add(c->ukf.D, NP * MP * 8), add(c->ukf.DZ, NP * MP * 8), add(c->ukf.Tc, NP * NP * 8), add(c->ukf.K, NP * NP * 8);
+        }
+        if (c->ukfl.D)
+                add(c->ukfl.D, NP * (size_t)c->ukfl.MP * 8), add(c->ukfl.DZ, NP * (size_t)c->ukfl.MP * 8);
+#endif
+        return s;
+}
+} // namespace
+
+int64_t aslam_snapshot_record_bytes(int n, int sens_n, int wait_n)
+{
+        return snap_record_bytes(n, sens_n, wait_n);
+}
+
+int aslam_snapshot_check(const void *host_blob, int64_t bytes, int32_t *filter, int32_t *count)
+{
+        if (!host_blob)
+                return fail(ASLAM_ERR_ARG, "null blob");
+        const char *b = static_cast<const char *>(host_blob);
+        SnapBlobHeader h;
+        int64_t table_end = 0;
+        if (bytes >= 64)
+                std::memcpy(&h, b, 64);
+        if (const char *e = snap_check_header(h, bytes, &table_end))
+                return fail(ASLAM_ERR_ARG, std::string("snapshot: ") + e);
+        for (uint32_t i = 0; i < h.count; ++i)
+        {
+                uint64_t off;
+                std::memcpy(&off, b + 64 + 8 * (size_t)i, 8);
+                const char *e = snap_check_offset(off, table_end, h.total_bytes);
+                SnapRecHeader r;
+                if (!e)
+                {
+                        std::memcpy(&r, b + off, 64);
+                        e = snap_check_record(r, off, h.total_bytes);
+                }
+                if (e)
+                        return fail(ASLAM_ERR_ARG, "snapshot record " + std::to_string(i) + ": " + e);
+        }
+        if (filter)
+                *filter = (int32_t)h.filter;
+        if (count)
+                *count = (int32_t)h.count;
+        return ASLAM_OK;
+}
+
+int aslam_snapshot(aslam_ctx *c, const int32_t *trajs, int count, void *blob, int64_t cap_bytes, int is_device, int64_t *bytes_needed,
+                   void *stream)
+{
+        if (!c)
+                return fail(ASLAM_ERR_ARG, "null context");
+        const int B = c->cfg.batch;
+        if (!trajs)
+                count = B;
+        if (count < 1)
+                return fail(ASLAM_ERR_ARG, "count must be positive");
+        for (int i = 0; trajs && i < count; ++i)
+                if (trajs[i] < 0 || trajs[i] >= B)
+                        return fail(ASLAM_ERR_ARG, "trajectory index out of range");
+        int rc = sync_ctx(c);
+        if (rc != ASLAM_OK)
+                return rc;
+        // n, sens_n, wait_n of the batch: three small copies, whatever `count` is
+        std::vector<int> meta(3 * (size_t)B);
+        HIP_TRY(hipMemcpy(&meta[0], c->dv.n, sizeof(int) * B, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&meta[B], c->dv.sens_n, sizeof(int) * B, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&meta[2 * (size_t)B], c->dv.wait_n, sizeof(int) * B, hipMemcpyDeviceToHost));
+        std::vector<SnapDesc> desc(count);
+        int64_t off = 64 + snap_pad64(8 * (int64_t)count);
+        int n_max = 3;
+        for (int i = 0; i < count; ++i)
+        {
+                const int t = trajs ? trajs[i] : i;
+                SnapDesc &d = desc[i];
+                d = SnapDesc{off, t, meta[t], std::min(std::max(meta[B + t], 0), c->dv.max_obs), std::min(std::max(meta[2 * (size_t)B + t], 0), c->dv.max_wait), {0, 0}};
+                const int64_t rb = snap_record_bytes(d.n, d.sens_n, d.wait_n);
+                if (rb < 0 || d.n >= c->cfg.max_landmark_count)
+                        return fail(ASLAM_ERR_STATE, "a filter of the context has an invalid dimension");
+                off += snap_pad64(rb);
+                n_max = std::max(n_max, d.n);
+        }
+        const int64_t total = off;
+        if (bytes_needed)
+                *bytes_needed = total;
+        if (!blob)
+                return ASLAM_OK;
+        if (cap_bytes < total)
+                return fail(ASLAM_ERR_ARG, "blob capacity below the snapshot's size (" + std::to_string(total) + " bytes)");
+        if (is_device && ((uintptr_t)blob & 15))
+                return fail(ASLAM_ERR_ARG, "a device blob must be 16-byte aligned");
+        const size_t dbytes = (size_t)snap_pad64((int64_t)sizeof(SnapDesc) * count);
+        if ((rc = snap_reserve(c, dbytes + (is_device ? 0 : (size_t)total))) != ASLAM_OK)
+                return rc;
+        HIP_TRY(hipMemcpy(c->snap_dev, desc.data(), sizeof(SnapDesc) * count, hipMemcpyHostToDevice));
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        char *out = is_device ? static_cast<char *>(blob) : c->snap_dev + dbytes;
+        c->last_stream = st;
+        c->snap_count = count, c->snap_nmax = n_max, c->snap_total = total;
+        hipLaunchKernelGGL(snapshot_pack, snap_grid((int64_t)n_max * (n_max + 1) / 2, count), dim3(SNAP_WG), 0, st, snap_ctx(c),
+                           reinterpret_cast<const SnapDesc *>(c->snap_dev), count, (uint32_t)c->cfg.filter, (uint64_t)total, out);
+        HIP_TRY(hipGetLastError());
+        if (!is_device)
+        {
+                HIP_TRY(hipMemcpyAsync(blob, out, (size_t)total, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipStreamSynchronize(st));
+        }
+        return ASLAM_OK;
+}
+
+int aslam_restore(aslam_ctx *c, const int32_t *records, const int32_t *trajs, int count, const void *blob, int64_t bytes, int is_device,
+                  void *stream)
+{
+        if (!c || !blob)
+                return fail(ASLAM_ERR_ARG, "null argument");
+        if (count < 1 || count > c->cfg.batch)
+                return fail(ASLAM_ERR_ARG, "count must be 1 .. batch (a slot is restored once)");
+        if (is_device && ((uintptr_t)blob & 15))
+                return fail(ASLAM_ERR_ARG, "a device blob must be 16-byte aligned");
+        int rc = sync_ctx(c);
+        if (rc != ASLAM_OK)
+                return rc;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        const char *b = static_cast<const char *>(blob);
+        const size_t dbytes = (size_t)snap_pad64((int64_t)sizeof(SnapDesc) * count);
+
+        // ---- the headers, on the host
+        SnapBlobHeader h;
+        int64_t table_end = 0;
+        std::vector<uint64_t> table;
+        std::vector<SnapRecHeader> recs;
+        if (!is_device)
+        {
+                int32_t cnt = 0;
+                if ((rc = aslam_snapshot_check(blob, bytes, nullptr, &cnt)) != ASLAM_OK)
+                        return rc;
+                std::memcpy(&h, b, 64);
+                table.resize(cnt), recs.resize(cnt);
+                for (int i = 0; i < cnt; ++i)
+                {
+                        std::memcpy(&table[i], b + 64 + 8 * (size_t)i, 8);
+                        std::memcpy(&recs[i], b + table[i], 64);
+                }
+        }
+        else
+        {
+                if (bytes >= 64)
+                {
+                        HIP_TRY(hipMemcpyAsync(&h, b, 64, hipMemcpyDeviceToHost, st));
+                        HIP_TRY(hipStreamSynchronize(st));
+                }
+                if (const char *e = snap_check_header(h, bytes, &table_end))
+                        return fail(ASLAM_ERR_ARG, std::string("snapshot: ") + e);
+                const size_t cnt = h.count;
+                table.resize(cnt), recs.resize(cnt);
+                if (cnt)
+                {
+                        HIP_TRY(hipMemcpyAsync(table.data(), b + 64, 8 * cnt, hipMemcpyDeviceToHost, st));
+                        HIP_TRY(hipStreamSynchronize(st));
+                        for (size_t i = 0; i < cnt; ++i)
+                                if (const char *e = snap_check_offset(table[i], table_end, h.total_bytes))
+                                        return fail(ASLAM_ERR_ARG, "snapshot record " + std::to_string(i) + ": " + e);
+                        // one gather launch through the validated table, one copy
+                        const size_t tbytes = (size_t)snap_pad64(8 * (int64_t)cnt);
+                        if ((rc = snap_reserve(c, dbytes + tbytes + 64 * cnt)) != ASLAM_OK)
+                                return rc;
+                        uint64_t *tdev = reinterpret_cast<uint64_t *>(c->snap_dev + dbytes);
+                        SnapRecHeader *hdev = reinterpret_cast<SnapRecHeader *>(c->snap_dev + dbytes + tbytes);
+                        HIP_TRY(hipMemcpyAsync(tdev, table.data(), 8 * cnt, hipMemcpyHostToDevice, st));
+                        hipLaunchKernelGGL(snapshot_gather, dim3((unsigned)((4 * cnt + SNAP_WG - 1) / SNAP_WG)), dim3(SNAP_WG), 0, st, b, tdev, (int)cnt, hdev);
+                        HIP_TRY(hipGetLastError());
+                        HIP_TRY(hipMemcpyAsync(recs.data(), hdev, 64 * cnt, hipMemcpyDeviceToHost, st));
+                        HIP_TRY(hipStreamSynchronize(st));
+                        for (size_t i = 0; i < cnt; ++i)
+                                if (const char *e = snap_check_record(recs[i], table[i], h.total_bytes))
+                                        return fail(ASLAM_ERR_ARG, "snapshot record " + std::to_string(i) + ": " + e);
+                }
+        }
+
+        // ---- the request against the context
+        if ((int32_t)h.filter != c->cfg.filter)
+                return fail(ASLAM_ERR_ARG, "the snapshot holds the other filter kind (EKF / UKF)");
+        std::vector<SnapDesc> desc(count);
+        std::vector<char> seen(c->cfg.batch, 0);
+        for (int i = 0; i < count; ++i)
+        {
+                const int r = records ? records[i] : i, t = trajs ? trajs[i] : i;
+                if (r < 0 || (size_t)r >= recs.size())
+                        return fail(ASLAM_ERR_ARG, "record index out of range");
+                if (t < 0 || t >= c->cfg.batch)
+                        return fail(ASLAM_ERR_ARG, "trajectory index out of range");
+                if (seen[t]++)
+                        return fail(ASLAM_ERR_ARG, "a slot is named twice");
+                const SnapRecHeader &q = recs[r];
+                if (q.n >= c->cfg.max_landmark_count)
+                        return fail(ASLAM_ERR_UNSUPPORTED, "record " + std::to_string(r) + ": state dimension " + std::to_string(q.n) +
+                                                               " does not fit below the context's max_landmark_count");
+                if (q.sens_n > c->cfg.max_obs)
+                        return fail(ASLAM_ERR_UNSUPPORTED, "record " + std::to_string(r) + ": stored sensor message beyond the context's max_obs");
+                if (q.wait_n > c->cfg.max_wait)
+                        return fail(ASLAM_ERR_UNSUPPORTED, "record " + std::to_string(r) + ": wait-list beyond the context's max_wait");
+                desc[i] = SnapDesc{(int64_t)table[r], t, q.n, q.sens_n, q.wait_n, {0, 0}};
+        }
+
+        // ---- one unpack launch
+        if ((rc = snap_reserve(c, dbytes + (is_device ? 0 : (size_t)h.total_bytes))) != ASLAM_OK)
+                return rc;
+        HIP_TRY(hipMemcpy(c->snap_dev, desc.data(), sizeof(SnapDesc) * count, hipMemcpyHostToDevice));
+        const char *src = b;
+        if (!is_device)
+        {
+                HIP_TRY(hipMemcpy(c->snap_dev + dbytes, b, (size_t)h.total_bytes, hipMemcpyHostToDevice));
+                src = c->snap_dev + dbytes;
+        }
+        c->last_stream = st;
+        hipLaunchKernelGGL(snapshot_unpack, snap_grid((int64_t)c->NP * c->NP / 2, count), dim3(SNAP_WG), 0, st, snap_ctx(c),
+                           reinterpret_cast<const SnapDesc *>(c->snap_dev), count, src);
+        HIP_TRY(hipGetLastError());
+        return ASLAM_OK;
+}
+
+/* diagnostic (tools/snapshot_rate.py): the pack and the unpack launch of the whole batch and a device-to-device copy of the blob's bytes, each
+   between two device events, alternating `reps` times after three untimed rounds.  dev_buf: device memory of at least twice the snapshot's
+   size.  ms [3][reps]: pack, unpack, copy.  info[3]: bytes of the blob, of the padded layout unpack writes, of the scratch it clears. */
+int aslam_debug_snapshot_rate(aslam_ctx *c, void *dev_buf, int64_t cap_bytes, int reps, float *ms, int64_t *info)
+{
+        if (!c || !dev_buf || !ms || !info || reps < 1)
+                return fail(ASLAM_ERR_ARG, "null argument");
+        int64_t total = 0;
+        int rc = aslam_snapshot(c, nullptr, 0, nullptr, 0, 1, &total, nullptr);
+        if (rc == ASLAM_OK && cap_bytes < 2 * total)
+                rc = fail(ASLAM_ERR_ARG, "aslam_debug_snapshot_rate needs twice the snapshot's size");
+        if (rc == ASLAM_OK)
+                rc = aslam_snapshot(c, nullptr, 0, dev_buf, total, 1, nullptr, nullptr); // leaves the descriptors of the batch on the device
+        if (rc != ASLAM_OK)
+                return rc;
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        const SnapCtx sc = snap_ctx(c);
+        const SnapDesc *desc = reinterpret_cast<const SnapDesc *>(c->snap_dev);
+        const int count = c->snap_count;
+        const size_t NP = (size_t)c->NP;
+        char *blob = static_cast<char *>(dev_buf);
+        info[0] = total;
+        info[1] = (int64_t)count * (int64_t)(8 * NP * NP + 16 * NP + 8 * (size_t)sc.max_obs + 12 * (size_t)sc.max_wait);
+        info[2] = 0;
+        for (int k = 0; k < SNAP_CLEAR_MAX; ++k)
+                info[2] += sc.clear[k] ? (int64_t)count * (int64_t)sc.clear_bytes[k] : 0;
+        hipEvent_t e0, e1;
+        HIP_TRY(hipEventCreate(&e0));
+        HIP_TRY(hipEventCreate(&e1));
+        for (int r = -3; r < reps; ++r)
+                for (int what = 0; what < 3; ++what)
+                {
+                        HIP_TRY(hipEventRecord(e0, nullptr));
+                        if (what == 0)
+                                hipLaunchKernelGGL(snapshot_pack, snap_grid((int64_t)c->snap_nmax * (c->snap_nmax + 1) / 2, count), dim3(SNAP_WG), 0, nullptr,
+                                                   sc, desc, count, (uint32_t)c->cfg.filter, (uint64_t)total, blob);
+                        else if (what == 1)
+                                hipLaunchKernelGGL(snapshot_unpack, snap_grid((int64_t)c->NP * c->NP / 2, count), dim3(SNAP_WG), 0, nullptr, sc, desc, count,
+                                                   (const char *)blob);
+                        else
+                                HIP_TRY(hipMemcpyAsync(blob + total, blob, (size_t)total, hipMemcpyDeviceToDevice, nullptr));
+                        HIP_TRY(hipEventRecord(e1, nullptr));
+                        HIP_TRY(hipEventSynchronize(e1));
+                        float t = 0.f;
+                        HIP_TRY(hipEventElapsedTime(&t, e0, e1));
+                        if (r >= 0)
+                                ms[what * reps + r] = t;
+                }
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
         return ASLAM_OK;
 }
 

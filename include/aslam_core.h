@@ -117,7 +117,8 @@ int aslam_abi_version(void);
 
 /* ---- the per-callback seam (host keeps association/growth: ekf.cpp:137-290 stay on the host) ------ */
 /* Set the device state of one filter: dimension n, X[n], Z[n], P[n*n] row-major (any of them NULL = keep).
- * Used for state hand-over and kernel-level tests. */
+ * Used for state hand-over and kernel-level tests.  It clears both init flags and carries neither A nor the stored sensor message, the
+ * wait-list or the status bits: aslam_snapshot.h moves a WHOLE filter. */
 int aslam_set_state(aslam_ctx *ctx, int traj, int n, const double *X, const double *Z, const double *P);
 /* the matrix part of updateNewLandmark (ekf.cpp:271-278 / ukf.cpp:238-245): grow filter `traj` from its
  * current dimension to n_new; new P diagonal = UKF_KP_LANDMARK_POSE, new X/Z entries from the seeds

@@ -1,0 +1,380 @@
+"""-m gpu: snapshot and restore of whole filters (include/aslam_snapshot.h) -- a restored filter continues the run it came from BIT FOR BIT,
+in the same context configuration, in another slot or batch size, in a slot that held a larger filter before, and the record migrates
+between the single-CU and the large-state kernels and between the dtypes.
+
+All traces are make_traces(L, 60, B=3, seed=s, sensor_every=2, dt_mode="random") with (L, s) in {(8, 2), (20, 3), (64, 5), (80, 62)}: at the
+cut k = 21 callback 21 carries no sensor message (the stored one is re-walked), the wait-list is in use (6 / 14 / 43 / 54 entries with
+counts of 7 .. 11 on the CPU oracle, which the record must equal; it grows to 375 entries later, hence max_wait = 512) and n = 9 / 17 / 47 /
+57 still has to grow to 19 / 43 / 131 / 163; at k = 49 n is final and the EKF's A has left the identity.  Every comparison asserts
+status == 0 on the filters it compares.  Against the oracle the bars are the ones the kernel families already have: util.REL_TOL, and
+test_gpu_large.F32_TOL for binary32 products."""
+import functools
+
+import numpy as np
+import pytest
+
+from awesomeslam_amd import snapshot
+from awesomeslam_amd import trace as tg
+from test_gpu_large import F32_TOL
+from util import REL_TOL, cov_err, rel_err
+
+pytestmark = pytest.mark.gpu
+
+T = 60
+SEEDS = {8: 2, 20: 3, 64: 5, 80: 62}
+CUTS = (21, 49)
+N_AT_21 = {8: 9, 20: 17, 64: 47, 80: 57}
+N_FINAL = {8: 19, 20: 43, 64: 131, 80: 163}
+MAX_WAIT = 512
+
+# name -> (filter, L, dtype, flags): the three NT instantiations of the single-CU EKF, two of the UKF, the large-state chains
+CASES = {
+    "ekf-L8": ("ekf", 8, "f64", 0), "ekf-L20": ("ekf", 20, "f64", 0), "ekf-L64": ("ekf", 64, "f64", 0),
+    "ukf-L8": ("ukf", 8, "f64", 0), "ukf-L64": ("ukf", 64, "f64", 0),
+    "ekf-L80-f64": ("ekf", 80, "f64", 0), "ekf-L80-f32": ("ekf", 80, "f32", 0), "ukf-L80-large": ("ukf", 80, "f64", 1),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def trace(L, max_obs=None):
+    tr = tg.make_traces(L, T, B=3, seed=SEEDS[L], sensor_every=2, dt_mode="random")
+    if max_obs is not None and max_obs != tr.max_obs:
+        # the same messages in a wider array (a context takes traces of its own max_obs only)
+        obs = np.zeros(tr.obs.shape[:2] + (max_obs, 2), np.float32)
+        obs[:, :, :tr.max_obs] = tr.obs
+        tr = tg.Trace(tr.odom, tr.dt, tr.obs_new, tr.n_obs, obs, tr.landmarks, tr.truth, tr.warmup, dict(tr.meta))
+    return tr
+
+
+@functools.lru_cache(maxsize=None)
+def oracle(kind, L, upto=T):
+    """the CPU oracle's uninterrupted replay of callbacks 0 .. upto-1: per filter (poses, dims, X, Z, P, wait-list)"""
+    from oracle.c_oracle import CFilter
+
+    out = []
+    for b in range(3):
+        o = CFilter(kind, tg.dim_cap(L))
+        po, do = o.replay(trace(L)[b], upto)
+        out.append((po, do) + o.state() + (o.wait_list(),))
+    return out
+
+
+def make(case, batch=3, cap=None, max_obs=None, max_wait=MAX_WAIT):
+    from awesomeslam_amd.core import Core, F32, F64
+
+    kind, L, dtype, flags = CASES[case]
+    return Core(kind, cap or tg.dim_cap(L), batch=batch, max_obs=max_obs or trace(L).max_obs, max_wait=max_wait,
+                dtype=F32 if dtype == "f32" else F64, flags=flags)
+
+
+def run(core, t0, k, stream=None):
+    """replay(t0, k) -> poses [B, k, 3], dims [B, k] (synchronised)"""
+    import torch
+
+    poses = torch.zeros((core.batch, k, 3), dtype=torch.float64, device="cuda")
+    dims = torch.zeros((core.batch, k), dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    core.replay(t0, k, poses.data_ptr(), dims.data_ptr(), stream)
+    torch.cuda.synchronize()
+    return poses.cpu().numpy(), dims.cpu().numpy()
+
+
+def final(core, b):
+    """everything the getters say about filter b"""
+    return (np.int64(core.dim(b)),) + core.state(b) + (np.array(core.A(b)),) + core.wait_list(b, cap=MAX_WAIT) + \
+        (np.uint32(core.status(b)),) + core.landmarks(b)
+
+
+def same(a, b):
+    return len(a) == len(b) and all(np.array_equal(x, y) for x, y in zip(a, b))
+
+
+_REF = {}
+
+
+def reference(case, k):
+    """context A: replay(0, k), replay(k, 60 - k) without a snapshot in between.  Computed once per (case, k) and never changed:
+    (poses of 0 .. k-1, poses of k .. 59, dims of k .. 59, final(b) for every b, the snapshot at the cut)"""
+    if (case, k) not in _REF:
+        core = make(case)
+        core.set_trace(trace(CASES[case][1]))
+        p0, _ = run(core, 0, k)
+        blob = core.snapshot()
+        p1, d1 = run(core, k, T - k)
+        fin = [final(core, b) for b in range(3)]
+        assert all(core.status(b) == 0 for b in range(3))
+        core.close()
+        for a in (p0, p1, d1, blob):
+            a.setflags(write=False)
+        _REF[case, k] = (p0, p1, d1, fin, blob)
+    return _REF[case, k]
+
+
+def assert_continues(core, case, k, rows=(0, 1, 2), slots=None):
+    """`core` holds records `rows` of the cut at k in `slots` and has the matching trace bound: the rest of the run equals context A's"""
+    _, p1, d1, fin, _ = reference(case, k)
+    slots = range(len(rows)) if slots is None else slots
+    pg, dg = run(core, k, T - k)
+    for r, s in zip(rows, slots):
+        assert core.status(s) == 0
+        assert np.array_equal(pg[s], p1[r]) and np.array_equal(dg[s], d1[r]), (case, k, r, s)
+        assert same(final(core, s), fin[r]), (case, k, r, s)
+    return pg
+
+
+# ---- 1. resume is bitwise ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("k", CUTS)
+@pytest.mark.parametrize("case", list(CASES))
+def test_resume_is_bitwise(case, k, built):
+    kind, L, dtype, _ = CASES[case]
+    tr = trace(L)
+    assert tr.obs_new[:, k].max() == 0 and tr.obs_new[:, k - 1].min() == 1  # callback k re-walks the message stored at k - 1
+    p0, p1, d1, fin, _ = reference(case, k)
+    b_ctx = make(case)
+    b_ctx.set_trace(tr)
+    pb0, _ = run(b_ctx, 0, k)
+    blob = b_ctx.snapshot()
+    assert all(b_ctx.status(b) == 0 for b in range(3))
+    b_ctx.close()
+    assert np.array_equal(pb0, p0)
+    recs = snapshot.parse(blob)
+    if k == 21:  # the cut is where the module docstring says it is
+        assert [r["n"] for r in recs] == [N_AT_21[L]] * 3
+        for r, o in zip(recs, oracle(kind, L, 21)):  # a wait-list in use, with counts: the oracle's, entry for entry
+            wr, wb, wc = o[5]
+            assert len(wc) >= 6 and wc.min() > 0
+            assert np.array_equal(r["wait_rb"][:, 0], wr) and np.array_equal(r["wait_rb"][:, 1], wb) and np.array_equal(r["wait_cnt"], wc)
+    else:
+        assert [r["n"] for r in recs] == [N_FINAL[L]] * 3
+        if kind == "ekf":
+            assert [bool(r["A"][0] != 1.0 or r["A"][1] != 0.0) for r in recs] == [not (L == 8 and b == 0) for b in range(3)]
+
+    fresh = make(case)
+    fresh.restore(blob)
+    fresh.set_trace(tr)
+    pg = assert_continues(fresh, case, k)
+    if k == 21:  # once per case: the resumed run against the oracle's uninterrupted one
+        tol = F32_TOL if dtype == "f32" else REL_TOL
+        for b, (po, do, Xo, Zo, Po, _) in enumerate(oracle(kind, L)):
+            X, Z, P = fresh.state(b)
+            errs = rel_err(np.concatenate([pb0[b], pg[b]]), po), rel_err(X, Xo), cov_err(P, Po)
+            print(f"snapshot resume {case} b={b} N={fresh.dim(b)}: rel err pose/X/P = {errs[0]:.2e} {errs[1]:.2e} {errs[2]:.2e}")
+            assert max(errs) < tol and np.array_equal(Z, Zo) and fresh.dim(b) == do[-1] == N_FINAL[L]
+    fresh.close()
+
+
+# ---- 2. the record says what the getters say ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", ["ekf-L8", "ukf-L64", "ekf-L80-f32", "ukf-L80-large"])
+def test_record_equals_getters(case, built):
+    L = CASES[case][1]
+    tr = trace(L)
+    core = make(case)
+    core.set_trace(tr)
+    run(core, 0, 21)
+    blob = core.snapshot()
+    recs = snapshot.parse(blob)
+    assert len(recs) == 3 and blob.size == core.snapshot_bytes()
+    for b, r in enumerate(recs):
+        X, Z, P = core.state(b)
+        wr, wb, wc = core.wait_list(b, cap=MAX_WAIT)
+        assert core.status(b) == 0 and r["status"] == 0 and r["flags"] == 0
+        assert r["n"] == core.dim(b) == N_AT_21[L]
+        assert np.array_equal(r["X"], X) and np.array_equal(r["Z"], Z) and np.array_equal(r["P"], P)
+        assert np.array_equal(r["A"], np.array(core.A(b)))
+        assert np.array_equal(r["wait_rb"][:, 0], wr) and np.array_equal(r["wait_rb"][:, 1], wb) and np.array_equal(r["wait_cnt"], wc)
+        assert tr.obs_new[b, 20] == 1 and np.array_equal(r["sens"], tr.obs[b, 20, :tr.n_obs[b, 20]])
+    # a snapshot of some filters, in another order, holds the same records
+    part = snapshot.parse(core.snapshot(trajs=[2, 0]))
+    assert snapshot.records_equal(part[0], recs[2]) and snapshot.records_equal(part[1], recs[0])
+    core.close()
+
+
+# ---- 3. fork and permute -----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", ["ekf-L8", "ukf-L8"])
+def test_fork_and_permute(case, built):
+    tr = trace(8)
+    blob = reference(case, 21)[4]
+    rows = [2, 0, 2]
+    core = make(case, batch=3)
+    core.restore(blob, records=rows, trajs=[0, 1, 2])
+    core.set_trace(tr.select(rows))
+    assert_continues(core, case, 21, rows=rows)
+    core.close()
+    core = make(case, batch=5)
+    core.restore(blob, records=[1], trajs=[3])
+    core.set_trace(tr.select([0, 0, 0, 1, 0]))
+    assert [core.dim(b) for b in range(5)] == [3, 3, 3, 9, 3]
+    assert_continues(core, case, 21, rows=[1], slots=[3])
+    core.close()
+
+
+# ---- 4. dirty slots ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case,big,small", [("ekf-L64", 64, 8), ("ukf-L64", 64, 8), ("ekf-L80-f64", 80, 80), ("ekf-L80-f32", 80, 80),
+                                            ("ukf-L80-large", 80, 80)])
+def test_dirty_slots(case, big, small, built):
+    """Slots that have run the big trace to its final n receive records of a SMALLER n (cut at k = 21 in a context of this configuration)
+    and continue their trace exactly as a freshly created context restored from the same blob does."""
+    mo = trace(big).max_obs
+    tr_small = trace(small, mo)
+    src = make(case)
+    src.set_trace(tr_small)
+    run(src, 0, 21)
+    blob = src.snapshot()
+    src.close()
+    n_rec = [r["n"] for r in snapshot.parse(blob)]
+    assert n_rec == [N_AT_21[small]] * 3
+
+    def cont(dirty):
+        core = make(case)
+        if dirty:
+            core.set_trace(trace(big))
+            run(core, 0, T)
+            assert [core.dim(b) for b in range(3)] == [N_FINAL[big]] * 3 and N_FINAL[big] > n_rec[0]
+        core.restore(blob)
+        assert [core.dim(b) for b in range(3)] == n_rec
+        core.set_trace(tr_small)
+        pg, dg = run(core, 21, T - 21)
+        out = (pg, dg, [final(core, b) for b in range(3)], core.snapshot())
+        assert all(core.status(b) == 0 for b in range(3))
+        core.close()
+        return out
+
+    (pf, df, ff, sf), (pd, dd, fd, sd) = cont(False), cont(True)
+    assert np.array_equal(pd, pf) and np.array_equal(dd, df)
+    assert all(same(a, b) for a, b in zip(fd, ff)) and sd.tobytes() == sf.tobytes()
+    assert df[:, -1].tolist() == [N_FINAL[small]] * 3
+    if big == small:  # (the same configuration as test 1: the continuation is context A's, too)
+        assert np.array_equal(pf, reference(case, 21)[1])
+
+
+# ---- 5. migration ------------------------------------------------------------------------------------------------------------------
+def readback(core, b):
+    return (np.int64(core.dim(b)),) + core.state(b) + (np.array(core.A(b)),) + core.wait_list(b, cap=MAX_WAIT) + (np.uint32(core.status(b)),)
+
+
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+def test_migration_small_to_large_and_back(dtype, built):
+    from awesomeslam_amd.core import Core, F32, F64
+
+    L, k = 64, 49
+    tr = trace(L)
+    small = make("ekf-L64")
+    small.set_trace(tr)
+    run(small, 0, k)
+    blob = small.snapshot()
+    want = [readback(small, b) for b in range(3)]
+    assert [w[0] for w in want] == [131] * 3 and small.launch_info()["launches_per_callback"] == 1
+    small.close()
+
+    large = Core("ekf", tg.dim_cap(80), batch=3, max_obs=tr.max_obs, max_wait=MAX_WAIT, dtype=F32 if dtype == "f32" else F64)
+    assert large.layout()[0] % 64 == 0 and large.layout()[0] >= 164
+    large.restore(blob)
+    for b in range(3):
+        assert same(readback(large, b), want[b]) and large.status(b) == 0
+    back_blob = large.snapshot()
+    assert back_blob.tobytes() == blob.tobytes()  # the record does not know which context it came from
+    large.set_trace(tr)
+    pg, dg = run(large, k, 5)
+    info = large.launch_info()
+    assert info["launches_per_callback"] > 1 and "large" in large.kernel_info()["name"], info
+    tol = F32_TOL if dtype == "f32" else REL_TOL
+    for b, (po, do, Xo, Zo, Po, _) in enumerate(oracle("ekf", L, k + 5)):
+        X, Z, P = large.state(b)
+        errs = rel_err(pg[b], po[k:]), rel_err(X, Xo), cov_err(P, Po)
+        print(f"snapshot migration small -> large {dtype} b={b}: rel err pose/X/P = {errs[0]:.2e} {errs[1]:.2e} {errs[2]:.2e}")
+        assert max(errs) < tol and np.array_equal(Z, Zo) and np.array_equal(dg[b], do[k:]) and large.status(b) == 0
+
+    # the reverse direction: what the large context holds now (n = 131) into single-CU slots, in another order and batch size
+    want = [readback(large, b) for b in range(3)]
+    blob = large.snapshot()
+    large.close()
+    small = make("ekf-L64", batch=4)
+    small.restore(blob, records=[1, 2, 0], trajs=[3, 0, 2])
+    for r, s in ((1, 3), (2, 0), (0, 2)):
+        assert same(readback(small, s), want[r])
+    assert small.dim(1) == 3
+    small.close()
+
+
+# ---- 6. refusals leave the context unchanged ---------------------------------------------------------------------------------------
+def refused(core, code, *args, **kw):
+    from awesomeslam_amd.core import AslamError
+
+    with pytest.raises(AslamError, match=f"aslam_core error {code}:"):
+        core.restore(*args, **kw)
+
+
+def test_refusals_leave_the_context_unchanged(built):
+    import torch
+
+    core = make("ekf-L8")  # max_landmark_count 20, max_obs 8, max_wait 512
+    core.set_trace(trace(8))
+    run(core, 0, 21)
+    before = core.snapshot()
+    recs = snapshot.parse(before)
+    good = dict(recs[1], X=recs[1]["X"] + 1.0)  # a valid record that differs from what the context holds: a half-applied request would show
+
+    def grown(n):
+        P = np.eye(n)
+        P[:9, :9] = recs[0]["P"]
+        return dict(recs[0], n=n, X=np.resize(recs[0]["X"], n), Z=np.resize(recs[0]["Z"], n), P=P)
+
+    long_wait = dict(recs[0], wait_rb=np.ones((MAX_WAIT + 1, 2), np.float32), wait_cnt=np.ones(MAX_WAIT + 1, np.uint32))
+    long_sens = dict(recs[0], sens=np.ones((9, 2), np.float32))
+    UNSUPPORTED, ARG = -3, -1
+    refused(core, UNSUPPORTED, snapshot.pack([good, grown(21)], "ekf"))   # n >= max_landmark_count (21 is what the next cap would take)
+    refused(core, UNSUPPORTED, snapshot.pack([good, long_wait], "ekf"))  # wait_n > max_wait
+    refused(core, UNSUPPORTED, snapshot.pack([good, long_sens], "ekf"))  # sens_n > max_obs
+    refused(core, ARG, snapshot.pack([good, good], "ukf"))               # the other filter kind
+    ok = snapshot.pack([good, good, good], "ekf")
+    refused(core, ARG, ok, records=[0, 1], trajs=[1, 1])                 # a slot twice
+    refused(core, ARG, ok, records=[0, 3], trajs=[0, 1])                 # a record index >= count
+    refused(core, ARG, ok, records=[0, 1], trajs=[0, 3])                 # a slot index >= batch
+    bad = torch.from_numpy(ok.copy()).cuda()
+    bad[3] = ord("X")
+    refused(core, ARG, bad, records=[0, 1, 2])                           # a corrupted magic in a device blob
+    assert core.snapshot().tobytes() == before.tobytes()
+    # the UKF refuses the EKF's blob
+    ukf = make("ukf-L8")
+    u_before = ukf.snapshot()
+    refused(ukf, ARG, before)
+    assert ukf.snapshot().tobytes() == u_before.tobytes()
+    ukf.close()
+    # ... and the request the refusals were variations of goes through, from the host and from the device
+    core.restore(ok)
+    assert all(np.array_equal(core.state(b)[0], good["X"]) for b in range(3))
+    core.restore(torch.from_numpy(before.copy()).cuda(), records=[0, 1, 2])
+    assert core.snapshot().tobytes() == before.tobytes()
+    # a capacity below the size writes nothing
+    small = torch.zeros(before.size - 64, dtype=torch.uint8, device="cuda")
+    from awesomeslam_amd.core import AslamError
+    with pytest.raises(AslamError, match="aslam_core error -1:"):
+        core.snapshot(out=small)
+    assert int(small.max()) == 0
+    core.close()
+
+
+# ---- 7. device blobs are asynchronous ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", ["ekf-L8", "ekf-L80-f32", "ukf-L80-large"])
+def test_device_blob_on_a_side_stream(case, built):
+    """replay, snapshot into a device tensor and restore from it into a second context, all enqueued on one side stream: nothing between the
+    two calls synchronises the host beyond what they document (snapshot: the context's last stream; restore: its own header reads)."""
+    import torch
+
+    kind, L, _, _ = CASES[case]
+    tr, k = trace(L), 21
+    a, b = make(case), make(case)
+    a.set_trace(tr)
+    b.set_trace(tr)
+    s = torch.cuda.Stream()
+    cap = 64 + 64 + 3 * ((snapshot.record_bytes(tg.dim_cap(L) - 1, tr.max_obs, MAX_WAIT) + 63) // 64 * 64)  # an upper bound: no size query
+    buf = torch.empty(cap, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    a.replay(0, k, None, None, s.cuda_stream)
+    blob = a.snapshot(out=buf, stream=s.cuda_stream)
+    b.restore(blob, records=[0, 1, 2], stream=s.cuda_stream)
+    pg = assert_continues(b, case, k)
+    assert blob.numel() == reference(case, k)[4].size and blob.cpu().numpy().tobytes() == reference(case, k)[4].tobytes()
+    assert pg.shape == (3, T - k, 3)
+    a.close()
+    b.close()
