@@ -1051,6 +1051,11 @@ __global__ __launch_bounds__(256) void large_syrk(DevView d, LargeView<T> lv, in
                 }
 }
 
+#ifndef ASLAM_XU_ROWS
+#define ASLAM_XU_ROWS 8
+#endif
+constexpr int XU_ROWS = ASLAM_XU_ROWS; // (rows per wave of large_x_update_rows; 4 and 16 measured in round 4: profiles/r04_experiments.md)
+
 /// P -= V V^T with the binary32 products formed on the BF16 matrix pipe ("bf16x3"): every float is the exact sum of three bf16 pieces of
 /// eight mantissa bits (a = a1 + a2 + a3), and  a b ~= a1 b1 + (a1 b2 + a2 b1) + (a1 b3 + a2 b2 + a3 b1):  six v_mfma_f32_16x16x32_bf16
 /// (16x16x32 per instruction, fp32 accumulation, bf16 x bf16 products exact) do the work of eight v_mfma_f32_16x16x4_f32 at twice
@@ -1069,19 +1074,13 @@ __global__ __launch_bounds__(256) void large_syrk(DevView d, LargeView<T> lv, in
 /// ways (the X update's workgroups inside this launch: 2436 us against 1997 + 324 per 256 filters; on a side stream: 31.7 k against 36.4 k filter-steps/s)
 /// and both lose: at this kernel's register footprint the latency-bound X-update workgroups take slots while the matrix pipes idle, and next to it they
 /// fight it for L2 (profiles/r04_experiments.md section 1).
-#ifndef ASLAM_XU_ROWS
-#define ASLAM_XU_ROWS 8
-#endif
-constexpr int XU_ROWS = ASLAM_XU_ROWS; // (rows per wave of large_x_update_rows; 4 and 16 measured in round 4: profiles/r04_experiments.md)
 ///
-/// PL = 1 (round 4; NOT integrated: the library always launches PL = 0 with LPlanes{nullptr}, and no kernel of the library writes V's planes; PL = 1 is
-/// instantiated by tools/ubench/syrk_bench.hip only): V arrives ALREADY SPLIT -- its producer would store the three bf16 planes of every solved block next to the binary32 V
-/// (`vpl`: [B][3][NP][NP], the columns of every 64-block permuted as in LPlanes; the permutation stays inside a 32-column half, and a slab's contraction
-/// order is the same for both operands) -- and a slab goes global -> LDS by LDS-DMA (twelve 1-KiB pieces per wave: 16 rows x 64 bytes each, the k-group
-/// swizzle applied on the source side): no staging registers, no VALU split (176 instructions per thread and slab: each element of V was split ~ 17 times,
-/// once per tile that reads it), no ds_write.  tools/ubench/syrk_bench.hip: K loop 1.81 -> see profiles/r04_experiments.md.
-template <int DIAG = 0, int PL = 0>
-__global__ __launch_bounds__(256, 3) void large_syrk_bf16x3(DevView d, LargeView<float> lv, LPlanes vpl, int nfilters, const int *skipped)
+/// What the chain does around this kernel, then: V arrives in binary32 (the TRSM's output) and is split by the VALU on the way into LDS -- no kernel of the
+/// library writes bf16 planes of V -- and the X update is a launch of its own, launch 6 of the chain, behind this one.
+/// RUNNING = false is the default chain's kernel.  RUNNING = true (ASLAM_SYRK_RUNNING=1) is round 2's accumulation order, kept for comparison: every tile
+/// takes the general path and the six products of a slab are added straight into the running sum (profiles/r03_experiments.md).
+template <bool RUNNING>
+__global__ __launch_bounds__(256, 3) void large_syrk_bf16x3(DevView d, LargeView<float> lv, int nfilters, const int *skipped)
 {
         constexpr int TB = 128, KC = 32;
         constexpr int LDB = KC; // bf16 per LDS row: 64 bytes, unpadded; the four 16-byte k-groups of a row are XOR-swizzled with (row & 15) >> 2, which
@@ -1129,42 +1128,12 @@ __global__ __launch_bounds__(256, 3) void large_syrk_bf16x3(DevView d, LargeView
                         acc[u][v] = (f4){0.f, 0.f, 0.f, 0.f};
         f4 ta[NPASS], tb[NPASS];
         auto fetch = [&](int kc) {
-                if constexpr (PL)
-                        return;
 #pragma unroll
                 for (int q = 0; q < NPASS; ++q)
                 {
                         ta[q] = *reinterpret_cast<const f4 *>(Ap[q] + kc);
                         tb[q] = *reinterpret_cast<const f4 *>(Bp[q] + kc);
                 }
-        };
-        // PL: the LDS-DMA of a slab.  Piece = 16 rows x 64 bytes of one plane: lane l = row l >> 2, LDS chunk l & 3, which holds logical k-group
-        // (l & 3) ^ ((row & 15) >> 2) = (l & 3) ^ (l >> 4) (the swizzle of the operand reads).  Wave w moves pieces 2 w, 2 w + 1 (rows 32 w .. 32 w + 31) of the
-        // three planes of A and of B.  Rows past NP read the next plane / zeros (buffer bounds): finite, and their results are never stored.
-        typedef __attribute__((address_space(3))) unsigned short lds_us;
-        const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(PL ? (void *)vpl.Lq(b, NP) : (void *)nullptr, 0, (int)(LPlanes::per_filter(NP) * 2), 0x00020000);
-        const unsigned dma_vo = (unsigned)(((lane >> 2) * NP) * 2 + (((lane & 3) ^ (lane >> 4)) * 16));
-        const unsigned ldsA = (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)(uintptr_t)(lds_us *)&As[0][0] + (unsigned)wave * 2048u));
-        const unsigned ldsB = (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)(uintptr_t)(lds_us *)&Bs[0][0] + (unsigned)wave * 2048u));
-        auto dma_slab = [&](int kc) {
-                const unsigned plane_b = (unsigned)(NP * NP * 2);
-                const unsigned soA = (unsigned)__builtin_amdgcn_readfirstlane(((rt * TB + 32 * wave) * NP + kc) * 2);
-                const unsigned soB = (unsigned)__builtin_amdgcn_readfirstlane(((jt * TB + 32 * wave) * NP + kc) * 2);
-                const unsigned r16 = (unsigned)(16 * NP * 2);
-#pragma unroll
-                for (int p = 0; p < 3; ++p)
-#pragma unroll
-                        for (int jj = 0; jj < 2; ++jj)
-                        {
-                                asm volatile("s_add_u32 m0, %0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds"
-                                             :
-                                             : "s"(ldsA), "n"(p * TB * LDB * 2 + jj * 1024), "v"(dma_vo), "s"(vrs), "s"(soA + (unsigned)p * plane_b + (unsigned)jj * r16)
-                                             : "m0", "scc", "memory");
-                                asm volatile("s_add_u32 m0, %0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds"
-                                             :
-                                             : "s"(ldsB), "n"(p * TB * LDB * 2 + jj * 1024), "v"(dma_vo), "s"(vrs), "s"(soB + (unsigned)p * plane_b + (unsigned)jj * r16)
-                                             : "m0", "scc", "memory");
-                        }
         };
         // four floats -> their three bf16 planes: x = h + m + l up to 2^-25 |x|.  Round to nearest at every level (v_cvt_pk_bf16_f32): with
         // truncated pieces, which all carry the sign of x, the dropped terms a2 b3 + a3 b2 have the sign of the product, V V^T comes out
@@ -1195,37 +1164,20 @@ __global__ __launch_bounds__(256, 3) void large_syrk_bf16x3(DevView d, LargeView
         const bool diagq = (rt == jt && wc == wr);
         const int nu = idle ? 0 : __builtin_amdgcn_readfirstlane(max(0, min(4, (n - (rt * TB + wr) + 15) >> 4)));
         const int nv = idle ? 0 : __builtin_amdgcn_readfirstlane(max(0, min(4, (n - (jt * TB + wc) + 15) >> 4)));
-        const bool full = !(DIAG & 2) && nu == 4 && nv == 4 && !diagq; // wave-uniform: an interior 64x64 quadrant
+        const bool full = !RUNNING && nu == 4 && nv == 4 && !diagq; // wave-uniform: an interior 64x64 quadrant
         const int kend = min(na, (n + KC - 1) / KC * KC); // columns n .. na-1 of V are zero (G = P H^T is zero there and L is the identity)
         const int a_off = (wr + li) * LDB + 8 * (lg ^ (li >> 2)), b_off = (wc + li) * LDB + 8 * (lg ^ (li >> 2)); // swizzled k-group
         const int s_off = lrow * LDB + 8 * ((lc0 >> 3) ^ ((lrow & 15) >> 2)) + (lc0 & 4); // this thread's 8 bytes of a staged row (rows lrow + 32 q: same row & 15)
         fetch(0);
         for (int kc = 0; kc < kend; kc += KC)
         {
-                if constexpr (PL)
-                {
-                        // single-buffered: the slab is fetched behind the barrier that ended the previous slab's reads; the two other workgroups of the CU
-                        // multiply while this one waits for its pieces
-                        dma_slab(kc);
-                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                }
-                else if (!(DIAG & 4) || kc == 0) // (DIAG 4, tools/ubench/syrk_bench.hip: timing without the split and the LDS stash -- stale LDS, wrong results)
-                {
 #pragma unroll
-                        for (int q = 0; q < NPASS; ++q)
-                        {
-                                stash(As, s_off + RPP * q * LDB, ta[q]);
-                                stash(Bs, s_off + RPP * q * LDB, tb[q]);
-                        }
-                }
-                else
+                for (int q = 0; q < NPASS; ++q)
                 {
-#pragma unroll
-                        for (int q = 0; q < NPASS; ++q)
-                                asm volatile("" ::"v"(ta[q]), "v"(tb[q])); // the loads stay
+                        stash(As, s_off + RPP * q * LDB, ta[q]);
+                        stash(Bs, s_off + RPP * q * LDB, tb[q]);
                 }
-                if (!(DIAG & 32)) // (DIAG 32: timing without the barriers -- racy)
-                        __syncthreads();
+                __syncthreads();
                 if (kc + KC < kend)
                         fetch(kc + KC);
                 // two column tiles of the wave's 64x64 at a time: 24 operand registers instead of 48 (three workgroups per CU).
@@ -1237,10 +1189,7 @@ __global__ __launch_bounds__(256, 3) void large_syrk_bf16x3(DevView d, LargeView
                 // (tools/ubench/syrk_accum.hip).  Interior tiles (the bulk) take the branch-free path, where the addition of a pair of
                 // temporaries is issued behind the MFMAs of the NEXT pair.
 #define ASLAM_MM(t, bb, aa, c) t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf8, bb), __builtin_bit_cast(bf8, aa), c, 0, 0, 0)
-                if (DIAG & 8) // (timing without the MFMAs)
-                {
-                }
-                else if (full)
+                if (full)
                 {
 #pragma unroll
                         for (int vh = 0; vh < 4; vh += 2)
@@ -1250,12 +1199,7 @@ __global__ __launch_bounds__(256, 3) void large_syrk_bf16x3(DevView d, LargeView
                                 for (int v = 0; v < 2; ++v)
 #pragma unroll
                                         for (int p = 0; p < 3; ++p)
-                                        {
-                                                if (DIAG & 16) // (timing without the operand reads)
-                                                        asm volatile("" : "=v"(bq[v][p]));
-                                                else
-                                                        bq[v][p] = *reinterpret_cast<const u4 *>(&Bs[p][b_off + 16 * (vh + v) * LDB]);
-                                        }
+                                                bq[v][p] = *reinterpret_cast<const u4 *>(&Bs[p][b_off + 16 * (vh + v) * LDB]);
                                 f4 pa = {0.f, 0.f, 0.f, 0.f}, pb = {0.f, 0.f, 0.f, 0.f}; // the previous row tile's pair, not yet added
 #pragma unroll
                                 for (int u = 0; u < 4; ++u)
@@ -1263,12 +1207,7 @@ __global__ __launch_bounds__(256, 3) void large_syrk_bf16x3(DevView d, LargeView
                                         u4 ap[3];
 #pragma unroll
                                         for (int p = 0; p < 3; ++p)
-                                        {
-                                                if (DIAG & 16)
-                                                        asm volatile("" : "=v"(ap[p]));
-                                                else
-                                                        ap[p] = *reinterpret_cast<const u4 *>(&As[p][a_off + 16 * u * LDB]);
-                                        }
+                                                ap[p] = *reinterpret_cast<const u4 *>(&As[p][a_off + 16 * u * LDB]);
                                         f4 ta, tb;
                                         ASLAM_MM(ta, bq[0][0], ap[2], ((f4){0.f, 0.f, 0.f, 0.f}));
                                         ASLAM_MM(tb, bq[1][0], ap[2], ((f4){0.f, 0.f, 0.f, 0.f}));
@@ -1318,7 +1257,7 @@ __global__ __launch_bounds__(256, 3) void large_syrk_bf16x3(DevView d, LargeView
                                                         if (vh + v < nv && !(diagq && vh + v > u))
                                                         {
                                                                 f4 tmp;
-                                                                if constexpr (DIAG & 2) // diagnostic build only (trsm_bench): round 2's running accumulator
+                                                                if constexpr (RUNNING) // round 2's running accumulator
                                                                 {
                                                                         ASLAM_MM(tmp, bq[v][0], ap[2], acc[u][vh + v]);
                                                                         ASLAM_MM(tmp, bq[v][1], ap[1], tmp);
@@ -1341,24 +1280,10 @@ __global__ __launch_bounds__(256, 3) void large_syrk_bf16x3(DevView d, LargeView
                         }
                 }
 #undef ASLAM_MM
-                if (!(DIAG & 32)) // (DIAG 32: timing without the barriers -- racy)
-                        __syncthreads();
+                __syncthreads();
         }
         if (idle)
                 return;
-        if constexpr (DIAG & 1)
-        {
-                // diagnostic build only (tools/ubench/trsm_bench.hip): the K loop without the read-modify-write of P
-                float sres = 0.f;
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                        for (int v = 0; v < 4; ++v)
-                                sres += acc[u][v][0] + acc[u][v][1] + acc[u][v][2] + acc[u][v][3];
-                if (sres == 12345.678f)
-                        P[0] = sres;
-                return;
-        }
         const bool mirror = (jt < rt || wc < wr);
         // The DIAGONAL of V V^T and its three POSE columns (and their mirror image, the pose rows) are formed with binary64 accumulation by the X-update
         // kernel (large_x_update_rows) and are NOT TOUCHED here -- not even read and stored back (a store-back of an old value would tie the order of the two
@@ -1428,14 +1353,8 @@ __global__ __launch_bounds__(256, 3) void large_syrk_bf16x3(DevView d, LargeView
 }
 
 /// X <- X + V q with q = row n of G = (L^-1 Y)^T; one wave per state row.  grid (ceil(NP/4), B), 256 threads.  In replay
-/// mode also writes the pose of this callback.
-///
-/// binary32 chain (SLIM): the same pass over row a of V also forms, with binary64 accumulation, the entries of V V^T that large_syrk_bf16x3
-/// leaves out -- the DIAGONAL (a sum of squares: every rounding of an fp32 accumulator chain pulls it the same way, and the covariance
-/// diagonal is where the error of the fp32 path was largest) and the three POSE columns (the pose block changes by as much as it holds in
-/// every callback, Q against the update, so eps32 |dP| is eps32 |P| there) -- and subtracts them from P: P(a,a), P(a,0..2) and the mirror
-/// image P(0..2,a).  Costs four more FMAs per element of a row the kernel reads anyway.
-template <typename T, int MODE, bool SLIM = false>
+/// mode also writes the pose of this callback.  The binary64 chain's X update; the binary32 chain runs large_x_update_rows below.
+template <typename T, int MODE>
 __global__ __launch_bounds__(256) void large_x_update(DevView d, LargeView<T> lv, int s, int nsteps, double *poses_out,
                                                       int32_t *dims_out, const int *skipped)
 {
@@ -1452,51 +1371,12 @@ __global__ __launch_bounds__(256) void large_x_update(DevView d, LargeView<T> lv
         // 16 bytes per lane and load (rows are 256-byte aligned: NP is a multiple of 64); columns n .. of both rows are zero
         typedef T vec_t __attribute__((ext_vector_type(16 / sizeof(T))));
         constexpr int VW = 16 / sizeof(T);
-        if constexpr (SLIM)
+        for (int j = VW * lane; j < n; j += 64 * VW)
         {
-                const T *p0 = lv.G + (size_t)b * NP * NP, *p1 = p0 + NP, *p2 = p1 + NP;
-                double dd = 0.0, d0 = 0.0, d1 = 0.0, d2 = 0.0;
-                for (int j = VW * lane; j < n; j += 64 * VW)
-                {
-                        const vec_t v = *reinterpret_cast<const vec_t *>(vrow + j), w = *reinterpret_cast<const vec_t *>(q + j);
-                        const vec_t u0 = *reinterpret_cast<const vec_t *>(p0 + j), u1 = *reinterpret_cast<const vec_t *>(p1 + j),
-                                    u2 = *reinterpret_cast<const vec_t *>(p2 + j);
+                const vec_t v = *reinterpret_cast<const vec_t *>(vrow + j), w = *reinterpret_cast<const vec_t *>(q + j);
 #pragma unroll
-                        for (int e = 0; e < VW; ++e)
-                        {
-                                const double ve = (double)v[e];
-                                acc = fma(ve, (double)w[e], acc);
-                                dd = fma(ve, ve, dd);
-                                d0 = fma(ve, (double)u0[e], d0);
-                                d1 = fma(ve, (double)u1[e], d1);
-                                d2 = fma(ve, (double)u2[e], d2);
-                        }
-                }
-                dd = wave_sum_dpp(dd), d0 = wave_sum_dpp(d0), d1 = wave_sum_dpp(d1), d2 = wave_sum_dpp(d2);
-                if (lane == 63)
-                {
-                        double *P = lv.P + (size_t)b * NP * NP;
-                        double *prow = P + (size_t)a * NP;
-                        const double dp[3] = {d0, d1, d2};
-                        // pose columns j < min(a, 3) with their mirror image; the diagonal entry itself (a < 3: dd == dp[a] bit for bit)
-                        for (int j = 0; j < 3 && j < a; ++j)
-                        {
-                                const double pn = prow[j] - dp[j];
-                                prow[j] = pn;
-                                P[(size_t)j * NP + a] = pn;
-                        }
-                        prow[a] -= dd;
-                }
-        }
-        else
-        {
-                for (int j = VW * lane; j < n; j += 64 * VW)
-                {
-                        const vec_t v = *reinterpret_cast<const vec_t *>(vrow + j), w = *reinterpret_cast<const vec_t *>(q + j);
-#pragma unroll
-                        for (int e = 0; e < VW; ++e)
-                                acc = fma((double)v[e], (double)w[e], acc);
-                }
+                for (int e = 0; e < VW; ++e)
+                        acc = fma((double)v[e], (double)w[e], acc);
         }
         acc = wave_sum_dpp(acc);
         if (lane == 63)
@@ -1512,7 +1392,11 @@ __global__ __launch_bounds__(256) void large_x_update(DevView d, LargeView<T> lv
                 }
         }
 }
-/// binary32 chain: X <- X + V q, and the diagonal + the three pose columns of V V^T in binary64 (see large_x_update<.., SLIM>), with the four rows
+/// binary32 chain: X <- X + V q, and -- in the same pass over row a of V, with binary64 accumulation -- the entries of V V^T that large_syrk_bf16x3
+/// leaves out: the DIAGONAL (a sum of squares: every rounding of an fp32 accumulator chain pulls it the same way, and the covariance
+/// diagonal is where the error of the fp32 path was largest) and the three POSE columns (the pose block changes by as much as it holds in
+/// every callback, Q against the update, so eps32 |dP| is eps32 |P| there), which are subtracted from P: P(a,a), P(a,0..2) and the mirror
+/// image P(0..2,a).  Costs four more FMAs per element of a row the kernel reads anyway.  The four rows
 /// every row of V is multiplied with -- q and the pose rows of V -- staged ONCE per workgroup in LDS (17 KB) for the XU_ROWS x 4 rows its waves
 /// walk.  With a wave per row and the shared rows read from memory every wave issued 25 loads of 16 bytes per lane for 4 KB of new data: 391 us
 /// per 256 filters against 217 us for round 2's single product (profiles/r03_experiments.md).  grid (ceil(NP / (4 XU_ROWS)), B), 256 threads.

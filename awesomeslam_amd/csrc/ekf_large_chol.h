@@ -459,7 +459,7 @@ __global__ __launch_bounds__(256, 1) void large_chol_resident(DevView d, LargeVi
                 const TrsmSeq seq_diag(Sb, Linv, I, I + 1, NP, tid); // the history blocks of the diagonal block: L(I, 0 .. I-1), this sweep's own output
                 TrsmPipe pp = {pipe, pipe + LB * TRSM_LDT, pipe + 2 * LB * TRSM_LDT, &sync_ctr, nsig, 0u};
                 f4 c[4];
-                trsm_sweep<0, true>(c, rsb, vs, I, seq, seq_diag, pp, a_off, tid, rq, vq0 + (unsigned)(LB * I * NP * 2), qplane);
+                trsm_sweep<true>(c, rsb, vs, I, seq, seq_diag, pp, a_off, tid, rq, vq0 + (unsigned)(LB * I * NP * 2), qplane);
                 nsig = pp.nsig;
                 lost |= pp.lost;
                 __syncthreads(); // every wave is done with the pipeline buffers: the tiles take their place

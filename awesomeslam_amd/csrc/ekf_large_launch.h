@@ -65,7 +65,7 @@ struct LargePlan
         LargeChain chain;
         bool chol16, trsm16;         // F32_RESIDENT: large_chol_bf16 for large_chol_resident, large_trsm_bf16 for large_trsm_pipe
         bool chol_f32out;            // large_chol_bf16 also stores the off-diagonal blocks of L in binary32 (the bf16 TRSM reads L through its planes only)
-        bool gs_tiles, syrk_running; // large_build_GS_tiles for large_build_GS; large_syrk_bf16x3<2> for <0>
+        bool gs_tiles, syrk_running; // large_build_GS_tiles for large_build_GS; large_syrk_bf16x3<true> for <false>
         int launches;                // kernel launches per callback and stream group
         bool need_Lpl, need_Vw;      // buffers a context of `batch` filters owns besides P, G, S, Hc, Y, Linv
 };
@@ -198,7 +198,7 @@ void launch_large_chain(const LargePlan &plan, const LargeGroup<T> &g, size_t ld
                         hipLaunchKernelGGL(large_update_panel<T>, dim3((2 * NB - k) / 2, 1, gb), dim3(256), 0, g.st, g.dv, g.v, k, 0, g.skip);
                 }
                 hipLaunchKernelGGL(large_syrk<T>, syrk_grid, dim3(256), 0, g.st, g.dv, g.v, gb, g.skip);
-                hipLaunchKernelGGL((large_x_update<T, MODE, false>), dim3((NP + 3) / 4, gb), dim3(256), 0, g.st, g.dv, g.v, s, nsteps, g.poses, g.dims, g.skip);
+                hipLaunchKernelGGL((large_x_update<T, MODE>), dim3((NP + 3) / 4, gb), dim3(256), 0, g.st, g.dv, g.v, s, nsteps, g.poses, g.dims, g.skip);
                 if (g.sv.any())
                         hipLaunchKernelGGL(large_stats<T>, dim3(gb), dim3(256), 0, g.st, g.dv, g.v, s, nsteps, g.sv, g.skip);
         }
@@ -236,9 +236,9 @@ void launch_large_chain(const LargePlan &plan, const LargeGroup<T> &g, size_t ld
                         hipLaunchKernelGGL(large_trsm_pipe<LARGE_NB_MAX>, dim3(8 * ((gb + 7) / 8) * NB), dim3(256), 0, g.st, g.dv, g.v, gb, g.skip);
                 }
                 if (plan.syrk_running)
-                        hipLaunchKernelGGL((large_syrk_bf16x3<2>), syrk_grid, dim3(256), 0, g.st, g.dv, vv, LPlanes{nullptr}, gb, g.skip);
+                        hipLaunchKernelGGL((large_syrk_bf16x3<true>), syrk_grid, dim3(256), 0, g.st, g.dv, vv, gb, g.skip);
                 else
-                        hipLaunchKernelGGL((large_syrk_bf16x3<0>), syrk_grid, dim3(256), 0, g.st, g.dv, vv, LPlanes{nullptr}, gb, g.skip);
+                        hipLaunchKernelGGL((large_syrk_bf16x3<false>), syrk_grid, dim3(256), 0, g.st, g.dv, vv, gb, g.skip);
                 // X += V q (+ the diagonal and the pose columns of V V^T in binary64) BEHIND the syrk on the same stream.  Round 4 tried the two ways of
                 // running it next to the syrk -- its workgroups inside the syrk launch, and on a side stream of its own (the two write disjoint entries
                 // of P) -- and both were slower: 2436 us against 1997 + 324 per 256 filters, and 31.7 k against 36.4 k filter-steps/s

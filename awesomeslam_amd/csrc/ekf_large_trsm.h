@@ -239,7 +239,6 @@ struct TrsmSeq
         unsigned offh, offl;       // byte offsets of L(k, 0) inside S and of Linv_k inside Linv (this filter's)
         unsigned voh, vol;         // this thread's byte offset inside a block of L (row stride NP) / of Linv (row stride 64): row tid >> 4, columns 4 (tid & 15) ..
         __amdgpu_buffer_rsrc_t rs, rl;
-        int pin = 0; // diagnostic (trsm_bench, DIAG & 32): every fetch reads block 0 of S -- L1 hits instead of L2 / HBM
         __device__ __forceinline__ TrsmSeq(const float *Sb, const float *Linv, int k0, int nb_, int NP_, int tid)
             : k(k0), j(0), nb(nb_), NP(NP_), offh((unsigned)(LB * k0) * NP_ * 4u), offl((unsigned)k0 * LB * LB * 4u),
               voh((unsigned)(((tid >> 4) * NP_ + (tid & 15) * 4) * 4)), vol((unsigned)(((tid >> 4) * LB + (tid & 15) * 4) * 4)),
@@ -253,7 +252,7 @@ struct TrsmSeq
                 typedef unsigned u4 __attribute__((ext_vector_type(4)));
                 const bool hist = j < k;
                 const __amdgpu_buffer_rsrc_t r = hist ? rs : rl;
-                const unsigned so = pin ? 0u : hist ? offh + (unsigned)(LB * 4 * j) : offl;
+                const unsigned so = hist ? offh + (unsigned)(LB * 4 * j) : offl;
                 const unsigned ldb = (unsigned)(hist ? NP : LB) * 64u; // bytes between rows r and r + 16
                 const unsigned vo = hist ? voh : vol;
 #pragma unroll
@@ -324,7 +323,7 @@ struct TrsmPipe
 };
 
 /// one history block with fragments a0 (column tile 0) and a1 (column tile 1) of it already in registers; leaves a0 / a1 of the NEXT block
-template <int J, int DIAG>
+template <int J>
 __device__ __forceinline__ void trsm_history_pipe(f4 (&c)[4], f4 (&a0)[4], f4 (&a1)[4], f4 (&pf)[4], TrsmPipe &pp, TrsmSeq &seq, int a_off, int tid)
 {
         typedef __attribute__((address_space(3))) float lds_float;
@@ -334,46 +333,33 @@ __device__ __forceinline__ void trsm_history_pipe(f4 (&c)[4], f4 (&a0)[4], f4 (&
         trsm_half_a<4 * J + 0, 2>(c[0], c[1], c[2], c[3], a0[0], a0[1], a0[2], a0[3], a2, rd_cur);
         trsm_half_b<4 * J + 0>(c[0], c[1], c[2], c[3], a0[0], a0[1], a0[2], a0[3]);
         // group 1 (column tile 1), reading column tile 3 -- the last read of buffer `cur` -- and the synchronisation counter
-        if constexpr (!(DIAG & 2) && !(DIAG & 16))
-                trsm_half_a_peek<4 * J + 1, 3>(c[0], c[1], c[2], c[3], a1[0], a1[1], a1[2], a1[3], a3, rd_cur, pp.ctr_lds(), pp.seen);
-        else
-                trsm_half_a<4 * J + 1, 3>(c[0], c[1], c[2], c[3], a1[0], a1[1], a1[2], a1[3], a3, rd_cur);
+        trsm_half_a_peek<4 * J + 1, 3>(c[0], c[1], c[2], c[3], a1[0], a1[1], a1[2], a1[3], a3, rd_cur, pp.ctr_lds(), pp.seen);
         trsm_half_b<4 * J + 1>(c[0], c[1], c[2], c[3], a1[0], a1[1], a1[2], a1[3]);
         // The synchronisation point of this block (TrsmPipe).  It orders (a) the stash of block i + 1 (third group of the PREVIOUS block) before
         // the first read of that data (in the third group of this block) and (b) every wave's reads of the previous block's buffer before
         // the stash below overwrites it -- events a whole block apart.
-        if constexpr (!(DIAG & 2) && !(DIAG & 16)) // (16: timing experiment without the synchronisation -- racy)
-                pp.wait();
-        else
-                asm volatile("" ::: "memory");
+        pp.wait();
         // group 2 (column tile 2): block i + 2 -> LDS (fetched while block i - 1 was multiplied) and the signal between its MFMAs, reading
         // column tile 0 of the NEXT block; block i + 3 -> registers behind it
-        if constexpr (!(DIAG & 2))
-        {
-                const unsigned lds = (unsigned)(uintptr_t)(lds_float *)(pp.far + (tid >> 4) * TRSM_LDT + (tid & 15) * 4);
-                trsm_half_a_stash<4 * J + 2, 0>(c[0], c[1], c[2], c[3], a2[0], a2[1], a2[2], a2[3], a0, rd_nxt, pf, lds, pp.ctr_lds());
-                if constexpr (!(DIAG & 16))
-                        ++pp.nsig;
-        }
-        else
-                trsm_half_a<4 * J + 2, 0>(c[0], c[1], c[2], c[3], a2[0], a2[1], a2[2], a2[3], a0, rd_nxt);
+        const unsigned lds = (unsigned)(uintptr_t)(lds_float *)(pp.far + (tid >> 4) * TRSM_LDT + (tid & 15) * 4);
+        trsm_half_a_stash<4 * J + 2, 0>(c[0], c[1], c[2], c[3], a2[0], a2[1], a2[2], a2[3], a0, rd_nxt, pf, lds, pp.ctr_lds());
+        ++pp.nsig;
         trsm_half_b<4 * J + 2>(c[0], c[1], c[2], c[3], a2[0], a2[1], a2[2], a2[3]);
-        if constexpr (!(DIAG & 1))
-                seq.fetch(pf);
+        seq.fetch(pf);
         // group 3 (column tile 3), reading column tile 1 of the next block
         trsm_half_a<4 * J + 3, 1>(c[0], c[1], c[2], c[3], a3[0], a3[1], a3[2], a3[3], a1, rd_nxt);
         trsm_half_b<4 * J + 3>(c[0], c[1], c[2], c[3], a3[0], a3[1], a3[2], a3[3]);
         pp.rotate();
 }
 
-template <int J, int DIAG>
+template <int J>
 __device__ __forceinline__ void trsm_chain_pipe(f4 (&c)[4], f4 (&a0)[4], f4 (&a1)[4], f4 (&pf)[4], int k, TrsmPipe &pp, TrsmSeq &seq, int a_off, int tid)
 {
         if (J < k)
         {
-                trsm_history_pipe<J, DIAG>(c, a0, a1, pf, pp, seq, a_off, tid);
+                trsm_history_pipe<J>(c, a0, a1, pf, pp, seq, a_off, tid);
                 if constexpr (J + 1 < LARGE_NB_MAX - 1)
-                        trsm_chain_pipe<J + 1, DIAG>(c, a0, a1, pf, k, pp, seq, a_off, tid);
+                        trsm_chain_pipe<J + 1>(c, a0, a1, pf, k, pp, seq, a_off, tid);
         }
 }
 
@@ -403,7 +389,7 @@ __device__ __forceinline__ void trsm_pipe_start(f4 (&pf)[4], f4 (&a0)[4], f4 (&a
 /// large_trsm_bf16 streams (ekf_large_trsm16.h: position 32 (t >> 1) + 8 lg + 4 (t & 1) + r holds column 16 t + 4 lg + r, so row tiles 2 u and
 /// 2 u + 1 of a lane make one 16-byte store) -- buffer resource of the filter's planes, this lane's byte offset inside a plane (row, + 8 lg
 /// elements), bytes per plane.
-template <int DIAG, bool CHOL>
+template <bool CHOL>
 __device__ __forceinline__ void trsm_sweep(f4 (&c)[4], __amdgpu_buffer_rsrc_t rg, unsigned vg, int nbk, TrsmSeq &seq, const TrsmSeq &seq_diag, TrsmPipe &pp,
                                            int a_off, int tid, __amdgpu_buffer_rsrc_t rq, unsigned vq, unsigned qplane)
 {
@@ -437,7 +423,7 @@ __device__ __forceinline__ void trsm_sweep(f4 (&c)[4], __amdgpu_buffer_rsrc_t rg
                         seq = seq_diag; // L(nbk, 0), ..., L(nbk, nbk - 1)
                         trsm_pipe_start(pf, a0, a1, pp, seq, a_off, tid);
                 }
-                trsm_chain_pipe<0, DIAG>(c, a0, a1, pf, k, pp, seq, a_off, tid);
+                trsm_chain_pipe<0>(c, a0, a1, pf, k, pp, seq, a_off, tid);
                 // ---- the closing block of column k: C = G - history, X = Linv_k C (a0 = tiles (t, 0), a1 = tiles (t, 1) of Linv_k)
                 asm volatile("s_nop 15" : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3])); // MFMA result -> VALU read
 #pragma unroll
@@ -451,25 +437,16 @@ __device__ __forceinline__ void trsm_sweep(f4 (&c)[4], __amdgpu_buffer_rsrc_t rg
                 for (int t = 0; t < 4; ++t)
                         x[t] = (f4){0.f, 0.f, 0.f, 0.f};
                 trsm_mfma_x<4>(x[0], x[1], x[2], x[3], a0[0], a0[1], a0[2], a0[3], c[0]);
-                if constexpr (!(DIAG & 2) && !(DIAG & 16))
-                        pp.peek();
+                pp.peek();
                 // fragments (2,2), (3,2), (3,3) of Linv_k
                 a0[2] = *reinterpret_cast<const f4 *>(pp.cur + a_off + 32 * TRSM_LDT + 32);
                 a0[3] = *reinterpret_cast<const f4 *>(pp.cur + a_off + 48 * TRSM_LDT + 32);
                 a0[0] = *reinterpret_cast<const f4 *>(pp.cur + a_off + 48 * TRSM_LDT + 48);
                 // the synchronisation point of this block (see trsm_history_pipe): the three reads above stay in flight
-                if constexpr (!(DIAG & 2) && !(DIAG & 16))
-                        pp.wait();
-                else
-                        asm volatile("" ::: "memory");
-                if constexpr (!(DIAG & 2))
-                {
-                        trsm_stash(pp.far, pf, tid);
-                        if constexpr (!(DIAG & 16))
-                                pp.signal(tid & 63);
-                }
-                if constexpr (!(DIAG & 1))
-                        seq.fetch(pf);
+                pp.wait();
+                trsm_stash(pp.far, pf, tid);
+                pp.signal(tid & 63);
+                seq.fetch(pf);
                 trsm_mfma_x<3>(x[0], x[1], x[2], x[3], a1[1], a1[2], a1[3], a1[3], c[1]);
                 trsm_mfma_x<2>(x[0], x[1], x[2], x[3], a0[2], a0[3], a0[3], a0[3], c[2]);
                 trsm_frags(a1, pp.nxt, a_off, 1);
@@ -541,7 +518,8 @@ __device__ __forceinline__ void trsm_sweep(f4 (&c)[4], __amdgpu_buffer_rsrc_t rg
 /// V = G L^-T.  grid (8 * ceil(B / 8) * NP / 64), 256 threads; wave w of a workgroup owns 16 rows of G.  In place: G -> V.
 /// The 17 workgroups of a filter stream the same blocks of L: they are dealt to ONE XCD (workgroup i runs on XCD i % 8), next to each other
 /// in its dispatch order, so that a block comes from HBM once and from that XCD's L2 sixteen times (PMC: 23.6 -> MB per filter and callback).
-template <int NBMAX, int DIAG = 0>
+/// STAMP (tools/ubench/trsm_bench.hip only): every workgroup writes the shader cycles and the 100 MHz ticks of its sweep to lv.Y[2 wg], lv.Y[2 wg + 1].
+template <int NBMAX, bool STAMP = false>
 __global__ __launch_bounds__(256, 1) void large_trsm_pipe(DevView d, LargeView<float> lv, int nfilters, const int *skipped)
 {
         static_assert(NBMAX == 17, "trsm_sweep lists 17 block columns");
@@ -561,23 +539,21 @@ __global__ __launch_bounds__(256, 1) void large_trsm_pipe(DevView d, LargeView<f
         const int a_off = li * TRSM_LDT + 4 * lg;
         asm volatile("" ::: "a0", "a255"); // the strip (see above)
         unsigned long long t0_ = 0, r0_ = 0;
-        if constexpr (DIAG & 8)
+        if constexpr (STAMP)
         {
                 t0_ = __builtin_amdgcn_s_memtime();
                 r0_ = __builtin_amdgcn_s_memrealtime();
         }
         TrsmSeq seq(lv.S + (size_t)b * NP * NP, lv.Linv + (size_t)b * LARGE_NB_MAX * LB * LB, 0, nb, NP, tid);
-        if constexpr (DIAG & 32)
-                seq.pin = 1;
         __shared__ unsigned sync_ctr;
         if (tid == 0)
                 sync_ctr = 0; // (the first barrier of the sweep publishes it)
         TrsmPipe pp = {lds[0], lds[1], lds[2], &sync_ctr, 0u, 0u};
         f4 c[4];
-        trsm_sweep<DIAG, false>(c, rg, vg, nb, seq, seq, pp, a_off, tid, rg, 0u, 0u);
+        trsm_sweep<false>(c, rg, vg, nb, seq, seq, pp, a_off, tid, rg, 0u, 0u);
         if (pp.lost && lane == 0)
                 atomicOr(&d.status[b], 16u); // ASLAM_ST_INTERNAL
-        if constexpr (DIAG & 8)
+        if constexpr (STAMP)
         {
                 if (tid == 0)
                 {

@@ -195,7 +195,7 @@ struct Pipe
         unsigned short *b0, *b1, *b2, *b3, *b4;
         // diagnostic builds (STAMP): shader cycles by phase -- 0 first-half region, 1 between the halves, 2 second-half region, 3 end (barrier), 4 closing block
         unsigned long long ph[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast = 0; // 5 .. 8: inside the closing block (C + split, first half, second half, strip write); 9 .. 12: the wait for the slice of the rows, its LDS reads + the issue of the next slice, the stores, the vmcnt wait at the end
-        template <int STAMP> __device__ __forceinline__ void stamp(int i)
+        template <bool STAMP> __device__ __forceinline__ void stamp(int i)
         {
                 if constexpr (STAMP)
                 {
@@ -267,7 +267,7 @@ struct Regs
 /// (-> set Q), and the finished sums of the previous block are added to the column's running sum; inside those of the second half: the same for the
 /// first half of the next block in the stream (history block J + 1 of this column, whose operand rows are in b1 -- or the closing block, whose B
 /// operand is not a strip tile: that split is wasted).  Both halves carry three of the six DMA pieces of the block three ahead.
-template <int J, int STAMP, int NST> __device__ __forceinline__ void history_block(Regs &R, Pipe &pp, Seq &seq, int a_h0, int a_h1, int tid)
+template <int J, bool STAMP, int NST> __device__ __forceinline__ void history_block(Regs &R, Pipe &pp, Seq &seq, int a_h0, int a_h1, int tid)
 {
         typedef __attribute__((address_space(3))) unsigned short lds_us;
         const Dma dm = seq.next();
@@ -289,15 +289,7 @@ template <int J, int STAMP, int NST> __device__ __forceinline__ void history_blo
         const unsigned a_nxt = (unsigned)(uintptr_t)(lds_us *)(pp.b1 + a_h0); // the first half of the next block
         constexpr int RN = (J + 1 < LARGE_NB_MAX - 1) ? 16 * (J + 1) : 0;
         pp.template stamp<STAMP>(1);
-        if constexpr (STAMP == 2)
-                asm volatile(ASLAM_T16_H1_E_NOVALU : "+{v[32:47]}"(R.e), ASLAM_T16_P_OUT : ASLAM_T16_Q_IN, ASLAM_T16_COMMON(a_nxt, RN, 3) : ASLAM_T16_SCRATCH);
-        else if constexpr (STAMP == 3)
-                asm volatile(ASLAM_T16_H1_E_NODS : "+{v[32:47]}"(R.e), ASLAM_T16_P_OUT : ASLAM_T16_Q_IN, ASLAM_T16_COMMON(a_nxt, RN, 3) : ASLAM_T16_SCRATCH);
-        else if constexpr (STAMP == 5) // (the block's pieces 3 .. 5 are never fetched: timing only)
-                asm volatile(ASLAM_T16_H1_E_NODMA : "+{v[32:47]}"(R.e), ASLAM_T16_P_OUT : ASLAM_T16_Q_IN, ASLAM_T16_COMMON(a_nxt, RN, 3) : ASLAM_T16_SCRATCH);
-        else if constexpr (STAMP == 4)
-                asm volatile(ASLAM_T16_H1_E_BARE : "+{v[32:47]}"(R.e), ASLAM_T16_P_OUT : ASLAM_T16_Q_IN, ASLAM_T16_COMMON(a_nxt, RN, 3) : ASLAM_T16_SCRATCH);
-        else if constexpr (J % 2 == 0)
+        if constexpr (J % 2 == 0)
                 asm volatile(ASLAM_T16_H1_E : "+{v[32:47]}"(R.e), ASLAM_T16_P_OUT : ASLAM_T16_Q_IN, ASLAM_T16_COMMON(a_nxt, RN, 3) : ASLAM_T16_SCRATCH);
         else
                 asm volatile(ASLAM_T16_H1_O : "+{v[48:63]}"(R.o), ASLAM_T16_P_OUT : ASLAM_T16_Q_IN, ASLAM_T16_COMMON(a_nxt, RN, 3) : ASLAM_T16_SCRATCH);
@@ -306,7 +298,7 @@ template <int J, int STAMP, int NST> __device__ __forceinline__ void history_blo
         pp.template stamp<STAMP>(3);
 }
 
-template <int J, int STAMP, int NST> __device__ __forceinline__ void chain(Regs &R, int k, Pipe &pp, Seq &seq, int a_h0, int a_h1, int tid)
+template <int J, bool STAMP, int NST> __device__ __forceinline__ void chain(Regs &R, int k, Pipe &pp, Seq &seq, int a_h0, int a_h1, int tid)
 {
         if (J < k)
         {
@@ -361,7 +353,7 @@ struct Rows
 /// caller to factor.  `lds`: four block buffers; `gl`: this wave's 16 x 64 floats for the slices of the rows.
 /// F32OUT (CHOL only): also store the solved columns in binary32 (the L of large_trsm_pipe and of the diagnostics); the default chain reads L through its
 /// planes only, and the Cholesky is HBM-bound: 2.1 MB of stores per filter less.
-template <int STAMP, bool CHOL, bool F32OUT = true>
+template <bool STAMP, bool CHOL, bool F32OUT = true>
 __device__ __forceinline__ void sweep16(f4 (&cdiag)[4], Regs &R, Pipe &pp, unsigned short (*lds)[BLK], float *gl, const Planes &pl, int b, int nbk, int nb_rows, int NP,
                                         const Rows &rows, int tid)
 {
@@ -536,7 +528,7 @@ __device__ __forceinline__ void sweep16(f4 (&cdiag)[4], Regs &R, Pipe &pp, unsig
 
 /// V = G L^-T on the bf16 pipe.  grid (8 * ceil(B / 8) * NP / 64), 256 threads; wave w of a workgroup owns 16 rows of G; in place: G -> V.
 /// Same workgroup -> (filter, row block) map as large_trsm_pipe (a filter's workgroups share one XCD).
-template <int NBMAX, int STAMP = 0>
+template <int NBMAX, bool STAMP = false>
 __global__ __launch_bounds__(256, 1) void large_trsm_bf16(DevView d, LargeView<float> lv, t16::Planes pl, int nfilters, const int *skipped)
 {
         using namespace t16;
@@ -620,7 +612,7 @@ __global__ __launch_bounds__(256, 1) void large_chol_bf16(DevView d, LargeView<f
                         asm volatile("; ASLAM_STRIP_LIVE_BEGIN vmem: global_store_dwordx4=4 buffer_store_dwordx4=6" ::: "memory"); // (tools/check_vmcnt_protocol.py)
                 else
                         asm volatile("; ASLAM_STRIP_LIVE_BEGIN vmem: buffer_store_dwordx4=6" ::: "memory");
-                sweep16<0, true, F32OUT>(c, R, pp, lds, gl[wv], pl, b, I, nb, NP, rows, tid);
+                sweep16<false, true, F32OUT>(c, R, pp, lds, gl[wv], pl, b, I, nb, NP, rows, tid);
                 asm volatile("; ASLAM_STRIP_LIVE_END" ::: "memory");
                 // every DMA piece still in flight targets the buffers the tiles are about to take
                 asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");

@@ -164,7 +164,7 @@ template <int NT> struct SmallLayout
 };
 
 /// Sum of x over the 64 lanes of a wave, valid in lane 63, by DPP moves only (quad permutes, row mirrors, row broadcasts: VALU instructions).
-/// __shfl_xor is a ds_bpermute -- an LDS crossbar instruction: the five binary64 sums per row of large_x_update<.., SLIM> were 60 of them per
+/// __shfl_xor is a ds_bpermute -- an LDS crossbar instruction: the five binary64 sums per row of large_x_update_rows were 60 of them per
 /// wave and made the kernel LDS-bound (393 us per 256 filters against 217 for the one sum of round 2; profiles/r03_experiments.md).
 __device__ __forceinline__ double wave_sum_dpp(double x)
 {

@@ -36,6 +36,11 @@ def chol_mode(dtype, monkeypatch):
         monkeypatch.setenv("ASLAM_BF16_PIPE", dtype.split("-pipe")[1])
     else:
         monkeypatch.delenv("ASLAM_BF16_PIPE", raising=False)
+    # "-running": large_syrk_bf16x3<RUNNING = true>, round 2's accumulation order (ASLAM_SYRK_RUNNING=1)
+    if "-running" in dtype:
+        monkeypatch.setenv("ASLAM_SYRK_RUNNING", "1")
+    else:
+        monkeypatch.delenv("ASLAM_SYRK_RUNNING", raising=False)
     return dtype.split("-")[0]
 
 
@@ -55,8 +60,14 @@ def synth(n, seed):
 
 # 191 / 193: n + 1 (state rows + the Y^T row) exactly fills / just overflows three 64-blocks; 1087 = the largest state the
 # path takes (17 blocks, NP = 1088: the last 128-row syrk tile and the last update_panel pair hang over the allocation)
-@pytest.mark.parametrize("n,steps", [(145, 3), (191, 3), (193, 3), (203, 3), (321, 3), (515, 3), (1087, 1)])
-@pytest.mark.parametrize("dtype", ["f64", "f32", "f32-resident"])
+SYNTH_CASES = [pytest.param(n, steps, dtype, id=f"{dtype}-{n}-{steps}")
+               for n, steps in [(145, 3), (191, 3), (193, 3), (203, 3), (321, 3), (515, 3), (1087, 1)] for dtype in ["f64", "f32", "f32-resident"]]
+# the syrk with the running accumulator, which nothing else launches: n = 321 is NP = 384 = three 128-row tiles -- a diagonal tile, an
+# off-diagonal tile and a partly filled one
+SYNTH_CASES.append(pytest.param(321, 3, "f32-running", id="f32-running-321-3"))
+
+
+@pytest.mark.parametrize("n,steps,dtype", SYNTH_CASES)
 def test_single_slam_on_synthetic_state(n, steps, dtype, built, monkeypatch):
     from awesomeslam_amd.core import Core, F32, F64
     from oracle.c_oracle import CFilter

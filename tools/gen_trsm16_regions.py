@@ -1,5 +1,6 @@
 """Generator of awesomeslam_amd/csrc/ekf_large_trsm16_regions.inc: the hand-scheduled half-block regions of the bf16-pipe sweep
-(ekf_large_trsm16.h).
+(ekf_large_trsm16.h) -- exactly the regions the library compiles -- and of tools/ubench/trsm16_right_looking_regions.inc: the three regions of
+the right-looking experiment (tools/ubench/trsm16_right_looking.h), which the library never sees.
 
 A region = the 24 v_mfma_f32_16x16x32_bf16 of one half block (four row tiles x six split products) with, INSIDE their issue gaps, everything the
 NEXT half block needs: the eight strip registers of its B operand read from the AGPRs and split into three bf16 pieces (52 VALU), its twelve
@@ -15,13 +16,14 @@ tuple -- unlike the AGPR strip nothing here is hidden from it.  Two operand sets
     set Q   A rows v[160:207]                                                     B pieces h v[208:211]  m v[212:215]  l v[216:219]
     sums    even blocks v[32:47], odd blocks v[48:63], running sum of the column v[64:79]     scratch v[224:239]
 
-    python tools/gen_trsm16_regions.py            (re)writes the .inc; the build fails if the checked-in file differs from the generator's output
+    python tools/gen_trsm16_regions.py            (re)writes both files; the build fails (--check) if a checked-in file differs from the generator's output
 """
 import os
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.join(HERE, "..", "awesomeslam_amd", "csrc", "ekf_large_trsm16_regions.inc")
+OUT_RIGHT = os.path.join(HERE, "ubench", "trsm16_right_looking_regions.inc")
 
 PLD, LB = 64, 64  # unpadded rows (LDS-DMA); the chunk swizzle and the half are part of the lane's base address
 PLANE = LB * PLD
@@ -33,7 +35,7 @@ PRODUCTS = [(0, "l"), (1, "m"), (2, "h"), (0, "m"), (1, "h"), (0, "h")]  # (plan
 BOFF = {"h": 0, "m": 4, "l": 8}
 
 
-def region(src, dst, acc, first, prev, half_next, strip=True, tiles=4, rows=4, diag="", dma=(), csplit=False):
+def region(src, dst, acc, first, prev, half_next, strip=True, tiles=4, rows=4, dma=(), csplit=False):
     """src/dst: operand sets; acc: 'E' / 'O'; first: the sums start here; prev: set whose sums are added to the running sum (or None);
     half_next: which half (0 / 1) of the staged block the next operand rows come from; strip: read + split the next B operand from the strip;
     csplit: the next B operand is split from registers 8 .. 15 of the running-sum tuple instead (the closing block: C tiles 2, 3);
@@ -89,10 +91,6 @@ def region(src, dst, acc, first, prev, half_next, strip=True, tiles=4, rows=4, d
         for t in range(4 - rows, 4):
             off = (16 * t * PLD + p * PLANE) * 2
             ds.append(f"ds_read_b128 v[{a_dst + 16 * p + 4 * t}:{a_dst + 16 * p + 4 * t + 3}], %[lds] offset:{off}")
-    if "novalu" in diag:
-        queue = []
-    if "nods" in diag:
-        ds = []
     n = len(mf)
     lines = []
     vq, dq = list(queue), list(ds)
@@ -169,6 +167,15 @@ def cstring(lines):
     return "\n".join(f'        "{ln}\\n\\t"' for ln in lines[:-1]) + f'\n        "{lines[-1]}"'
 
 
+def render(variants):
+    out = ["// GENERATED by tools/gen_trsm16_regions.py -- do not edit (the register map and the interleave are described there)"]
+    for name, lines in variants.items():
+        out.append(f"#define ASLAM_T16_{name} \\")
+        out += [f'        "{ln}\\n\\t" \\' for ln in lines[:-1]] + [f'        "{lines[-1]}"']
+        out.append("")
+    return "\n".join(out) + "\n"
+
+
 def main():
     variants = {
         # history blocks: first half (sums start), second half
@@ -181,36 +188,28 @@ def main():
         # second half (row tiles 2, 3 only: Linv is lower triangular; the first operand of the next block column is prepared behind it)
         "C0": region("P", "Q", "E", True, None, 1, strip=False, csplit=True, rows=2, dma=(0, 1, 2)),
         "C1": region("Q", "P", "E", False, None, 0, tiles=2, dma=(3, 4, 5)),
-        # timing diagnostics (tools/ubench/trsm_bench.hip): wrong results
-        "H1_E_NOVALU": region("Q", "P", "E", False, None, 0, diag="novalu", dma=(3, 4, 5)),
-        "H1_E_NODS": region("Q", "P", "E", False, None, 0, diag="nods", dma=(3, 4, 5)),
-        "H1_E_BARE": region("Q", "P", "E", False, None, 0, diag="novalu nods"),
-        "H1_E_NODMA": region("Q", "P", "E", False, None, 0),
-        # right-looking sweep (large_trsm_bf16r): history halves into the strip; the closing block's second half without a strip operand
+        "STRIP_WRITE_DYN": strip_write_dyn(),
+    }
+    # right-looking sweep (large_trsm_bf16r): history halves into the strip; the closing block's second half without a strip operand
+    right = {
         "R0": rregion("P", "Q", (0, 1, 2)),
         "R1": rregion("Q", "P", (3, 4, 5)),
         "C1R": region("Q", "P", "E", False, None, 0, strip=False, tiles=2, dma=(3, 4, 5)),
-        "STRIP_WRITE_DYN": strip_write_dyn(),
     }
-    out = ["// GENERATED by tools/gen_trsm16_regions.py -- do not edit (the register map and the interleave are described there)"]
-    for name, lines in variants.items():
-        out.append(f"#define ASLAM_T16_{name} \\")
-        body = [f'        "{ln}\\n\\t" \\' for ln in lines[:-1]] + [f'        "{lines[-1]}"']
-        out += body
-        out.append("")
-    text = "\n".join(out) + "\n"
+    files = ((OUT, variants), (OUT_RIGHT, right))
     if len(sys.argv) > 1 and sys.argv[1] == "--check":
-        cur = open(OUT).read() if os.path.exists(OUT) else ""
-        if cur != text:
-            print("ekf_large_trsm16_regions.inc is stale: run python tools/gen_trsm16_regions.py")
+        stale = [os.path.basename(path) for path, v in files if not os.path.exists(path) or open(path).read() != render(v)]
+        if stale:
+            print(f"{', '.join(stale)} stale: run python tools/gen_trsm16_regions.py")
             return 1
         print("gen_trsm16_regions: up to date")
         return 0
-    with open(OUT, "w") as f:
-        f.write(text)
-    for name, lines in variants.items():
-        print(f"{name}: {sum(l.startswith('v_mfma') for l in lines)} MFMA, {sum(l.startswith('v_') and not l.startswith('v_mfma') for l in lines)} VALU, "
-              f"{sum(l.startswith('ds_') for l in lines)} LDS reads")
+    for path, v in files:
+        with open(path, "w") as f:
+            f.write(render(v))
+        for name, lines in v.items():
+            print(f"{name}: {sum(l.startswith('v_mfma') for l in lines)} MFMA, {sum(l.startswith('v_') and not l.startswith('v_mfma') for l in lines)} VALU, "
+                  f"{sum(l.startswith('ds_') for l in lines)} LDS reads")
     return 0
 
 

@@ -21,6 +21,8 @@ namespace aslam
 // block (its rows wait in VGPRs until then).
 namespace t16
 {
+#include "trsm16_right_looking_regions.inc" // R0, R1, C1R (tools/gen_trsm16_regions.py)
+
 #define ASLAM_T16_QA_OUT "=&{v[160:175]}"(R.QA0), "=&{v[176:191]}"(R.QA1), "=&{v[192:207]}"(R.QA2)
 #define ASLAM_T16_PA_OUT "=&{v[96:111]}"(R.PA0), "=&{v[112:127]}"(R.PA1), "=&{v[128:143]}"(R.PA2)
 
@@ -79,7 +81,7 @@ struct SeqR
 
 /// history block (K, j): strip(:, K) -= X_j L(K, j)^T, the pieces of -X_j in the B registers of sets P (columns 0 .. 31 of block j) and Q (32 .. 63).
 /// On entry set P holds the first-half operand rows of this block, on exit those of the next block of the sequence.
-template <int K, int STAMP> __device__ __forceinline__ void rblock(Regs &R, Pipe &pp, SeqR &seq, int a_h0, int a_h1, bool after_closing)
+template <int K, bool STAMP> __device__ __forceinline__ void rblock(Regs &R, Pipe &pp, SeqR &seq, int a_h0, int a_h1, bool after_closing)
 {
         typedef __attribute__((address_space(3))) unsigned short lds_us;
         constexpr int R0 = 16 * (K & 15); // (block column 16 lives in the registers of block column 0)
@@ -95,7 +97,7 @@ template <int K, int STAMP> __device__ __forceinline__ void rblock(Regs &R, Pipe
         pp.template stamp<STAMP>(3);
 }
 
-template <int K, int STAMP> __device__ __forceinline__ void rchain(Regs &R, int j, int nb, Pipe &pp, SeqR &seq, int a_h0, int a_h1)
+template <int K, bool STAMP> __device__ __forceinline__ void rchain(Regs &R, int j, int nb, Pipe &pp, SeqR &seq, int a_h0, int a_h1)
 {
         if (K < nb)
         {
@@ -107,7 +109,7 @@ template <int K, int STAMP> __device__ __forceinline__ void rchain(Regs &R, int 
 }
 
 /// The right-looking sweep of one 16-row strip per wave: rows (row stride NP floats, this lane's row + 4 lg at `rowp`) -> X = rows L^-T, in place.
-template <int STAMP> __device__ __forceinline__ void sweep16r(Regs &R, Pipe &pp, unsigned short (*lds)[BLK], const Planes &pl, int b, int nb, int NP, float *rowp, int tid)
+template <bool STAMP> __device__ __forceinline__ void sweep16r(Regs &R, Pipe &pp, unsigned short (*lds)[BLK], const Planes &pl, int b, int nb, int NP, float *rowp, int tid)
 {
         typedef __attribute__((address_space(3))) unsigned short lds_us;
         const int lane = tid & 63, li = lane & 15, lg = lane >> 4;
@@ -240,7 +242,7 @@ template <int STAMP> __device__ __forceinline__ void sweep16r(Regs &R, Pipe &pp,
 } // namespace t16
 
 /// V = G L^-T on the bf16 pipe, right-looking (see above).  Same grid and workgroup -> (filter, row block) map as large_trsm_bf16.
-template <int NBMAX, int STAMP = 0>
+template <int NBMAX, bool STAMP = false>
 __global__ __launch_bounds__(256, 1) void large_trsm_bf16r(DevView d, LargeView<float> lv, t16::Planes pl, int nfilters, const int *skipped)
 {
         using namespace t16;

@@ -1,12 +1,12 @@
 // trsm_bench.hip -- stand-alone correctness + timing harness for the kernels of the large-state EKF's binary32 chain
-// (ekf_large_trsm.h, ekf_large_chol.h, large_syrk_bf16x3 in ekf_large.h), round 2.
+// (ekf_large_trsm.h, ekf_large_trsm16.h, ekf_large_chol.h, large_syrk_bf16x3 in ekf_large.h).
 // Random SPD S -> host Cholesky (double) -> L and the inverses of its 64x64 diagonal blocks in binary32; random G.  Checks:
-// large_trsm_pipe's V against a host triangular solve, large_chol_resident's L and Linv against the host factor.  Timings: the product
-// kernels at several batch sizes, and diagnostic variants of large_trsm_pipe with one part of the block pipeline removed, stamped inside
-// the kernel with s_memtime / s_memrealtime (cycles per MFMA and wave).  DIAG bits of large_trsm_pipe: 1 = no global fetch of the L
-// blocks (stale LDS), 2 = no LDS stash and no synchronisation, 16 = no synchronisation (racy), 32 = every fetch reads one block (L1 hits:
-// separates the issue cost of the fetch from its latency), 8 = stamps.  large_chol_resident<17, 1>: phase stamps.  large_syrk_bf16x3<1>:
-// the K loop without the read-modify-write of P.  The numbers quoted in DESIGN.md and profiles/r02_experiments.md come from this program.
+// large_trsm_pipe's and large_trsm_bf16's V against a host triangular solve, large_chol_resident's and large_chol_bf16's L and Linv against
+// the host factor, the bf16 planes bit for bit, and every filter of a batch of identical inputs bit for bit against filter 0 (a race
+// detector).  Timings: the product kernels at several batch sizes, and their own phase stamps (STAMP = true: s_memtime / s_memrealtime
+// inside the kernel).  RIGHT=1 runs the right-looking experiment (trsm16_right_looking.h) in place of large_trsm_bf16.
+// The ablation variants (one part of a pipeline removed) behind the numbers quoted in DESIGN.md and profiles/r02 .. r04_experiments.md are
+// no longer in the kernels (profiles/README.md).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I awesomeslam_amd/csrc tools/ubench/trsm_bench.hip -o /tmp/trsm_bench && /tmp/trsm_bench [filters]
 #include <hip/hip_runtime.h>
 
@@ -149,7 +149,7 @@ int main(int argc, char **argv)
         };
         // ---- correctness of the product kernel on the last filter
         reset_G();
-        hipLaunchKernelGGL((large_trsm_pipe<LARGE_NB_MAX, 0>), dim3(8 * ((B + 7) / 8) * NB), dim3(256), 0, 0, d, lv, B, dskip);
+        hipLaunchKernelGGL((large_trsm_pipe<LARGE_NB_MAX>), dim3(8 * ((B + 7) / 8) * NB), dim3(256), 0, 0, d, lv, B, dskip);
         CK(hipDeviceSynchronize());
         std::vector<float> V(M);
         CK(hipMemcpy(V.data(), dG + M * (B - 1), sizeof(float) * M, hipMemcpyDeviceToHost));
@@ -182,8 +182,8 @@ int main(int argc, char **argv)
                 const float msp = time_ms([&]() { hipLaunchKernelGGL(large_split_planes<0>, dim3(NB + 1, B), dim3(256), 0, 0, d, lv, pl, dskip); }, 3);
                 reset_G();
                 const bool rl = std::getenv("RIGHT") != nullptr; // RIGHT=1: the right-looking experiment (trsm16_right_looking.h) in this section instead of the library's kernel
-                auto k16 = rl ? large_trsm_bf16r<LARGE_NB_MAX, 0> : large_trsm_bf16<LARGE_NB_MAX, 0>;
-                auto k16s = rl ? large_trsm_bf16r<LARGE_NB_MAX, 1> : large_trsm_bf16<LARGE_NB_MAX, 1>;
+                auto k16 = rl ? large_trsm_bf16r<LARGE_NB_MAX, false> : large_trsm_bf16<LARGE_NB_MAX, false>;
+                auto k16s = rl ? large_trsm_bf16r<LARGE_NB_MAX, true> : large_trsm_bf16<LARGE_NB_MAX, true>;
                 std::printf("bf16 sweep: %s\n", rl ? "right-looking (large_trsm_bf16r)" : "left-looking (large_trsm_bf16)");
                 hipLaunchKernelGGL(k16, dim3(8 * ((B + 7) / 8) * NB), dim3(256), 0, 0, d, lv, pl, B, dskip);
                 CK(hipDeviceSynchronize());
@@ -234,26 +234,18 @@ int main(int argc, char **argv)
                                 std::printf("      closing block: wait for the slice %.0f, its LDS reads + issue of the next %.0f, C + split %.0f, first half %.0f, second half %.0f, stores %.0f, strip write %.0f, vmcnt wait %.0f, barrier %.0f\n", y[9] / 17, y[10] / 17, y[5] / 17, y[6] / 17, y[7] / 17, y[11] / 17, y[8] / 17, y[12] / 17, y[4] / 17);
                         };
                         stamps("product", k16s);
-                        if (!rl)
-                        {
-                        stamps("second half: no DMA pieces", large_trsm_bf16<LARGE_NB_MAX, 5>);
-                        stamps("second half: no VALU", large_trsm_bf16<LARGE_NB_MAX, 2>);
-                        stamps("second half: no LDS reads", large_trsm_bf16<LARGE_NB_MAX, 3>);
-                        stamps("second half: MFMAs only", large_trsm_bf16<LARGE_NB_MAX, 4>);
-                        }
                 }
         }
         if (only && std::string(only) == "trsm16")
                 return 0;
-        // ---- timings (the result does not matter: G is solved again in place).  DIAG bits: 1 = no global fetch of the L blocks (stale
-        // LDS), 2 = no LDS stash and no barrier, 16 = no barrier (racy), 8 = in-kernel stamps
+        // ---- timings (the result does not matter: G is solved again in place)
         const double mfma_per_wave = 64.0 * 136 + 40.0 * 17;
         const double fl = mfma_per_wave * 2048.0 * 68 * B; // x 2048 flop x 68 waves per filter
         for (int bb : {15, 30, 60, 120, B})
         {
                 if (bb > B)
                         break;
-                const float m0 = time_ms([&]() { hipLaunchKernelGGL((large_trsm_pipe<LARGE_NB_MAX, 0>), dim3(8 * ((bb + 7) / 8) * NB), dim3(256), 0, 0, d, lv, bb, dskip); }, 5);
+                const float m0 = time_ms([&]() { hipLaunchKernelGGL((large_trsm_pipe<LARGE_NB_MAX>), dim3(8 * ((bb + 7) / 8) * NB), dim3(256), 0, 0, d, lv, bb, dskip); }, 5);
                 std::printf("  %3d filters = %4d workgroups (%.2f per CU): %7.3f ms = %6.1f TFLOP/s executed (%4.1f %% of 157.3)\n", bb, 17 * bb, 17.0 * bb / 256, m0,
                             fl * bb / B / (m0 * 1e-3) / 1e12, fl * bb / B / (m0 * 1e-3) / 1e12 / 157.3 * 100);
         }
@@ -278,18 +270,8 @@ int main(int argc, char **argv)
                                     cyc / (real / 100.0), cyc / mfma_per_wave);
                 };
                 CK(hipMemset(dY, 0, sizeof(double) * 2 * NB * (B + 8)));
-                hipLaunchKernelGGL((large_trsm_pipe<LARGE_NB_MAX, 8>), dim3(8 * ((bb + 7) / 8) * NB), dim3(256), 0, 0, d, lw, bb, dskip);
+                hipLaunchKernelGGL((large_trsm_pipe<LARGE_NB_MAX, true>), dim3(8 * ((bb + 7) / 8) * NB), dim3(256), 0, 0, d, lw, bb, dskip);
                 report("product");
-                hipLaunchKernelGGL((large_trsm_pipe<LARGE_NB_MAX, 9>), dim3(8 * ((bb + 7) / 8) * NB), dim3(256), 0, 0, d, lw, bb, dskip);
-                report("no fetch");
-                hipLaunchKernelGGL((large_trsm_pipe<LARGE_NB_MAX, 9 + 16>), dim3(8 * ((bb + 7) / 8) * NB), dim3(256), 0, 0, d, lw, bb, dskip);
-                report("no fetch, no barrier");
-                hipLaunchKernelGGL((large_trsm_pipe<LARGE_NB_MAX, 11>), dim3(8 * ((bb + 7) / 8) * NB), dim3(256), 0, 0, d, lw, bb, dskip);
-                report("no fetch/stash/barrier");
-                hipLaunchKernelGGL((large_trsm_pipe<LARGE_NB_MAX, 8 + 16>), dim3(8 * ((bb + 7) / 8) * NB), dim3(256), 0, 0, d, lw, bb, dskip);
-                report("no barrier");
-                hipLaunchKernelGGL((large_trsm_pipe<LARGE_NB_MAX, 8 + 32>), dim3(8 * ((bb + 7) / 8) * NB), dim3(256), 0, 0, d, lw, bb, dskip);
-                report("every fetch from one block (L1)");
                 CK(hipFree(dY));
         }
         // ---- large_chol_resident: S (binary32 copy of the SPD matrix) -> L, Linv against the host factor; then its time
@@ -496,13 +478,10 @@ int main(int argc, char **argv)
                 const dim3 grid(8 * (ntile * (ntile + 1) / 2) * ((B + 7) / 8));
                 const double sf = (ntile * (ntile + 1) / 2 - ntile * 0.25) * 2.0 * 128 * 128 * 1056 * B;
                 // (round 2 also timed large_syrk_f32p64 here, the fp32-MFMA form: 3.06 ms per 256 filters, K loop 2.7 ms; removed in round 3)
-                const float mb = time_ms([&]() { hipLaunchKernelGGL((large_syrk_bf16x3<0>), grid, dim3(256), 0, 0, d, lv, LPlanes{nullptr}, B, dskip); }, 5);
+                const float mb = time_ms([&]() { hipLaunchKernelGGL((large_syrk_bf16x3<false>), grid, dim3(256), 0, 0, d, lv, B, dskip); }, 5);
                 std::printf("  syrk_bf16x3      %8.3f ms for %d filters = %6.1f T fp32-equivalent FLOP/s executed\n", mb, B, sf / (mb * 1e-3) / 1e12);
-                const float mbk = time_ms([&]() { hipLaunchKernelGGL((large_syrk_bf16x3<1>), grid, dim3(256), 0, 0, d, lv, LPlanes{nullptr}, B, dskip); }, 5);
-                std::printf("  syrk_bf16x3 without the read-modify-write of P      %8.3f ms\n", mbk);
-                const float mb2 = time_ms([&]() { hipLaunchKernelGGL((large_syrk_bf16x3<2>), grid, dim3(256), 0, 0, d, lv, LPlanes{nullptr}, B, dskip); }, 5);
-                const float mbk2 = time_ms([&]() { hipLaunchKernelGGL((large_syrk_bf16x3<3>), grid, dim3(256), 0, 0, d, lv, LPlanes{nullptr}, B, dskip); }, 5);
-                std::printf("  syrk_bf16x3 with round 2's running accumulator (no per-slab temporaries)  %8.3f ms, without the read-modify-write %8.3f ms\n", mb2, mbk2);
+                const float mb2 = time_ms([&]() { hipLaunchKernelGGL((large_syrk_bf16x3<true>), grid, dim3(256), 0, 0, d, lv, B, dskip); }, 5);
+                std::printf("  syrk_bf16x3 with round 2's running accumulator (no per-slab temporaries)  %8.3f ms\n", mb2);
         }
         return 0;
 }
