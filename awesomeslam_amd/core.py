@@ -27,11 +27,13 @@ CORE_SYMBOLS = (
     "aslam_get_state", "aslam_get_A", "aslam_get_landmarks", "aslam_get_wait", "aslam_get_status",
     "aslam_get_layout", "aslam_kernel_info", "aslam_get_launch_info",
     "aslam_replay_stats", "aslam_innovation_enable", "aslam_get_innovation",
+    "aslam_params_default", "aslam_set_params", "aslam_get_params",
 )
 NODE_SYMBOLS = (
     "aslam_node_create", "aslam_node_create_at", "aslam_node_destroy", "aslam_node_error", "aslam_node_sensor", "aslam_node_odom",
     "aslam_node_odom_now", "aslam_node_dim", "aslam_node_get", "aslam_node_wait", "aslam_node_core",
     "aslam_host_narrow_odom", "aslam_node_enable_innovation", "aslam_node_innovation",
+    "aslam_node_set_params", "aslam_node_get_params",
 )
 TRACE_FILE_SYMBOLS = (
     "aslam_trace_file_open", "aslam_trace_file_close", "aslam_trace_file_error", "aslam_trace_file_dims",
@@ -53,6 +55,36 @@ class TraceView(ctypes.Structure):
                 ("pose", ctypes.c_void_p), ("yaw", ctypes.c_void_p), ("twist", ctypes.c_void_p),
                 ("dt", ctypes.c_void_p), ("obs_new", ctypes.c_void_p), ("n_obs", ctypes.c_void_p),
                 ("obs", ctypes.c_void_p)]
+
+
+class Params(ctypes.Structure):
+    """aslam_params (include/aslam_core.h): the noise and association parameters of one filter.  80 bytes."""
+    _fields_ = [(k, ctypes.c_double) for k in
+                ("r_xy", "r_yaw", "r_range", "r_bearing", "q_xy", "q_yaw", "p0_pose", "p0_landmark", "var_a")] + \
+               [("assoc_dist", ctypes.c_float), ("promote_count", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+    @classmethod
+    def make(cls, params=None):
+        """A Params from a Params (copied), a dict of overrides of the defaults, or None (the defaults)."""
+        if isinstance(params, cls):
+            return cls.from_buffer_copy(params)
+        p = default_params()
+        names = {k for k, _ in cls._fields_}
+        for k, v in (params or {}).items():
+            if k not in names:
+                raise KeyError(f"aslam_params has no field {k!r}")
+            setattr(p, k, v)
+        return p
+
+
+def default_params():
+    """The reference's constants (include/awesome_slam/config.h) as the library holds them: aslam_params_default."""
+    p = Params()
+    _chk(core_lib().aslam_params_default(ctypes.byref(p)))
+    return p
 
 
 _BUILT_HERE = False  # set by build() when THIS process's make run (re)compiled libaslam_core.so
@@ -137,6 +169,9 @@ def core_lib():
         L.aslam_replay_stats.argtypes = [vp, ctypes.c_int64, ctypes.c_int64, vp, vp, vp, vp, vp, vp]
         L.aslam_innovation_enable.argtypes = [vp, ci]
         L.aslam_get_innovation.argtypes = [vp, ci, pd, pd]
+        L.aslam_params_default.argtypes = [ctypes.POINTER(Params)]
+        L.aslam_set_params.argtypes = [vp, ci, ctypes.POINTER(Params)]
+        L.aslam_get_params.argtypes = [vp, ci, ctypes.POINTER(Params)]
         L.aslam_get_dim.argtypes = [vp, ci, pi]
         L.aslam_get_state.argtypes = [vp, ci, pd, pd, pd]
         L.aslam_get_A.argtypes = [vp, ci, pd, pd]
@@ -183,6 +218,8 @@ def node_lib():
         L.aslam_host_narrow_odom.argtypes = [ctypes.c_int64, pd, pd, pf, pd]
         L.aslam_node_enable_innovation.argtypes = [vp, ci]
         L.aslam_node_innovation.argtypes = [vp, pd, pd]
+        L.aslam_node_set_params.argtypes = [vp, ctypes.POINTER(Params)]
+        L.aslam_node_get_params.argtypes = [vp, ctypes.POINTER(Params)]
         # include/aslam_trace_file.h
         L.aslam_trace_file_error.restype = ctypes.c_char_p
         L.aslam_trace_file_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
@@ -343,6 +380,20 @@ class Core:
 
     def reset(self):
         _chk(core_lib().aslam_reset(self._h))
+
+    # ---- noise and association parameters (aslam_set_params / aslam_get_params)
+    def set_params(self, params, traj=None):
+        """Set the parameters of filter `traj` (None: every filter).  `params`: a Params, or a dict of overrides of the DEFAULTS (not of the
+        filter's current record).  Synchronises.  R, Q, var_a and assoc_dist apply from the next callback, p0_landmark to later growths, p0_pose
+        at the next reset(); promote_count is meant to be set before the first callback.  AslamError names a refused field."""
+        p = Params.make(params)
+        _chk(core_lib().aslam_set_params(self._h, -1 if traj is None else int(traj), ctypes.byref(p)))
+
+    def params(self, traj=0):
+        """The record of filter `traj` as the kernels read it (synchronises)."""
+        p = Params()
+        _chk(core_lib().aslam_get_params(self._h, int(traj), ctypes.byref(p)))
+        return p
 
     # ---- per-callback seam
     def set_state(self, traj, n, X=None, Z=None, P=None):
@@ -607,6 +658,17 @@ class Node:
         if node_lib().aslam_node_innovation(self._h, ctypes.byref(a), ctypes.byref(b)) != 0:
             raise AslamError(node_lib().aslam_node_error().decode())
         return a.value, b.value
+
+    def set_params(self, params):
+        """FilterNode::setParams: a Params or a dict of overrides of the defaults.  Before the first callback (p0_pose applies then)."""
+        p = Params.make(params)
+        if node_lib().aslam_node_set_params(self._h, ctypes.byref(p)) != 0:
+            raise AslamError(node_lib().aslam_node_error().decode())
+
+    def params(self):
+        p = Params()
+        node_lib().aslam_node_get_params(self._h, ctypes.byref(p))
+        return p
 
     def wait_list(self, cap=4096):
         r, b, c = np.empty(cap, np.float32), np.empty(cap, np.float32), np.empty(cap, np.uint32)

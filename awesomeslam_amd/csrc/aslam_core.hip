@@ -32,6 +32,8 @@
 
 using namespace aslam;
 
+static_assert(sizeof(aslam_params) == 80, "aslam_params is part of the C ABI");
+
 namespace
 {
 thread_local std::string g_err;
@@ -76,6 +78,9 @@ struct aslam_ctx
         // aslam_innovation_enable: [batch][2] (nis, logdet) of every filter's last callback, allocated by the first enable; off by default
         double *innov = nullptr;
         bool innov_on = false;
+        // aslam_set_params: the host copy of dv.prm ([batch] records in HBM); aslam_grow and init_state read p0_landmark / p0_pose from it
+        std::vector<aslam_params> params;
+        aslam_params *params_dev = nullptr;
         // aslam_snapshot / aslam_restore: descriptors, gathered headers and the staged copy of a host blob (grown on demand, not state)
         char *snap_dev = nullptr;
         size_t snap_cap = 0;
@@ -116,14 +121,14 @@ int download_P(aslam_ctx *c, int traj, int n, double *P)
         return ASLAM_OK;
 }
 
-/// new rows of P on growth: zero, with KP_LANDMARK_POSE on the diagonal (rows n_old .. n_new-1, full padded length)
+/// new rows of P on growth: zero, with the filter's p0_landmark (UKF_KP_LANDMARK_POSE) on the diagonal (rows n_old .. n_new-1, full padded length)
 int grow_P_rows(aslam_ctx *c, int traj, int n_old, int n_new)
 {
         const size_t NP = (size_t)c->NP;
         for (int i = n_old; i < n_new; ++i)
         {
                 std::vector<double> row(NP, 0.0);
-                row[i] = (double)KP_LANDMARK_POSE;
+                row[i] = c->params[traj].p0_landmark;
                 double *dst = (c->large ? c->largeP : c->dv.P) + traj * NP * NP + (size_t)i * NP;
                 HIP_TRY(hipMemcpy(dst, row.data(), sizeof(double) * NP, hipMemcpyHostToDevice));
         }
@@ -151,15 +156,34 @@ template <typename F> int with_large_view(aslam_ctx *c, F &&f)
         return c->cfg.dtype == ASLAM_F32 ? f(c->lv32) : f(c->lv64);
 }
 
-/// P = Identity * KP_ROBOT_POSE on the 3 pose entries of every filter (P zeroed by the caller)
-int seed_pose_block(double *P, size_t B, size_t NP)
+/// P = Identity * p0_pose (*_KP_ROBOT_POSE) on the 3 pose entries of every filter, each from its own record (P zeroed by the caller)
+int seed_pose_block(const aslam_ctx *c, double *P, size_t B, size_t NP)
 {
         std::vector<double> blk(3 * NP, 0.0);
-        for (int i = 0; i < 3; ++i)
-                blk[(size_t)i * NP + i] = (double)KP_ROBOT_POSE;
         for (size_t b = 0; b < B; ++b)
+        {
+                for (int i = 0; i < 3; ++i)
+                        blk[(size_t)i * NP + i] = c->params[b].p0_pose;
                 HIP_TRY(hipMemcpy(P + b * NP * NP, blk.data(), sizeof(double) * blk.size(), hipMemcpyHostToDevice));
+        }
         return ASLAM_OK;
+}
+
+/// the first field of a record that aslam_set_params refuses, or nullptr
+const char *bad_param(const aslam_params &p)
+{
+        const struct
+        {
+                const char *name;
+                double v;
+                bool zero_ok;
+        } f[] = {{"r_xy", p.r_xy, false},       {"r_yaw", p.r_yaw, false},     {"r_range", p.r_range, false},         {"r_bearing", p.r_bearing, false},
+                 {"q_xy", p.q_xy, true},        {"q_yaw", p.q_yaw, true},      {"p0_pose", p.p0_pose, false},         {"p0_landmark", p.p0_landmark, false},
+                 {"var_a", p.var_a, false},     {"assoc_dist", (double)p.assoc_dist, false}};
+        for (const auto &e : f)
+                if (!std::isfinite(e.v) || e.v < 0.0 || (e.v == 0.0 && !e.zero_ok))
+                        return e.name;
+        return p.promote_count < 1 ? "promote_count" : nullptr;
 }
 
 template <typename T> int init_P_large(aslam_ctx *c, LargeView<T> &lv)
@@ -170,7 +194,7 @@ template <typename T> int init_P_large(aslam_ctx *c, LargeView<T> &lv)
         HIP_TRY(hipMemset(lv.S, 0, sizeof(T) * B * NP * NP));
         if (lv.Vw)
                 HIP_TRY(hipMemset(lv.Vw, 0, sizeof(T) * B * NP * NP));
-        return seed_pose_block(lv.P, B, NP);
+        return seed_pose_block(c, lv.P, B, NP);
 }
 
 /// initialize() for the whole batch: ekf.cpp:49-71 / ukf.cpp:49-67
@@ -204,7 +228,7 @@ int init_state(aslam_ctx *c)
                 HIP_TRY(hipMemset(c->ukf.K, 0, sizeof(double) * (size_t)B * NP * NP));
         }
 #endif
-        return seed_pose_block(d.P, B, NP);
+        return seed_pose_block(c, d.P, B, NP);
 }
 
 template <int NT, int MODE, bool STATS>
@@ -452,6 +476,11 @@ int aslam_create(const aslam_config *cfg, aslam_ctx **out)
         A_(dev_alloc(c, &d.wait_rb, B * cfg->max_wait * 2, c->owned));
         A_(dev_alloc(c, &d.wait_cnt, B * cfg->max_wait, c->owned));
         A_(dev_alloc(c, &d.wait_n, B, c->owned));
+        A_(dev_alloc(c, &c->params_dev, B, c->owned));
+        d.prm = c->params_dev;
+        c->params.assign(B, aslam_params ASLAM_PARAMS_DEFAULT_INIT);
+        if (rc == ASLAM_OK && hipMemcpy(c->params_dev, c->params.data(), sizeof(aslam_params) * B, hipMemcpyHostToDevice) != hipSuccess)
+                rc = fail(ASLAM_ERR_HIP, "hipMemcpy of the default parameters failed");
 #ifdef ASLAM_STAMPS
         A_(dev_alloc(c, &d.dbg, 64 + 1024, c->owned)); // [64 ..): diagnostic builds, last front-end launch, 100 MHz ticks per workgroup
 #endif
@@ -505,7 +534,51 @@ int aslam_reset(aslam_ctx *c)
         if (rc != ASLAM_OK)
                 return rc;
         rc = init_state(c);
-        return rc != ASLAM_OK ? rc : clear_innovation(c); // (the setting of aslam_innovation_enable stays)
+        return rc != ASLAM_OK ? rc : clear_innovation(c); // (the setting of aslam_innovation_enable and the parameters stay)
+}
+
+int aslam_params_default(aslam_params *out)
+{
+        if (!out)
+                return fail(ASLAM_ERR_ARG, "null argument");
+        *out = aslam_params ASLAM_PARAMS_DEFAULT_INIT;
+        return ASLAM_OK;
+}
+
+int aslam_set_params(aslam_ctx *c, int traj, const aslam_params *p)
+{
+        if (!p)
+                return fail(ASLAM_ERR_ARG, "null argument");
+        // (the record is judged before the context is looked at: a refused field is reported whatever else is wrong with the call)
+        if (const char *bad = bad_param(*p))
+                return fail(ASLAM_ERR_ARG, std::string("aslam_params.") + bad +
+                                                   (std::string(bad) == "promote_count" ? " must be at least 1"
+                                                                                        : (bad[0] == 'q' ? " must be finite and >= 0" : " must be finite and > 0")));
+        if (!c)
+                return fail(ASLAM_ERR_ARG, "null context");
+        if (traj < -1 || traj >= c->cfg.batch)
+                return fail(ASLAM_ERR_ARG, "trajectory index out of range (-1 = every filter)");
+        int rc = sync_ctx(c);
+        if (rc != ASLAM_OK)
+                return rc;
+        const size_t first = traj < 0 ? 0 : (size_t)traj, count = traj < 0 ? (size_t)c->cfg.batch : 1;
+        const std::vector<aslam_params> recs(count, *p);
+        HIP_TRY(hipMemcpy(c->params_dev + first, recs.data(), sizeof(aslam_params) * count, hipMemcpyHostToDevice));
+        std::copy(recs.begin(), recs.end(), c->params.begin() + first); // (behind the copy: the host copy never disagrees with what the kernels read)
+        return ASLAM_OK;
+}
+
+int aslam_get_params(aslam_ctx *c, int traj, aslam_params *p)
+{
+        int rc = check_traj(c, traj);
+        if (rc != ASLAM_OK)
+                return rc;
+        if (!p)
+                return fail(ASLAM_ERR_ARG, "null argument");
+        if ((rc = sync_ctx(c)) != ASLAM_OK)
+                return rc;
+        HIP_TRY(hipMemcpy(p, c->params_dev + traj, sizeof(aslam_params), hipMemcpyDeviceToHost)); // (what the kernels read)
+        return ASLAM_OK;
 }
 
 int aslam_set_state(aslam_ctx *c, int traj, int n, const double *X, const double *Z, const double *P)

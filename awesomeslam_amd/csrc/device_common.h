@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/aslam_core.h"
+
 namespace aslam
 {
 typedef double d4 __attribute__((ext_vector_type(4)));
@@ -15,14 +17,15 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 // ---- include/awesome_slam/config.h:39-65 -------------------------------------------------------------
 constexpr float PI_F = 3.141592654f;         // const float PI = 3.141592654
 constexpr float TWO_PI_F = 2.0f * PI_F;      // `2 * PI` (int * float)
-constexpr float MIN_DIST_THRESH = 0.5f;      // config.h:43
-constexpr unsigned MIN_LANDMARK_OCC = 10;    // config.h:44
-constexpr float UKF_STD_A = 0.2f;            // config.h:54
-constexpr float UKF_STD_YAW = 0.2f;          // config.h:55
-constexpr float KP_ROBOT_POSE = 0.001f;      // EKF_KP_ROBOT_POSE == UKF_KP_ROBOT_POSE (config.h:56,63)
-constexpr float KP_LANDMARK_POSE = 1.0f;     // UKF_KP_LANDMARK_POSE, used by BOTH nodes on growth (ekf.cpp:277)
-constexpr float KR = 0.2f;                   // EKF_KR == UKF_KR (config.h:58,65)
-constexpr float KQ = 0.001f;                 // EKF_KQ == UKF_KQ (config.h:59,66)
+// MIN_DIST_THRESH, MIN_LANDMARK_OCC, UKF_STD_A, *_KP_ROBOT_POSE, UKF_KP_LANDMARK_POSE, *_KR and *_KQ (config.h:43-66) are run-time parameters:
+// one aslam_params record per filter in HBM (DevView::prm, defaults from ASLAM_PARAMS_DEFAULT_INIT in aslam_core.h).  UKF_STD_YAW (config.h:55)
+// has no effect on any result (stateTransitionFunction never reads point(N+1)) and exists nowhere here.
+
+/// diagonal entry i of R (ekf.cpp:65,278) from a record's four r_* values (consecutive doubles): rows 0-1, row 2, range rows (odd), bearing rows (even)
+__device__ __forceinline__ double meas_r(const double *r4, int i)
+{
+        return r4[i < 2 ? 0 : i == 2 ? 1 : 3 - (i & 1)];
+}
 
 // flags of one filter
 constexpr int FLAG_INIT_X = 1; // init_x (ekf.h:93)

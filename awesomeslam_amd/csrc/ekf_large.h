@@ -276,7 +276,7 @@ __global__ __launch_bounds__(SMALL_WG) void large_frontend_kernel(DevView d, Lar
         ASLAM_STAMP(2);
         // P <- A P A^T + Q (ekf.cpp:297), A = I except A(0,0), A(1,0): rows 0,1 then columns 0,1
         {
-                const double a00 = sm.a00, a10 = sm.a10, q = (double)KQ;
+                const double a00 = sm.a00, a10 = sm.a10, q = sm.prm.q_xy, q_yaw = sm.prm.q_yaw; // Q = diag(q_xy, q_xy, q_yaw, 0 ...), ekf.cpp:66-68
                 for (int c = tid; c < n; c += SMALL_WG)
                 {
                         const double r0 = Pg[c];
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(SMALL_WG) void large_frontend_kernel(DevView d, Lar
                         row[0] = v0;
                         row[1] = v1;
                         if (r == 2)
-                                row[2] += q;
+                                row[2] += q_yaw;
                 }
         }
         ASLAM_STAMP(3);
@@ -336,7 +336,8 @@ template <typename T> __global__ __launch_bounds__(256) void large_build_GS(DevV
         T *G = lv.G + (size_t)b * NP * NP;
         T *S = lv.S + (size_t)b * NP * NP;
         const double *Hc = lv.Hc + (size_t)b * (NP / 2) * 4;
-        const double rm = (double)KR;
+        const aslam_params *const prm = d.prm + b; // (wave-uniform: one filter per workgroup)
+        const double r_xy = prm->r_xy, r_yaw = prm->r_yaw, r_range = prm->r_range, r_bearing = prm->r_bearing; // diagonal of R by row class (ekf.cpp:65,278)
         const int tid = threadIdx.x;
         const bool pose = (blockIdx.x == 0);
         constexpr int RP = GS_ROW_PAIRS; // landmark row pairs per workgroup: the pose rows of G and the H coefficients of a column pair are formed once for all of them
@@ -410,9 +411,9 @@ template <typename T> __global__ __launch_bounds__(256) void large_build_GS(DevV
                 if (pose)
                 {
                         G[c] = (T)g0, G[NP + c] = (T)g1, G[2 * (size_t)NP + c] = (T)g2;
-                        S[c] = (T)(g0 + (c == 0 ? rm : 0.0));
-                        S[NP + c] = (T)(g1 + (c == 1 ? rm : 0.0));
-                        S[2 * (size_t)NP + c] = (T)(g2 + (c == 2 ? rm : 0.0));
+                        S[c] = (T)(g0 + (c == 0 ? r_xy : 0.0));
+                        S[NP + c] = (T)(g1 + (c == 1 ? r_xy : 0.0));
+                        S[2 * (size_t)NP + c] = (T)(g2 + (c == 2 ? r_yaw : 0.0));
                 }
                 else
                 {
@@ -472,9 +473,9 @@ template <typename T> __global__ __launch_bounds__(256) void large_build_GS(DevV
                                                 double ue = srow(hb0[rp], hb1[rp], true, g0e, g1e, g2e, gae, gbe),
                                                        uo = srow(hb0[rp], hb1[rp], true, g0o, g1o, g2o, gao, gbo);
                                                 if (ce == ra)
-                                                        se += rm; // R on the diagonal
+                                                        se += r_range; // R on the diagonal: the range row of the pair ...
                                                 if (co == ra + 1)
-                                                        uo += rm;
+                                                        uo += r_bearing; // ... and its bearing row
                                                 sa[ce] = (T)se, sa[co] = (T)so;
                                                 sb[ce] = (T)ue, sb[co] = (T)uo;
                                         }
@@ -545,7 +546,8 @@ template <typename T> __global__ __launch_bounds__(256) void large_build_GS_tile
         T *S = lv.S + (size_t)b * NP * NP;
         const double *Hc = lv.Hc + (size_t)b * (NP / 2) * 4;
         const double *Y = lv.Y + (size_t)b * NP;
-        const double rm = (double)KR;
+        const aslam_params *const prm = d.prm + b; // (wave-uniform: one filter per workgroup)
+        const double r_xy = prm->r_xy, r_yaw = prm->r_yaw, r_range = prm->r_range, r_bearing = prm->r_bearing; // diagonal of R by row class (ekf.cpp:65,278)
         const int tid = threadIdx.x;
         const int r0 = LB * I - 1, c0 = LB * J - 1; // global index of halo row / column 0
         typedef double d2 __attribute__((ext_vector_type(2)));
@@ -647,7 +649,7 @@ template <typename T> __global__ __launch_bounds__(256) void large_build_GS_tile
                 else if (gc >= n)
                         sv = 0.0;
                 else if (gr < 3)
-                        sv = g + (gr == gc ? rm : 0.0);
+                        sv = g + (gr == gc ? (gr < 2 ? r_xy : r_yaw) : 0.0);
                 else
                 {
                         const bool even = !(gr & 1);                    // the bearing row of its landmark
@@ -659,7 +661,7 @@ template <typename T> __global__ __launch_bounds__(256) void large_build_GS_tile
                                 v -= g32;
                         sv = v - ha * go_ - hb * ge_;
                         if (gr == gc)
-                                sv += rm;
+                                sv += even ? r_bearing : r_range;
                 }
                 S[(size_t)gr * NP + gc] = (T)sv;
         }

@@ -122,6 +122,7 @@ inline DevView shifted(DevView d, size_t b, bool trace)
         d.wait_rb += b * (size_t)d.max_wait * 2;
         d.wait_cnt += b * (size_t)d.max_wait;
         d.wait_n += b;
+        d.prm += b;
         d.step_in += b; // [3][B]: the stride stays the whole batch
         if (trace)
         {

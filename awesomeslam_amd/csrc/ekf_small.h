@@ -147,7 +147,6 @@ __global__ __launch_bounds__(SMALL_WG) void ekf_small_kernel(DevView d, int64_t 
         const int tid_launch = threadIdx.x, tid = tid_launch;
         const int b = (MODE == MODE_STEP && sa.traj >= 0) ? sa.traj : (int)blockIdx.x; // sa.traj < 0: the batched step, one workgroup per filter
         double *Pg = d.P + (size_t)b * NP * NP;
-        const double r_meas = (double)KR, q_proc = (double)KQ;
 #ifdef ASLAM_STAMPS
         unsigned long long stamp_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         unsigned long long stamp_last = __builtin_amdgcn_s_memtime();
@@ -276,10 +275,11 @@ __global__ __launch_bounds__(SMALL_WG) void ekf_small_kernel(DevView d, int64_t 
                         {
                                 const double p00 = Lt[0], p10 = Lt[TLD], p11 = Lt[TLD + 1];
                                 const double r10 = a10 * p00 + p10; // (A P)(1,0)
-                                Lt[0] = a00 * (a00 * p00) + q_proc;
+                                const double q_xy = sm.prm.q_xy; // Q = diag(q_xy, q_xy, q_yaw, 0 ...), ekf.cpp:66-68
+                                Lt[0] = a00 * (a00 * p00) + q_xy;
                                 Lt[TLD] = a00 * r10;
-                                Lt[TLD + 1] = a10 * r10 + (a10 * p10 + p11) + q_proc;
-                                Lt[2 * TLD + 2] += q_proc;
+                                Lt[TLD + 1] = a10 * r10 + (a10 * p10 + p11) + q_xy;
+                                Lt[2 * TLD + 2] += sm.prm.q_yaw;
                         }
                         __syncthreads();
                 }
@@ -289,12 +289,12 @@ __global__ __launch_bounds__(SMALL_WG) void ekf_small_kernel(DevView d, int64_t 
                 ASLAM_STAMP(2);
                 ASLAM_STAMP(3);
                 ASLAM_STAMP(4);
-                // S = Pt + R = L L^T (ekf.cpp:300); r*Kt = r I - r^2 S^-1 -> the tiles (= (I - K H) P in measurement coordinates,
-                // ekf.cpp:301,310); u = Kt Y = Y - r S^-1 Y
+                // S = Pt + R = L L^T (ekf.cpp:300); Kt R = R - R S^-1 R -> the tiles (= (I - K H) P in measurement coordinates,
+                // ekf.cpp:301,310); u = Kt Y = Y - R S^-1 Y; R = diag of the filter's r_xy, r_yaw, r_range, r_bearing by row class
 #ifdef ASLAM_STAMPS
-                cholesky_inverse_tiles<NT>(Lt, Dinv, nt, n, sY, sU, L.sTv, r_meas, tid, &sm.status, (blockIdx.x == 0 && d.dbg) ? d.dbg + 16 : nullptr);
+                cholesky_inverse_tiles<NT>(Lt, Dinv, nt, n, sY, sU, L.sTv, &sm.prm.r_xy, tid, &sm.status, (blockIdx.x == 0 && d.dbg) ? d.dbg + 16 : nullptr);
 #else
-                cholesky_inverse_tiles<NT>(Lt, Dinv, nt, n, sY, sU, L.sTv, r_meas, tid, &sm.status);
+                cholesky_inverse_tiles<NT>(Lt, Dinv, nt, n, sY, sU, L.sTv, &sm.prm.r_xy, tid, &sm.status);
 #endif
                 ASLAM_STAMP(5);
                 __syncthreads();
@@ -342,7 +342,7 @@ __global__ __launch_bounds__(SMALL_WG) void ekf_small_kernel(DevView d, int64_t 
                                 sX[tid] += sU[tid];
                 }
                 ASLAM_STAMP(7);
-                // P = (I - K H) P = H^-1 (r Kt) H^-T (ekf.cpp:310), in place on the tiles
+                // P = (I - K H) P = H^-1 (Kt R) H^-T (ekf.cpp:310), in place on the tiles
                 congruence_tiles<false>(Lt, Dinv, sH, NLM, n, nl, tid);
                 ASLAM_STAMP(8);
                 ASLAM_STAMP(9);

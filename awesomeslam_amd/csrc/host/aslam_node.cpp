@@ -6,16 +6,15 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <stdexcept>
 
 namespace aslam
 {
 namespace
 {
-// include/awesome_slam/config.h:39-65
+// include/awesome_slam/config.h:39 (MIN_DIST_THRESH and MIN_LANDMARK_OCC, config.h:43-44, are FilterNode::params(): assoc_dist, promote_count)
 const float PI = 3.141592654;
-const float MIN_DIST_THRESH = 0.5;
-const uint32_t MIN_LANDMARK_OCC = 10;
 
 struct WorldPoint
 {
@@ -65,7 +64,7 @@ float quat2euler(float w, float x, float y, float z)
 FilterNode::FilterNode(int filter_, int max_landmark_count, int device, double now_init)
     : filter(filter_), MAX_LANDMARK_COUNT(max_landmark_count), ctx(nullptr), N(3), init_z(true), init_x(true),
       last_time((float)now_init), // ekf.cpp:54: last_time = ros::Time::now().toSec(), a float member (ekf.h:98)
-      growth_refused(false), slam_ran(false), param_X(3, 0.0), param_Z(3, 0.0), a00(1.0), a10(0.0)
+      growth_refused(false), slam_ran(false), prm ASLAM_PARAMS_DEFAULT_INIT, param_X(3, 0.0), param_Z(3, 0.0), a00(1.0), a10(0.0)
 {
         aslam_config cfg = {};
         cfg.filter = filter;
@@ -145,6 +144,31 @@ void FilterNode::innovation(double &nis, double &logdet) const
                 nis = logdet = std::nan(""); // the core still holds the callback before
 }
 
+// The parameter entry points are bound weakly for the same reason (and aslam_reset, which only setParams calls): with a core that lacks them
+// the mirror runs on the reference's constants, and anything else is refused.
+extern "C" {
+int aslam_set_params(aslam_ctx *, int, const aslam_params *) __attribute__((weak));
+int aslam_reset(aslam_ctx *) __attribute__((weak));
+}
+
+void FilterNode::setParams(const aslam_params &p)
+{
+        if (aslam_set_params && aslam_reset)
+        {
+                check(aslam_set_params(ctx, 0, &p), "aslam_set_params");
+                // p0_pose applies at initialize(): a node that has not run a callback yet is initialised again, a running one keeps its P
+                if (init_x)
+                        check(aslam_reset(ctx), "aslam_reset");
+        }
+        else
+        {
+                const aslam_params def = ASLAM_PARAMS_DEFAULT_INIT;
+                if (std::memcmp(&p, &def, sizeof(def)) != 0)
+                        throw std::runtime_error("this core has no run-time parameters: only the defaults can be set");
+        }
+        prm = p;
+}
+
 Landmarks FilterNode::landmarks() const
 {
         Landmarks out;
@@ -183,7 +207,7 @@ void FilterNode::updateZ(const Odometry &msg, float delta_time)
                                         best_d = dk;
                                 }
                         }
-                        if (best_d < MIN_DIST_THRESH)
+                        if (best_d < prm.assoc_dist)
                         {
                                 param_Z[3 + 2 * best] = obs.range;
                                 param_Z[4 + 2 * best] = obs.bearing;
@@ -197,7 +221,7 @@ void FilterNode::updateZ(const Odometry &msg, float delta_time)
         std::vector<LaserData> promoted;
         for (auto &entry : new_landmark_wait)
         {
-                if (entry.second == MIN_LANDMARK_OCC)
+                if (entry.second == prm.promote_count)
                 {
                         promoted.push_back(entry.first);
                         entry.second += 1;
@@ -232,7 +256,7 @@ void FilterNode::updateNewLandmarkWait(const LaserData &data)
                                 best_d = di;
                         }
                 }
-                if (best_d < MIN_DIST_THRESH)
+                if (best_d < prm.assoc_dist)
                 {
                         new_landmark_wait[best].second++;
                         return;
@@ -420,6 +444,30 @@ int aslam_node_enable_innovation(aslam_node *n, int on)
                 g_node_err = e.what();
                 return -1;
         }
+}
+
+int aslam_node_set_params(aslam_node *n, const aslam_params *p)
+{
+        try
+        {
+                if (!p)
+                        throw std::runtime_error("null argument");
+                n->impl->setParams(*p);
+                return 0;
+        }
+        catch (const std::exception &e)
+        {
+                g_node_err = e.what();
+                return -1;
+        }
+}
+
+int aslam_node_get_params(const aslam_node *n, aslam_params *p)
+{
+        if (!p)
+                return -1;
+        *p = n->impl->params();
+        return 0;
 }
 
 int aslam_node_innovation(const aslam_node *n, double *nis, double *logdet)

@@ -103,6 +103,17 @@ class FilterNode
         /// here, at run time ("this core has no innovation record"), not by the linker.
         void enableInnovation(bool on);
         void innovation(double &nis, double &logdet) const;
+        /// The noise and association parameters (aslam_params, aslam_core.h; the reference's config.h constants by default).  The mirror's own
+        /// association and wait-list use assoc_dist and promote_count; everything else lives in the core's record of this filter.  Meant to be
+        /// called before the first callback: the core is then initialised again so that p0_pose applies; later calls change R, Q, var_a,
+        /// assoc_dist and p0_landmark from the next callback on and leave P alone.  Throws on a refused field (the message names it) and, with
+        /// a core that lacks aslam_set_params (bound weakly, like the innovation record; aslam_reset with it), on anything but the defaults -- such
+        /// a core validates nothing: the record is only compared, byte for byte, with the default table.
+        void setParams(const aslam_params &p);
+        const aslam_params &params() const
+        {
+                return prm;
+        }
 
       private:
         int filter;
@@ -115,6 +126,7 @@ class FilterNode
         float last_time;
         bool growth_refused;
         bool slam_ran; // in the last odometry callback
+        aslam_params prm;
         std::vector<LaserData> sensor_landmark;
         std::vector<std::pair<LaserData, uint32_t>> new_landmark_wait;
         std::vector<double> param_X, param_Z; // host copies; P and the authoritative X are device-resident
@@ -166,6 +178,9 @@ int aslam_node_enable_innovation(aslam_node *n, int on);
 /* y^T S^-1 y and ln |det S| of the last odometry callback's slam() (NaN when that callback returned early, or before the first one);
  * -1 with aslam_node_error() while the record is off. */
 int aslam_node_innovation(const aslam_node *n, double *nis, double *logdet);
+/* FilterNode::setParams / params(): 0, or -1 with aslam_node_error() (a refused field, or a core without run-time parameters). */
+int aslam_node_set_params(aslam_node *n, const aslam_params *params);
+int aslam_node_get_params(const aslam_node *n, aslam_params *params);
 /* Narrow `count` recorded odometry messages ([count][8]: px,py,qw,qx,qy,qz,vx,wz) the way cbOdom/updateZandA do
  * (ekf.cpp:139-142): pose[count][2], yaw[count] = quat2euler(...) as binary32, twist[count][2]. */
 void aslam_host_narrow_odom(int64_t count, const double *odom, double *pose, float *yaw, double *twist);

@@ -64,7 +64,26 @@ template <class Filter> int node_main(int argc, char **argv, const char *node_na
         ros::Rate rate(1); // FREQ, config.h:42
         int max_landmark_count = 30; // config.h:45; a private parameter here instead of a recompile
         ros::param::param("~max_landmark_count", max_landmark_count, 30);
+        // the filter constants of config.h:43-66, private parameters too (aslam_params, aslam_core.h; the defaults are the reference's values)
+        aslam_params prm = ASLAM_PARAMS_DEFAULT_INIT;
+        const aslam_params def = prm;
+        ros::param::param("~r_xy", prm.r_xy, def.r_xy);
+        ros::param::param("~r_yaw", prm.r_yaw, def.r_yaw);
+        ros::param::param("~r_range", prm.r_range, def.r_range);
+        ros::param::param("~r_bearing", prm.r_bearing, def.r_bearing);
+        ros::param::param("~q_xy", prm.q_xy, def.q_xy);
+        ros::param::param("~q_yaw", prm.q_yaw, def.q_yaw);
+        ros::param::param("~p0_pose", prm.p0_pose, def.p0_pose);
+        ros::param::param("~p0_landmark", prm.p0_landmark, def.p0_landmark);
+        ros::param::param("~var_a", prm.var_a, def.var_a);
+        double assoc_dist = def.assoc_dist; // (the parameter server has no binary32 and no unsigned type)
+        int promote_count = (int)def.promote_count;
+        ros::param::param("~assoc_dist", assoc_dist, (double)def.assoc_dist);
+        ros::param::param("~promote_count", promote_count, (int)def.promote_count);
+        prm.assoc_dist = (float)assoc_dist;
+        prm.promote_count = promote_count < 0 ? 0u : (uint32_t)promote_count; // (0 is refused by setParams, with the field's name)
         Node<Filter> a(max_landmark_count, queue_size);
+        a.filter.setParams(prm); // before the first callback: p0_pose applies
         std::cerr << banner;
         while (ros::ok())
         {

@@ -20,6 +20,9 @@ namespace aslam
 constexpr int SCAN_BEAMS = 360;
 constexpr float SCAN_STD = 0.4f, SCAN_MIN_MEAN = 1.5f, SCAN_MAX_MEAN = 3.0f; // config.h:49-51
 constexpr int SCAN_MIN_CLUSTER_POINTS = 3;                                   // config.h:52
+// the cluster link distance is config.h:43 MIN_DIST_THRESH in the reference's sensor_landmark node: that node's own compiled-in constant, not the
+// filter's association distance (aslam_params.assoc_dist is per filter; a scan belongs to no filter)
+constexpr float SCAN_LINK_DIST = 0.5f;
 
 /// eigen-decomposition of a symmetric 4x4 matrix (cyclic Jacobi): A -> diagonal, V = eigenvectors in columns
 __device__ __forceinline__ void jacobi4(double (&A)[4][4], double (&V)[4][4])
@@ -286,7 +289,7 @@ __global__ __launch_bounds__(64) void scan_landmarks_kernel(const float *ranges,
         for (int k = 0; k < 6; ++k)
         {
                 const int t = lane + 64 * k;
-                const bool link = (t >= 1 && t < SCAN_BEAMS) && eulerDistance(px[t - 1], py[t - 1], px[t], py[t]) < MIN_DIST_THRESH;
+                const bool link = (t >= 1 && t < SCAN_BEAMS) && eulerDistance(px[t - 1], py[t - 1], px[t], py[t]) < SCAN_LINK_DIST;
                 lm[k] = __ballot(link);
         }
         if (lane == 0)
@@ -299,7 +302,7 @@ __global__ __launch_bounds__(64) void scan_landmarks_kernel(const float *ranges,
         auto linked = [&](int t) -> bool { return (linkm[t >> 6] >> (t & 63)) & 1ull; };
         uint32_t status = 0;
         int nout = 0;
-        if (eulerDistance(px[0], py[0], px[SCAN_BEAMS - 1], py[SCAN_BEAMS - 1]) < MIN_DIST_THRESH)
+        if (eulerDistance(px[0], py[0], px[SCAN_BEAMS - 1], py[SCAN_BEAMS - 1]) < SCAN_LINK_DIST)
                 status = 1u; // ASLAM_SCAN_REF_ABORT: the reference's assert(theta < 359), :69-81
         else
         {

@@ -10,21 +10,22 @@
 // for `nsteps` consecutive callbacks of a recorded trace (MODE_REPLAY), or just slam() for one callback
 // whose association the host did (MODE_STEP).
 //
-// slam() is evaluated in measurement coordinates.  With H square and R = r*I (both true in the reference:
-// ekf.cpp:61,65,276,278), Pt = H P H^T, S = Pt + r I = L L^T, Kt = Pt S^-1:
+// slam() is evaluated in measurement coordinates.  With H square and R diagonal (both true in the reference: ekf.cpp:61,65,276,278;
+// R = diag(r_i) with r_i the filter's r_xy, r_yaw, r_range or r_bearing by row class, aslam_params), Pt = H P H^T, S = Pt + R = L L^T, Kt = Pt S^-1:
 //     K = P H^T S^-1 = H^-1 Kt          ->  X += H^-1 (Kt Y)
-//     (I - K H) P    = H^-1 (r Kt) H^-T
+//     (I - K H) P    = H^-1 (Kt R) H^-T          (Kt R = Pt S^-1 R = Pt - Pt S^-1 Pt: symmetric)
 // which is algebraically identical to ekf.cpp:300-310 and needs at most a Cholesky factor and two triangular
 // solves with n right-hand sides (2.33 n^3 flops instead of 18 n^3); H, H^-1, A are applied as the
-// <=5-non-zeros-per-row operators they are.  With R = r I and P symmetric it is cheaper still:
-//     r Kt = r I - r^2 S^-1,   Kt Y = Y - r S^-1 Y          (cholesky_inverse_tiles: ~n^3 flops, no backward solve)
+// <=5-non-zeros-per-row operators they are.  With Pt = S - R and P symmetric it is cheaper still:
+//     Kt R = R - R S^-1 R,   Kt Y = Y - R S^-1 Y          (cholesky_inverse_tiles: ~n^3 flops, no backward solve)
+// entry (i, j) of the first is (i == j ? r_i : 0) - (r_i r_j) (S^-1)_ij; with all r_i equal this is the reference's r I - r^2 S^-1, bit for bit.
 //
 // Data placement (EKF): P is symmetric and lives in LDS for the whole launch as its lower 16x16 tiles (read from HBM,
 // row-major with row stride NP = 16*NT doubles and zero padding, once at launch start and written back at its end);
 // H P H^T and H^-1 (.) H^-T are one in-place block pass each on those tiles (ekf_small.h); the same tiles are then
 // factored in place (S = Pt + R -> L) next to the inverted diagonal blocks; the triangular solves keep a 16-row block of
 // Pt^T per wave in MFMA accumulators (v_mfma_f64_16x16x4_f64), taken from the tiles before they are factored, with L tiles
-// from LDS as the A operand and the freshly solved tile, untouched, as the B operand; the lower part of r*Kt returns to
+// from LDS as the A operand and the freshly solved tile, untouched, as the B operand; the lower part of Kt R returns to
 // the tiles.  (The UKF keeps P in HBM/L2 and only stages S -> L in the tiles: its LDS is taken by D / DZ slabs.)
 #pragma once
 
@@ -62,6 +63,7 @@ struct DevView
         float *wait_rb;     // [B][max_wait][2]
         uint32_t *wait_cnt; // [B][max_wait]
         int *wait_n;        // [B]
+        const aslam_params *prm; // [B] noise and association parameters (aslam_set_params)
         // bound trace
         int64_t T;
         const double *tr_pose;
@@ -120,6 +122,7 @@ struct SmallShared
         uint32_t status;
         float vx, az, dt, yaw;
         double px, py, tvx, twz, a00, a10;
+        aslam_params prm;     // this filter's parameters: read from HBM once at launch start (small_load), wave-uniform LDS reads at the use sites
         double pp0, pp1, pp2; // the predicted pose of this callback (EKF replay: formed by an idle wave of the front end)
         // the NEXT callback's messages, fetched while this one computes (small_prefetch_intake): valid for callback staged_t
         long long staged_t;
@@ -776,17 +779,19 @@ __device__ __forceinline__ void cholesky_forward_rows(const double *Src, double 
         __syncthreads();
 }
 
-/// EKF update in measurement coordinates when the tiles hold the symmetric P~ and R = r I (ekf.cpp:65,278):
-///     r Kt = r P~ S^-1 = r (S - r I) S^-1 = r I - r^2 S^-1,        Kt Y = Y - r S^-1 Y,        S = P~ + r I = L L^T
+/// EKF update in measurement coordinates when the tiles hold the symmetric P~ and R = diag(r_i) (ekf.cpp:65,278; r4 = the filter's r_xy, r_yaw,
+/// r_range, r_bearing, picked per row by meas_r):
+///     Kt R = P~ S^-1 R = (S - R) S^-1 R = R - R S^-1 R,        Kt Y = Y - R S^-1 Y,        S = P~ + R = L L^T
 /// so only the symmetric inverse S^-1 = L^-T L^-1 is needed: Cholesky (n^3/3), the forward substitution of the IDENTITY
 /// (its row blocks are triangular: n^3/3) and one triangular symmetric product (n^3/3) -- n^3 flops instead of the 2.33 n^3
 /// of factor + forward + backward on n right-hand sides, and no backward substitution at all.  The cancellation in
-/// r - r^2 (S^-1)_ii costs log10(r / P~_ii) digits (2-4 here), far inside the 1e-6 bar.
-/// In: tiles = P~ (lower).  Out: tiles = lower part of r Kt (zero padding), U = Kt Y.  Same three wave roles and look-ahead
+/// r_i - r_i^2 (S^-1)_ii costs log10(r_i / P~_ii) digits in row i (2-4 with the reference's constants, far inside the 1e-6 bar; a row whose
+/// r_i is set far above its P~_ii loses correspondingly more).
+/// In: tiles = P~ (lower).  Out: tiles = lower part of Kt R (zero padding), U = Kt Y.  Same three wave roles and look-ahead
 /// as cholesky_forward_rows; `Tv`: LDS scratch of 16*NT doubles.  Ends with a barrier.
 template <int NT>
 __device__ __forceinline__ void cholesky_inverse_tiles(double *Lt, double *Dinv, int nt, int n_true, const double *Y, double *U,
-                                                       double *Tv, double r, int tid, uint32_t *status, unsigned long long *wave_busy = nullptr)
+                                                       double *Tv, const double *r4, int tid, uint32_t *status, unsigned long long *wave_busy = nullptr)
 {
 #ifdef ASLAM_STAMPS
         // diagnostic builds: per role, shader cycles busy between the barriers of the factorisation loop (slot 0) and, for the diagonal wave, inside the
@@ -801,7 +806,7 @@ __device__ __forceinline__ void cholesky_inverse_tiles(double *Lt, double *Dinv,
         const int wave = role_of_wave(__builtin_amdgcn_readfirstlane(tid >> 6), DW), lane = tid & 63;
         const int li = lane & 15, lg = lane >> 4;
         if (tid < 16 * nt)
-                *tile_elem(Lt, tid, tid) += (tid < n_true) ? r : 1.0; // S = P~ + R; padding decouples
+                *tile_elem(Lt, tid, tid) += (tid < n_true) ? meas_r(r4, tid) : 1.0; // S = P~ + R; padding decouples
         __syncthreads();
         if (wave < nt)
         {
@@ -867,8 +872,9 @@ __device__ __forceinline__ void cholesky_inverse_tiles(double *Lt, double *Dinv,
                                         Lt[tile_index(cb, rb) * TSZ + (lg + 4 * q) * TLD + li] = acc[cb][q];
                         }
                 }
+                const double r_u = (16 * rb + li < n_true) ? meas_r(r4, 16 * rb + li) : 1.0; // r_i of this lane's row of U (in flight across the barrier)
                 __syncthreads(); // [A] L^-1 complete, t published
-                // U = Kt Y = Y - r S^-1 Y = Y - r L^-T t: this wave's rows of L^-T are its accumulators
+                // U = Kt Y = Y - R S^-1 Y = Y - R L^-T t: this wave's rows of L^-T are its accumulators
                 {
                         double pu = 0.0;
 #pragma unroll
@@ -884,7 +890,7 @@ __device__ __forceinline__ void cholesky_inverse_tiles(double *Lt, double *Dinv,
                         pu += __shfl_xor(pu, 16);
                         pu += __shfl_xor(pu, 32);
                         if (lg == 0)
-                                U[16 * rb + li] = Y[16 * rb + li] - r * pu;
+                                U[16 * rb + li] = Y[16 * rb + li] - r_u * pu;
                 }
                 WB(2); // (row-block roles: everything behind the factorisation loop -- L^-1 to the tiles, the L^-T L^-1 product, r I - r^2 S^-1)
         }
@@ -977,23 +983,60 @@ __device__ __forceinline__ void cholesky_inverse_tiles(double *Lt, double *Dinv,
 #ifdef ASLAM_STAMPS
                 tp1_ = __builtin_amdgcn_s_memtime();
 #endif
+                const double r_rng = r4[2], r_brg = r4[3]; // (in flight across the barrier)
                 __syncthreads(); // [B] nobody reads L^-1 any more
-                const double r2 = r * r;
+                // r_i r_j of this lane's entries without a look-up per entry (profiles/params.md): the tile offsets and 4 q are even, so row
+                // i = 16 rb + lg + 4 q has the parity of lg and column j = 16 jb + li that of li -- range rows are odd, bearing rows even (meas_r) --: one
+                // product per lane serves every tile off block column 0; the pose columns 0 .. 2 lie in block column 0, the pose rows in tile (0, 0).
+                // Tiles below the diagonal blocks (a wave-uniform test) have no diagonal entry and no entry above the diagonal: 0 - c out, unmasked.
+                const double r_row = (lg & 1) ? r_rng : r_brg, r_col = (li & 1) ? r_rng : r_brg;
+                const double c_lm = r_row * r_col;
 #pragma unroll
                 for (int qq = 0; qq < TPW; ++qq)
                 {
                         if (orb[qq] >= 0)
                         {
-#pragma unroll
-                                for (int q = 0; q < 4; ++q)
+                                const int rbq = orb[qq], jbq = ojb[qq];
+                                double *const T = Lt + tile_index(rbq, jbq) * TSZ + li;
+                                double rj = r_col, c = c_lm;
+                                if (jbq == 0)
                                 {
-                                        const int i = 16 * orb[qq] + lg + 4 * q, j = 16 * ojb[qq] + li;
-                                        if (j <= i)
+                                        rj = li < 2 ? r4[0] : li == 2 ? r4[1] : r_col;
+                                        c = r_row * rj;
+                                }
+                                if (rbq != jbq && 16 * rbq + 16 <= n_true) // (j < i < n: every row block but the last)
+                                {
+#pragma unroll
+                                        for (int q = 0; q < 4; ++q)
+                                                T[(lg + 4 * q) * TLD] = 0.0 - c * out[qq][q];
+                                }
+                                else if (rbq != jbq)
+                                {
+#pragma unroll
+                                        for (int q = 0; q < 4; ++q)
+                                                T[(lg + 4 * q) * TLD] = (16 * rbq + lg + 4 * q < n_true) ? 0.0 - c * out[qq][q] : 0.0; // (j < i)
+                                }
+                                else
+                                {
+#pragma unroll
+                                        for (int q = 0; q < 4; ++q)
                                         {
-                                                double v = 0.0;
-                                                if (i < n_true) // (j <= i < n)
-                                                        v = ((i == j) ? r : 0.0) - r2 * out[qq][q];
-                                                Lt[tile_index(orb[qq], ojb[qq]) * TSZ + (lg + 4 * q) * TLD + li] = v;
+                                                const int i = 16 * rbq + lg + 4 * q, j = 16 * jbq + li;
+                                                if (j <= i)
+                                                {
+                                                        double v = 0.0;
+                                                        if (i < n_true) // (j <= i < n)
+                                                        {
+                                                                double ri = r_row, cq = c;
+                                                                if (rbq == 0 && q == 0) // rows 0 .. 3
+                                                                {
+                                                                        ri = lg < 2 ? r4[0] : lg == 2 ? r4[1] : r_row;
+                                                                        cq = ri * rj;
+                                                                }
+                                                                v = ((i == j) ? ri : 0.0) - cq * out[qq][q];
+                                                        }
+                                                        T[(lg + 4 * q) * TLD] = v;
+                                                }
                                         }
                                 }
                         }
@@ -1120,6 +1163,7 @@ template <int MODE> __device__ __forceinline__ void small_load(const DevView &d,
                 sm.wn = d.wait_n[b];
                 sm.a00 = d.A[2 * b];
                 sm.a10 = d.A[2 * b + 1];
+                sm.prm = d.prm[b];
         }
         __syncthreads();
         if (MODE == MODE_REPLAY)
@@ -1326,6 +1370,7 @@ __device__ __forceinline__ bool small_frontend(const DevView &d, const SmallLds 
         __syncthreads();
         const int n0 = sm.n;
         const int nl = (n0 - 3) / 2;
+        const float assoc_dist = sm.prm.assoc_dist; // MIN_DIST_THRESH (config.h:43)
         for (int j = tid; j < sm.sn; j += SMALL_WG)
         {
                 const float bb = normalizeAngle(sSb[j]);
@@ -1487,7 +1532,7 @@ __device__ __forceinline__ bool small_frontend(const DevView &d, const SmallLds 
                         }
                         sMd[j] = bd;
                         sCid[j] = 2 * bk;
-                        if (n0 != 3 && bd < MIN_DIST_THRESH)
+                        if (n0 != 3 && bd < assoc_dist)
                                 atomicMax(&sNew[bk], j); // observations are walked in order: the last one wins (ekf.cpp:175-181)
                         else
                                 sm.any_miss = 1;
@@ -1498,7 +1543,7 @@ __device__ __forceinline__ bool small_frontend(const DevView &d, const SmallLds 
         // associated observations: Z(3 + corr_id) = range, Z(4 + corr_id) = bearing
         for (int j = tid; j < sm.sn; j += SMALL_WG)
         {
-                if (n0 != 3 && sMd[j] < MIN_DIST_THRESH && sNew[sCid[j] >> 1] == j)
+                if (n0 != 3 && sMd[j] < assoc_dist && sNew[sCid[j] >> 1] == j)
                 {
                         sZ[3 + sCid[j]] = (double)sSr[j];
                         sZ[4 + sCid[j]] = (double)sSb[j];
@@ -1534,7 +1579,7 @@ __device__ __forceinline__ bool small_frontend(const DevView &d, const SmallLds 
                 constexpr int NWAVE = SMALL_WG / 64;
                 for (int j = 0; j < sm.sn; ++j) // (workgroup-uniform: every condition below reads LDS values published by a barrier)
                 {
-                        if (n0 != 3 && sMd[j] < MIN_DIST_THRESH)
+                        if (n0 != 3 && sMd[j] < assoc_dist)
                                 continue;
                         const int wn = sm.wn;
                         if (wn > 0)
@@ -1593,7 +1638,7 @@ __device__ __forceinline__ bool small_frontend(const DevView &d, const SmallLds 
                                                 corr = bi;
                                                 mind = bd;
                                         }
-                                        if (mind < MIN_DIST_THRESH)
+                                        if (mind < assoc_dist)
                                                 sWc[corr]++;
                                         else
                                                 push = true;
@@ -1619,10 +1664,11 @@ __device__ __forceinline__ bool small_frontend(const DevView &d, const SmallLds 
                 if (tid == 0)
                         sm.any_promote = 0;
                 __syncthreads();
+                const uint32_t promote_count = sm.prm.promote_count; // MIN_LANDMARK_OCC (config.h:44)
                 {
                         bool mine = false;
                         for (int i = tid; i < sm.wn; i += SMALL_WG)
-                                mine = mine || (sWc[i] == MIN_LANDMARK_OCC);
+                                mine = mine || (sWc[i] == promote_count);
                         if (mine)
                                 sm.any_promote = 1;
                 }
@@ -1633,7 +1679,7 @@ __device__ __forceinline__ bool small_frontend(const DevView &d, const SmallLds 
                         int nnew = 0;
                         for (int i = 0; i < wn; ++i)
                         {
-                                if (sWc[i] == MIN_LANDMARK_OCC)
+                                if (sWc[i] == promote_count)
                                 {
                                         if (nnew < NEW_CAP)
                                                 sNew[nnew] = i;
@@ -1673,6 +1719,7 @@ __device__ __forceinline__ bool small_frontend(const DevView &d, const SmallLds 
         {
                 // conservativeResizeLike(Identity * UKF_KP_LANDMARK_POSE), ekf.cpp:277
                 const int g0 = sm.grow_from, n1 = sm.n;
+                const double p0_lm = sm.prm.p0_landmark;
                 for (int idx = tid; idx < n1 * n1; idx += SMALL_WG)
                 {
                         const int i = idx / n1, j = idx - i * n1;
@@ -1680,10 +1727,10 @@ __device__ __forceinline__ bool small_frontend(const DevView &d, const SmallLds 
                         {
                                 // P lives in LDS as lower tiles (single-CU EKF): new rows of the lower triangle
                                 if (i >= g0 && j <= i)
-                                        *tile_elem(tilesP, i, j) = (i == j) ? (double)KP_LANDMARK_POSE : 0.0;
+                                        *tile_elem(tilesP, i, j) = (i == j) ? p0_lm : 0.0;
                         }
                         else if (i >= g0 || j >= g0)
-                                Pg[(size_t)i * NP + j] = (i == j) ? (TP)KP_LANDMARK_POSE : (TP)0;
+                                Pg[(size_t)i * NP + j] = (i == j) ? (TP)p0_lm : (TP)0;
                 }
         }
         if (sm.flags & FLAG_INIT_X)

@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) void ukf_large_sigma_pose(DevView d, LargeView
         double *Dg = uv.D + (size_t)b * NP * MP, *DZg = uv.DZ + (size_t)b * NP * MP;
         const double *sc = uv.sc + (size_t)b * 8;
         const float vx = (float)sc[0], az = (float)sc[1], dtf = (float)sc[2];
-        const double std_a = sqrt((double)(UKF_STD_A * UKF_STD_A)); // llt of the augmented diagonal, ukf.cpp:276,280
+        const double std_a = sqrt(d.prm[b].var_a); // llt of the augmented diagonal, ukf.cpp:276,280
         const double x0 = X[0], x1 = X[1], x2 = X[2];
         double part[3] = {0.0, 0.0, 0.0};
         for (int i = tid; i < mk; i += 256)
@@ -477,6 +477,13 @@ __global__ __launch_bounds__(256) void ukf_large_wabt(DevView d, LargeView<doubl
         if (idle)
                 return;
         double *C = (mode == WABT_P ? lv.P : mode == WABT_S ? lv.S : lv.G) + (size_t)b * NP * NP;
+        // Q on the pose diagonal of P- (ukf.cpp:66-68), R on the diagonal of S (ukf.cpp:378): this filter's record, read once behind the product loop
+        const aslam_params *const prm = d.prm + b;
+        double q_xy = 0.0, q_yaw = 0.0, r_xy = 0.0, r_yaw = 0.0, r_range = 0.0, r_bearing = 0.0; // (mode is a kernel argument: each launch loads what it adds)
+        if (mode == WABT_P)
+                q_xy = prm->q_xy, q_yaw = prm->q_yaw;
+        else if (mode == WABT_S)
+                r_xy = prm->r_xy, r_yaw = prm->r_yaw, r_range = prm->r_range, r_bearing = prm->r_bearing;
         const bool diagq = sym && rt == jt && wc == wr; // holds (i, j) and (j, i): the lower one is stored to both places
 #pragma unroll
         for (int u = 0; u < 4; ++u)
@@ -495,14 +502,14 @@ __global__ __launch_bounds__(256) void ukf_large_wabt(DevView d, LargeView<doubl
                                 {
                                         if (!valid)
                                                 continue; // P's padding stays zero
-                                        const double val = acc[u][v][r] + ((row == col && row < 3) ? (double)KQ : 0.0);
+                                        const double val = acc[u][v][r] + ((row == col && row < 3) ? (row < 2 ? q_xy : q_yaw) : 0.0);
                                         C[(size_t)row * NP + col] = val;
                                         if (row != col) // (the mirror image; a diagonal quadrant stores its lower half to both places)
                                                 C[(size_t)col * NP + row] = val;
                                 }
                                 else if (mode == WABT_S)
                                 {
-                                        const double val = valid ? acc[u][v][r] + (row == col ? (double)KR : 0.0) : (row == col ? 1.0 : 0.0);
+                                        const double val = valid ? acc[u][v][r] + (row == col ? (row < 2 ? r_xy : row == 2 ? r_yaw : (row & 1) ? r_range : r_bearing) : 0.0) : (row == col ? 1.0 : 0.0);
                                         C[(size_t)row * NP + col] = val;
                                         if (diagq && row != col)
                                                 C[(size_t)col * NP + row] = val;

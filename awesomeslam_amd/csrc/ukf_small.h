@@ -60,7 +60,7 @@ enum
 {
         GEMM_STORE = 0,    // C = A diag(w) B^T            (HBM, full matrix)
         GEMM_SUBTRACT = 1, // C -= A diag(w) B^T           (HBM, full matrix)
-        GEMM_TILES = 2,    // lower tiles of A diag(w) B^T + diag_add on the true diagonal -> LDS tile storage
+        GEMM_TILES = 2,    // lower tiles of A diag(w) B^T + diag(R) on the true diagonal -> LDS tile storage
         GEMM_SUBTRACT_SYM = 3 // C -= A diag(w) A^T for a symmetric C: the lower tiles are computed (45 instead of 81 at NT = 9) and their new values stored
                               // into the upper triangle as well -- the (i, j) and (j, i) sums of the full product are the same MFMA chains, bit for bit
 };
@@ -70,7 +70,7 @@ enum
 /// of LDS.  Output tiles are dealt round-robin to the waves (<= TPW per wave).
 template <int NT, int MODE, bool SKIP_K0 = false>
 __device__ __forceinline__ void gemm_wabt(const double *A, const double *B, int ld, int nks, const double *w, int nt,
-                                          double *Cg, double *Ct, double diag_add, int n_true, double *stage, int tid,
+                                          double *Cg, double *Ct, const double *diag_r4, int n_true, double *stage, int tid,
                                           const double *gvec = nullptr, double gscale = 0.0, const double *pdelta = nullptr, double pcll = 0.0,
                                           double pwsum = 0.0)
 {
@@ -199,7 +199,7 @@ __device__ __forceinline__ void gemm_wabt(const double *A, const double *B, int 
                                 {
                                         double v = acc[q][r];
                                         if (i == j)
-                                                v += (i < n_true) ? diag_add : 1.0;
+                                                v += (i < n_true) ? meas_r(diag_r4, i) : 1.0; // + R (ukf.cpp:378): the filter's r_xy, r_yaw, r_range, r_bearing by row class
                                         Ct[tile_index(ib, jb) * TSZ + (lg + 4 * r) * TLD + li] = v;
                                 }
                                 else if (MODE == GEMM_STORE)
@@ -364,7 +364,6 @@ __global__ __launch_bounds__(SMALL_WG) void ukf_small_kernel(DevView d, UkfView 
         double *DZg = uv.DZ + (size_t)b * NP * MP;
         double *Tcg = uv.Tc + (size_t)b * NP * NP;
         double *Kg = uv.K + (size_t)b * NP * NP;
-        const double r_meas = (double)KR, q_proc = (double)KQ;
 
 #ifdef ASLAM_STAMPS
         unsigned long long stamp_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -413,7 +412,7 @@ __global__ __launch_bounds__(SMALL_WG) void ukf_small_kernel(DevView d, UkfView 
                 const double w_i = (double)(float)(0.5 / (double)den_f);
                 const double w_0 = (double)(lambda_f / den_f);
                 const double wsp = (double)sqrtf(den_f);
-                const double std_a = sqrt((double)(UKF_STD_A * UKF_STD_A)); // llt of the augmented diagonal, ukf.cpp:276,280
+                const double std_a = sqrt(sm.prm.var_a); // llt of the augmented diagonal, ukf.cpp:276,280
                 {
                         // One store per thread, none of them masked: threads beyond the padded sigma-point count write a spare slot.
                         // (A thread-strided loop here leaves EXEC empty at its exit; hipcc has placed VGPR spill stores into exactly
@@ -651,7 +650,7 @@ __global__ __launch_bounds__(SMALL_WG) void ukf_small_kernel(DevView d, UkfView 
 #pragma unroll
                                                 for (int a = 0; a < 3; ++a)
                                                 {
-                                                        Pg[(size_t)k * NP + a] = acc[a] + ((a == k) ? q_proc : 0.0);
+                                                        Pg[(size_t)k * NP + a] = acc[a] + ((a == k) ? (k < 2 ? sm.prm.q_xy : sm.prm.q_yaw) : 0.0);
                                                         Tcg[(size_t)a * NP + k] = tcc[a];
                                                 }
                                                 double zd = sZ[k] - zp;
@@ -855,7 +854,7 @@ __global__ __launch_bounds__(SMALL_WG) void ukf_small_kernel(DevView d, UkfView 
                 const double zscale = sqrt(-w_0);
                 for (int k = tid; k < NP; k += SMALL_WG)
                         sZv[k] = (k < n) ? zscale * DZg[(size_t)k * MP] : 0.0;
-                gemm_wabt<NT, GEMM_TILES, true>(DZg, DZg, MP, mt, sW, nt, nullptr, Lt, r_meas, n, stage, tid);
+                gemm_wabt<NT, GEMM_TILES, true>(DZg, DZg, MP, mt, sW, nt, nullptr, Lt, &sm.prm.r_xy, n, stage, tid);
                 // (GEMM_TILES wrote the tiles over the staging area after its last barrier; it ends with a barrier)
                 // z rides along as right-hand side row n (n is odd, so row n is always a padding row of the last tile)
                 for (int j = tid; j < 16 * nt; j += SMALL_WG)
@@ -943,7 +942,7 @@ __global__ __launch_bounds__(SMALL_WG) void ukf_small_kernel(DevView d, UkfView 
                         }
                         ASLAM_STAMP(9);
                         // ---- P = P - K S K^T (ukf.cpp:391) = P - W W^T - g g^T / (1 - q.q)
-                        gemm_wabt<NT, GEMM_SUBTRACT_SYM>(Kg, Kg, NP, nt, nullptr, nt, Pg, nullptr, 0.0, n, stage, tid, sGv, inv_den, sZpred, cll, wsum);
+                        gemm_wabt<NT, GEMM_SUBTRACT_SYM>(Kg, Kg, NP, nt, nullptr, nt, Pg, nullptr, nullptr, n, stage, tid, sGv, inv_den, sZpred, cll, wsum);
                 }
 
                 ASLAM_STAMP(10);

@@ -110,10 +110,51 @@ typedef struct
 /* EKFSlam()/UKFSlam() + initialize(): ekf.cpp:39-71, ukf.cpp:39-67 (for every filter of the batch) */
 int aslam_create(const aslam_config *cfg, aslam_ctx **out);
 int aslam_destroy(aslam_ctx *ctx);
-/* initialize() again: N = 3, P/Q/R defaults, empty wait-list, init_x = init_z = true */
+/* initialize() again: N = 3, P = p0_pose * I, empty wait-list, init_x = init_z = true; the parameters (aslam_set_params) stay */
 int aslam_reset(aslam_ctx *ctx);
 const char *aslam_last_error(void);
 int aslam_abi_version(void);
+
+/* ---- noise and association parameters, per filter ---------------------------------------------------- */
+/* The reference compiles these in (include/awesome_slam/config.h: "changing a filter constant = recompile"); here every filter of a context
+ * holds its own record in HBM and every kernel family reads it at launch start.  R and Q stay diagonal, as the reference builds them.
+ * UKF_STD_YAW (config.h:55) is NOT a parameter: stateTransitionFunction takes the yaw rate from its `az` argument and never reads
+ * point(N+1) (common.h:46-75), so Paug(N+1,N+1) (ukf.cpp:277) cannot reach any result of the filter. */
+typedef struct
+{
+        double r_xy, r_yaw;        /* R(0,0) = R(1,1), R(2,2): the odometry pose "measurement" rows (ekf.cpp:65) */
+        double r_range, r_bearing; /* R(3+2i,3+2i), R(4+2i,4+2i) (ekf.cpp:278) */
+        double q_xy, q_yaw;        /* Q(0,0) = Q(1,1), Q(2,2) (ekf.cpp:66-68) */
+        double p0_pose;            /* P diagonal at initialize() / aslam_reset (ekf.cpp:64) */
+        double p0_landmark;        /* new P diagonal on growth (ekf.cpp:277, aslam_grow) */
+        double var_a;              /* UKF: Paug(N,N) (ukf.cpp:276); ignored by the EKF */
+        float assoc_dist;          /* MIN_DIST_THRESH (config.h:43): landmark association and wait-list match */
+        uint32_t promote_count;    /* MIN_LANDMARK_OCC (config.h:44) */
+} aslam_params;                    /* 80 bytes */
+
+/* The reference's constants, each the widened binary32 value the reference's own arithmetic sees (config.h declares them `const float`).
+ * THE default table: aslam_params_default(), the device kernels' fresh contexts and the host mirror all initialise from it. */
+#define ASLAM_PARAMS_DEFAULT_INIT                                                                                                           \
+        {                                                                                                                                   \
+                (double)0.2f, (double)0.2f, (double)0.2f, (double)0.2f, /* EKF_KR == UKF_KR */                                              \
+                (double)0.001f, (double)0.001f,                         /* EKF_KQ == UKF_KQ */                                              \
+                (double)0.001f,                                         /* EKF_KP_ROBOT_POSE == UKF_KP_ROBOT_POSE */                        \
+                1.0,                                                    /* UKF_KP_LANDMARK_POSE, used by BOTH nodes on growth */            \
+                (double)(0.2f * 0.2f),                                  /* UKF_STD_A * UKF_STD_A, a binary32 product */                     \
+                0.5f, 10u                                               /* MIN_DIST_THRESH, MIN_LANDMARK_OCC */                             \
+        }
+
+int aslam_params_default(aslam_params *out);
+/* Set the record of filter `traj` (-1 = every filter of the context); synchronises like the getters.  ASLAM_ERR_ARG, with a message that names
+ * the field, unless r_*, p0_*, var_a and assoc_dist are finite and > 0, q_* finite and >= 0 and promote_count >= 1.
+ * r_*, q_*, var_a and assoc_dist apply from the next callback (= rewriting the diagonals of the reference's R and Q); p0_landmark to later
+ * growths; p0_pose at the next aslam_reset.  promote_count is compared with `==` against the counts as they stand, as the reference compares
+ * (ekf.cpp:187-195): set it before the first callback, or entries already past the new value are never promoted.
+ * aslam_reset keeps the parameters, as it keeps the innovation setting.  Snapshots (aslam_snapshot.h) do not carry them and aslam_restore
+ * leaves the destination's alone: one filter forked into B copies with B noise models is aslam_restore + aslam_set_params.
+ * In ASLAM_F32 contexts the parameters stay binary64 and are rounded where the chain rounds S. */
+int aslam_set_params(aslam_ctx *ctx, int traj, const aslam_params *params);
+int aslam_get_params(aslam_ctx *ctx, int traj, aslam_params *params);
 
 /* ---- the per-callback seam (host keeps association/growth: ekf.cpp:137-290 stay on the host) ------ */
 /* Set the device state of one filter: dimension n, X[n], Z[n], P[n*n] row-major (any of them NULL = keep).
@@ -121,7 +162,7 @@ int aslam_abi_version(void);
  * wait-list or the status bits: aslam_snapshot.h moves a WHOLE filter. */
 int aslam_set_state(aslam_ctx *ctx, int traj, int n, const double *X, const double *Z, const double *P);
 /* the matrix part of updateNewLandmark (ekf.cpp:271-278 / ukf.cpp:238-245): grow filter `traj` from its
- * current dimension to n_new; new P diagonal = UKF_KP_LANDMARK_POSE, new X/Z entries from the seeds
+ * current dimension to n_new; new P diagonal = the filter's p0_landmark (UKF_KP_LANDMARK_POSE), new X/Z entries from the seeds
  * (x_seed, z_seed hold n_new - n_old values). */
 int aslam_grow(aslam_ctx *ctx, int traj, int n_new, const double *x_seed, const double *z_seed);
 /* EKFSlam::slam (ekf.cpp:293-311) for one filter.  Z[n] is param.Z after updateZandA, a00/a10 are

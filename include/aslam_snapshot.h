@@ -25,7 +25,9 @@
  *
  * Records have their exact size (aslam_snapshot_record_bytes): a young filter in a large context is a few hundred bytes.
  * Not part of a record: the bound trace and the replay position (the caller's), the innovation record (restore sets it to NaN for the slots
- * it fills: "no callback yet"), and all scratch of the kernels.
+ * it fills: "no callback yet"), all scratch of the kernels, and the filter's parameters (aslam_params, aslam_core.h): format v1 does not carry
+ * them and aslam_restore leaves the destination slot's record alone -- one filter forked into B slots takes B noise models with one
+ * aslam_set_params per slot.
  *
  * Status returns and aslam_last_error() as in aslam_core.h.
  */
