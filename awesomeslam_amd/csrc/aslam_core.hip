@@ -186,90 +186,78 @@ const char *bad_param(const aslam_params &p)
         return p.promote_count < 1 ? "promote_count" : nullptr;
 }
 
-template <typename T> int init_P_large(aslam_ctx *c, LargeView<T> &lv)
+/// whether `p`, an array handed to a for_each_array visitor, is member `m` of the visited view
+template <typename P, typename M> bool same_slot(const P &p, const M &m)
 {
-        const size_t B = c->cfg.batch, NP = c->NP;
-        HIP_TRY(hipMemset(lv.P, 0, sizeof(double) * B * NP * NP));
-        HIP_TRY(hipMemset(lv.G, 0, sizeof(T) * B * NP * NP));
-        HIP_TRY(hipMemset(lv.S, 0, sizeof(T) * B * NP * NP));
-        if (lv.Vw)
-                HIP_TRY(hipMemset(lv.Vw, 0, sizeof(T) * B * NP * NP));
-        return seed_pose_block(c, lv.P, B, NP);
+        return static_cast<const void *>(&p) == static_cast<const void *>(&m);
+}
+
+/// elements per filter of the array member `m` of view `v` points to, as the view's for_each_array says (np: the NP a UKF view does not carry)
+template <typename V, typename M, typename... NP> size_t per_filter(V v, M V::*m, NP... np)
+{
+        size_t n = 0;
+        for_each_array(v, np..., [&](auto *&p, size_t per, bool) {
+                if (same_slot(p, v.*m))
+                        n = per;
+        });
+        return n;
+}
+
+/// f(pointer, bytes per filter) for every array of the context that must be zero when a filter starts (the `zero` entries of for_each_array):
+/// aslam_reset clears them for the whole batch, snapshot_unpack for the slots it restores -- one list, so the two cannot differ
+template <typename F> void for_each_scratch(aslam_ctx *c, F &&f)
+{
+        auto pick = [&f](auto *&p, size_t per, bool zero) {
+                if (zero && p)
+                        f(static_cast<void *>(p), per * sizeof(*p));
+        };
+        if (c->large)
+                with_large_view(c, [&](auto &lv) { return for_each_array(lv, pick), 0; });
+#if ASLAM_HAVE_UKF
+        for_each_array(c->ukf, c->NP, pick);
+        for_each_array(c->ukfl, c->NP, pick);
+#endif
 }
 
 /// initialize() for the whole batch: ekf.cpp:49-71 / ukf.cpp:49-67
 int init_state(aslam_ctx *c)
 {
-        const int B = c->cfg.batch, NP = c->NP;
+        const size_t B = c->cfg.batch, NP = c->NP;
         DevView &d = c->dv;
+        double *P = c->large ? c->largeP : d.P;
         HIP_TRY(hipMemset(d.X, 0, sizeof(double) * B * NP));
         HIP_TRY(hipMemset(d.Z, 0, sizeof(double) * B * NP));
-        if (!c->large)
-                HIP_TRY(hipMemset(d.P, 0, sizeof(double) * (size_t)B * NP * NP));
+        HIP_TRY(hipMemset(P, 0, sizeof(double) * B * NP * NP));
         HIP_TRY(hipMemset(d.status, 0, sizeof(uint32_t) * B));
         HIP_TRY(hipMemset(d.sens_n, 0, sizeof(int) * B));
         HIP_TRY(hipMemset(d.wait_n, 0, sizeof(int) * B));
         std::vector<int> n(B, 3), fl(B, FLAG_INIT_X | FLAG_INIT_Z);
-        std::vector<double> A(2 * (size_t)B, 0.0);
-        for (int b = 0; b < B; ++b)
+        std::vector<double> A(2 * B, 0.0);
+        for (size_t b = 0; b < B; ++b)
                 A[2 * b] = 1.0; // A = Identity
         HIP_TRY(hipMemcpy(d.n, n.data(), sizeof(int) * B, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d.flags, fl.data(), sizeof(int) * B, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d.A, A.data(), sizeof(double) * 2 * B, hipMemcpyHostToDevice));
-        if (c->large)
-                return with_large_view(c, [&](auto &lv) { return init_P_large(c, lv); });
-#if ASLAM_HAVE_UKF
-        if (c->ukf.D)
-        { // a reset context is a fresh one: the scratch too (ukf_alloc zeroes it; the kernels rely on never-written padding staying zero)
-                const size_t MP = (size_t)c->ukf.MP;
-                HIP_TRY(hipMemset(c->ukf.D, 0, sizeof(double) * (size_t)B * NP * MP));
-                HIP_TRY(hipMemset(c->ukf.DZ, 0, sizeof(double) * (size_t)B * NP * MP));
-                HIP_TRY(hipMemset(c->ukf.Tc, 0, sizeof(double) * (size_t)B * NP * NP));
-                HIP_TRY(hipMemset(c->ukf.K, 0, sizeof(double) * (size_t)B * NP * NP));
-        }
-#endif
-        return seed_pose_block(c, d.P, B, NP);
+        // a reset context is a fresh one: the scratch too (dev_alloc zeroes it; the kernels rely on never-written padding staying zero)
+        hipError_t e = hipSuccess;
+        for_each_scratch(c, [&](void *p, size_t bytes) {
+                if (e == hipSuccess)
+                        e = hipMemset(p, 0, B * bytes);
+        });
+        HIP_TRY(e);
+        return seed_pose_block(c, P, B, NP);
 }
 
-template <int NT, int MODE, bool STATS>
-int launch_ekf(aslam_ctx *c, int grid, int64_t t0, int nsteps, double *poses, int32_t *dims, StepArgs sa, hipStream_t st, StatsView sv)
+/// one launch of a single-CU kernel with LDS layout L; `views`: what the kernel takes first (the device view; the UKF's scratch behind it)
+template <typename L, typename K, typename... V>
+int launch_small(K kern, int grid, hipStream_t st, int64_t t0, int nsteps, double *poses, int32_t *dims, StepArgs sa, StatsView sv, const V &...views)
 {
-        auto kern = ekf_small_kernel<NT, MODE, STATS>;
-        const size_t lds = SmallLayout<NT>::total;
+        const size_t lds = L::total;
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(SMALL_WG), lds, st, c->dv, t0, nsteps, poses, dims, sa, sv);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(SMALL_WG), lds, st, views..., t0, nsteps, poses, dims, sa, sv);
         HIP_TRY(hipGetLastError());
         return ASLAM_OK;
 }
-
-#if ASLAM_HAVE_UKF
-/// HBM scratch of the UKF kernels: D, DZ ([NP][MP]) and Tc, K ([NP][NP]) per filter
-int ukf_alloc(aslam_ctx *c)
-{
-        const size_t B = (size_t)c->cfg.batch, NP = (size_t)c->NP;
-        const size_t MP = 2 * NP + 16;
-        c->ukf.MP = (int)MP;
-        int rc = dev_alloc(c, &c->ukf.D, B * NP * MP, c->owned);
-        if (rc == ASLAM_OK)
-                rc = dev_alloc(c, &c->ukf.DZ, B * NP * MP, c->owned);
-        if (rc == ASLAM_OK)
-                rc = dev_alloc(c, &c->ukf.Tc, B * NP * NP, c->owned);
-        if (rc == ASLAM_OK)
-                rc = dev_alloc(c, &c->ukf.K, B * NP * NP, c->owned);
-        return rc;
-}
-
-template <int NT, int MODE, bool STATS>
-int launch_ukf(aslam_ctx *c, int grid, int64_t t0, int nsteps, double *poses, int32_t *dims, StepArgs sa, hipStream_t st, StatsView sv)
-{
-        auto kern = ukf_small_kernel<NT, MODE, STATS>;
-        const size_t lds = UkfLayout<NT>::total;
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(SMALL_WG), lds, st, c->dv, c->ukf, t0, nsteps, poses, dims, sa, sv);
-        HIP_TRY(hipGetLastError());
-        return ASLAM_OK;
-}
-#endif
 
 /// f(std::integral_constant<int, NT>) for the tile count of a single-CU context: the small kernels are instantiated for 2, 5 and 9 tiles
 template <typename F> auto with_NT(int NT, F &&f)
@@ -296,14 +284,16 @@ int launch(aslam_ctx *c, int grid, int64_t t0, int nsteps, double *poses, int32_
                 });
         if (c->cfg.filter == ASLAM_EKF)
                 return with_NT(c->NT, [&](auto nt) {
-                        return sv.any() ? launch_ekf<decltype(nt)::value, MODE, true>(c, grid, t0, nsteps, poses, dims, sa, st, sv)
-                                        : launch_ekf<decltype(nt)::value, MODE, false>(c, grid, t0, nsteps, poses, dims, sa, st, sv);
+                        constexpr int NT = decltype(nt)::value;
+                        return sv.any() ? launch_small<SmallLayout<NT>>(ekf_small_kernel<NT, MODE, true>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv)
+                                        : launch_small<SmallLayout<NT>>(ekf_small_kernel<NT, MODE, false>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv);
                 });
 #if ASLAM_HAVE_UKF
         if (c->cfg.filter == ASLAM_UKF)
                 return with_NT(c->NT, [&](auto nt) {
-                        return sv.any() ? launch_ukf<decltype(nt)::value, MODE, true>(c, grid, t0, nsteps, poses, dims, sa, st, sv)
-                                        : launch_ukf<decltype(nt)::value, MODE, false>(c, grid, t0, nsteps, poses, dims, sa, st, sv);
+                        constexpr int NT = decltype(nt)::value;
+                        return sv.any() ? launch_small<UkfLayout<NT>>(ukf_small_kernel<NT, MODE, true>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv, c->ukf)
+                                        : launch_small<UkfLayout<NT>>(ukf_small_kernel<NT, MODE, false>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv, c->ukf);
                 });
 #endif
         return fail(ASLAM_ERR_UNSUPPORTED, "no kernel for this filter/size");
@@ -325,52 +315,6 @@ int clear_innovation(aslam_ctx *c)
         return ASLAM_OK;
 }
 
-/// the typed buffers of a large-state context, in this order (addresses follow from it)
-template <typename T> int alloc_large(aslam_ctx *c, LargeView<T> &lv)
-{
-        const size_t B = (size_t)c->cfg.batch, NP = (size_t)c->NP;
-        const LargePlan plan = large_plan(sizeof(T) == 4, c->NP, c->cfg.batch, c->cfg.batch, c->lh.knobs);
-        int rc = ASLAM_OK;
-        auto A_ = [&](int r) {
-                if (rc == ASLAM_OK)
-                        rc = r;
-        };
-        lv.NP = c->NP;
-        lv.xrows = c->cfg.filter == ASLAM_UKF ? 2 : 1; // vector rows behind the state rows of G: Y^T / z^T and the innovation (ukf_large.h)
-        A_(dev_alloc(c, &lv.P, B * NP * NP, c->owned));
-        c->largeP = lv.P;
-        A_(dev_alloc(c, &lv.G, B * NP * NP, c->owned));
-        A_(dev_alloc(c, &lv.S, B * NP * NP, c->owned));
-        A_(dev_alloc(c, &lv.Hc, B * (NP / 2) * 4, c->owned));
-        A_(dev_alloc(c, &lv.Y, B * NP, c->owned));
-        A_(dev_alloc(c, &lv.Linv, B * LARGE_NB_MAX * LB * LB, c->owned));
-        if (plan.need_Lpl)
-                A_(dev_alloc(c, &lv.Lpl, B * LPlanes::per_filter((int)NP), c->owned));
-        if (plan.need_Vw)
-                A_(dev_alloc(c, &lv.Vw, B * NP * NP, c->owned));
-        return rc;
-}
-
-#if ASLAM_HAVE_UKF
-/// HBM scratch of the large-state UKF chain: D, DZ ([NP][MP]), the propagated poses, the predicted mean and a few scalars per filter
-int ukf_large_alloc(aslam_ctx *c)
-{
-        const size_t B = (size_t)c->cfg.batch, NP = (size_t)c->NP;
-        const size_t MP = 2 * NP + 16; // >= 2 n + 5 rounded up to 16 for every n <= NP - 2
-        UkfLargeView &u = c->ukfl;
-        u.MP = (int)MP;
-        int rc = dev_alloc(c, &u.D, B * NP * MP, c->owned);
-        if (rc == ASLAM_OK)
-                rc = dev_alloc(c, &u.DZ, B * NP * MP, c->owned);
-        if (rc == ASLAM_OK)
-                rc = dev_alloc(c, &u.XP, B * 3 * MP, c->owned);
-        if (rc == ASLAM_OK)
-                rc = dev_alloc(c, &u.Xbar, B * NP, c->owned);
-        if (rc == ASLAM_OK)
-                rc = dev_alloc(c, &u.sc, B * 8, c->owned);
-        return rc;
-}
-#endif
 } // namespace
 
 extern "C" {
@@ -441,19 +385,15 @@ int aslam_create(const aslam_config *cfg, aslam_ctx **out)
         d.dim_cap = cfg->max_landmark_count;
         d.max_obs = cfg->max_obs;
         d.max_wait = cfg->max_wait;
-        const size_t B = (size_t)cfg->batch, NP = (size_t)c->NP;
+        const size_t B = (size_t)cfg->batch;
         int rc = ASLAM_OK;
-        auto A_ = [&](int r) {
+        auto take = [&](auto *&p, size_t per, bool = false) { // (the one error idiom here: the first failure stops every later allocation)
                 if (rc == ASLAM_OK)
-                        rc = r;
+                        rc = dev_alloc(c, &p, B * per, c->owned);
         };
-        A_(dev_alloc(c, &d.X, B * NP, c->owned));
-        A_(dev_alloc(c, &d.Z, B * NP, c->owned));
-        if (!large)
-                A_(dev_alloc(c, &d.P, B * NP * NP, c->owned));
-        else
-        {
-                A_(dev_alloc(c, &c->skipped, B, c->owned));
+        // what a large-state context owns where a single-CU context owns P: `skipped`, the streams of the stream groups, the typed view
+        auto take_large = [&]() {
+                take(c->skipped, 1);
                 c->lh.knobs = large_knobs_from_env();
                 for (hipStream_t &q : c->lh.aux)
                         if (hipStreamCreateWithFlags(&q, hipStreamNonBlocking) != hipSuccess)
@@ -463,34 +403,55 @@ int aslam_create(const aslam_config *cfg, aslam_ctx **out)
                 for (hipEvent_t &e : c->lh.ev_join)
                         if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess)
                                 rc = ASLAM_ERR_HIP;
-                A_(with_large_view(c, [&](auto &lv) { return alloc_large(c, lv); }));
-        }
-        A_(dev_alloc(c, &d.A, B * 2, c->owned));
-        A_(dev_alloc(c, &c->step_in, B * 3, c->owned));
+                with_large_view(c, [&](auto &lv) {
+                        const LargePlan plan = large_plan(c->cfg.dtype == ASLAM_F32, c->NP, c->cfg.batch, c->cfg.batch, c->lh.knobs);
+                        lv.NP = c->NP;
+                        lv.xrows = xrows;
+                        for_each_array(lv, [&](auto *&p, size_t per, bool) {
+                                const bool unused = (same_slot(p, lv.Lpl) && !plan.need_Lpl) || (same_slot(p, lv.Vw) && !plan.need_Vw);
+                                if (!unused)
+                                        take(p, per);
+                        });
+                        c->largeP = lv.P;
+                        return 0;
+                });
+        };
+        // Every view's arrays in the order of its for_each_array.  The order of the hipMalloc calls is as it was when the rates in profiles/ were
+        // measured (addresses follow from it): the large-state arrays come where P would, step_in ([3][B]) behind A
+        for_each_array(d, [&](auto *&p, size_t per, bool) {
+                if (large && same_slot(p, d.P))
+                        take_large();
+                else
+                        take(p, per);
+                if (same_slot(p, d.A))
+                        take(c->step_in, 3);
+        });
         d.step_in = c->step_in;
-        A_(dev_alloc(c, &d.n, B, c->owned));
-        A_(dev_alloc(c, &d.flags, B, c->owned));
-        A_(dev_alloc(c, &d.status, B, c->owned));
-        A_(dev_alloc(c, &d.sens, B * cfg->max_obs * 2, c->owned));
-        A_(dev_alloc(c, &d.sens_n, B, c->owned));
-        A_(dev_alloc(c, &d.wait_rb, B * cfg->max_wait * 2, c->owned));
-        A_(dev_alloc(c, &d.wait_cnt, B * cfg->max_wait, c->owned));
-        A_(dev_alloc(c, &d.wait_n, B, c->owned));
-        A_(dev_alloc(c, &c->params_dev, B, c->owned));
-        d.prm = c->params_dev;
+        c->params_dev = const_cast<aslam_params *>(d.prm);
         c->params.assign(B, aslam_params ASLAM_PARAMS_DEFAULT_INIT);
         if (rc == ASLAM_OK && hipMemcpy(c->params_dev, c->params.data(), sizeof(aslam_params) * B, hipMemcpyHostToDevice) != hipSuccess)
                 rc = fail(ASLAM_ERR_HIP, "hipMemcpy of the default parameters failed");
 #ifdef ASLAM_STAMPS
-        A_(dev_alloc(c, &d.dbg, 64 + 1024, c->owned)); // [64 ..): diagnostic builds, last front-end launch, 100 MHz ticks per workgroup
+        if (rc == ASLAM_OK) // [64 ..): diagnostic builds, last front-end launch, 100 MHz ticks per workgroup
+                rc = dev_alloc(c, &d.dbg, 64 + 1024, c->owned);
 #endif
 #if ASLAM_HAVE_UKF
-        if (rc == ASLAM_OK && cfg->filter == ASLAM_UKF)
-                rc = large ? ukf_large_alloc(c) : ukf_alloc(c);
+        if (cfg->filter == ASLAM_UKF)
+        { // HBM scratch of the UKF kernels; MP >= 2 n + 5 rounded up to 16 for every n the context takes
+                (large ? c->ukfl.MP : c->ukf.MP) = 2 * c->NP + 16;
+                if (large)
+                        for_each_array(c->ukfl, c->NP, take);
+                else
+                        for_each_array(c->ukf, c->NP, take);
+        }
 #else
         if (rc == ASLAM_OK && cfg->filter == ASLAM_UKF)
                 rc = fail(ASLAM_ERR_UNSUPPORTED, "library built without the UKF kernels");
 #endif
+        int scratch = 0; // a view that gains a zero-at-start array may need a larger SnapCtx::clear
+        for_each_scratch(c, [&](void *, size_t) { ++scratch; });
+        if (rc == ASLAM_OK && scratch > SNAP_CLEAR_MAX)
+                rc = fail(ASLAM_ERR_UNSUPPORTED, "more zero-at-start arrays than SnapCtx::clear holds (SNAP_CLEAR_MAX)");
         if (rc == ASLAM_OK)
                 rc = init_state(c);
         if (rc != ASLAM_OK)
@@ -999,8 +960,8 @@ int snap_reserve(aslam_ctx *c, size_t bytes)
         return ASLAM_OK;
 }
 
-/// the context side of a pack / unpack launch.  clear[]: the slot-wise scratch aslam_reset zeroes (init_state, init_P_large) -- G, S, Vw of
-/// the large path, D, DZ, Tc, K of the single-CU UKF -- and D, DZ of the large-state UKF, whose padding columns the weighted products read
+/// the context side of a pack / unpack launch.  clear[]: the slot-wise scratch aslam_reset zeroes, from the same list (for_each_scratch; at most
+/// SNAP_CLEAR_MAX entries in one context: G, S, Vw of the large path, D, DZ, Tc, K of the single-CU UKF, D, DZ of the large-state UKF)
 SnapCtx snap_ctx(aslam_ctx *c)
 {
         const DevView &d = c->dv;
@@ -1010,27 +971,11 @@ SnapCtx snap_ctx(aslam_ctx *c)
         s.n = d.n, s.flags = d.flags, s.status = d.status;
         s.sens = d.sens, s.sens_n = d.sens_n, s.wait_rb = d.wait_rb, s.wait_cnt = d.wait_cnt, s.wait_n = d.wait_n;
         s.innov = c->innov;
-        const size_t NP = (size_t)c->NP;
         int k = 0;
-        auto add = [&](void *p, size_t bytes) {
-                if (p)
+        for_each_scratch(c, [&](void *p, size_t bytes) {
+                if (k < SNAP_CLEAR_MAX) // (aslam_create refuses a context with more)
                         s.clear[k] = static_cast<char *>(p), s.clear_bytes[k] = bytes, ++k;
-        };
-        if (c->large)
-                with_large_view(c, [&](auto &lv) {
-                        const size_t e = sizeof(*lv.G);
-                        add(lv.G, NP * NP * e), add(lv.S, NP * NP * e), add(lv.Vw, NP * NP * e);
-                        return 0;
-                });
-#if ASLAM_HAVE_UKF
-        if (c->ukf.D)
-        {
-                const size_t MP = (size_t)c->ukf.MP;
-                add(c->ukf.D, NP * MP * 8), add(c->ukf.DZ, NP * MP * 8), add(c->ukf.Tc, NP * NP * 8), add(c->ukf.K, NP * NP * 8);
-        }
-        if (c->ukfl.D)
-                add(c->ukfl.D, NP * (size_t)c->ukfl.MP * 8), add(c->ukfl.DZ, NP * (size_t)c->ukfl.MP * 8);
-#endif
+        });
         return s;
 }
 } // namespace
@@ -1265,10 +1210,11 @@ int aslam_debug_snapshot_rate(aslam_ctx *c, void *dev_buf, int64_t cap_bytes, in
         const SnapCtx sc = snap_ctx(c);
         const SnapDesc *desc = reinterpret_cast<const SnapDesc *>(c->snap_dev);
         const int count = c->snap_count;
-        const size_t NP = (size_t)c->NP;
         char *blob = static_cast<char *>(dev_buf);
+        auto bytes = [&](auto m) { return per_filter(c->dv, m) * sizeof(*(c->dv.*m)); }; // (P: the large path's has the same shape)
         info[0] = total;
-        info[1] = (int64_t)count * (int64_t)(8 * NP * NP + 16 * NP + 8 * (size_t)sc.max_obs + 12 * (size_t)sc.max_wait);
+        info[1] = (int64_t)count * (int64_t)(bytes(&DevView::X) + bytes(&DevView::Z) + bytes(&DevView::P) + bytes(&DevView::sens) +
+                                             bytes(&DevView::wait_rb) + bytes(&DevView::wait_cnt));
         info[2] = 0;
         for (int k = 0; k < SNAP_CLEAR_MAX; ++k)
                 info[2] += sc.clear[k] ? (int64_t)count * (int64_t)sc.clear_bytes[k] : 0;
@@ -1309,20 +1255,20 @@ int aslam_debug_large(aslam_ctx *c, int traj, int which, double *out, int64_t ca
                 return fail(ASLAM_ERR_UNSUPPORTED, "aslam_debug_large: large-state contexts only");
         if (sync_ctx(c) != ASLAM_OK)
                 return ASLAM_ERR_HIP;
-        const size_t NP = c->NP;
-        const size_t cnt = which < 2 ? NP * NP : which == 2 ? (size_t)LARGE_NB_MAX * LB * LB : NP;
-        if ((int64_t)cnt > cap)
-                return fail(ASLAM_ERR_ARG, "aslam_debug_large: buffer too small");
         return with_large_view(c, [&](auto &lv) -> int {
+                using V = std::remove_reference_t<decltype(lv)>;
                 using T = std::remove_reference_t<decltype(*lv.G)>;
+                T *V::*const m = which == 0 ? &V::G : which == 1 ? &V::S : &V::Linv;
+                const size_t cnt = which == 3 ? per_filter(lv, &V::Y) : per_filter(lv, m);
+                if ((int64_t)cnt > cap)
+                        return fail(ASLAM_ERR_ARG, "aslam_debug_large: buffer too small");
                 if (which == 3)
                 {
-                        HIP_TRY(hipMemcpy(out, lv.Y + traj * NP, cnt * sizeof(double), hipMemcpyDeviceToHost));
+                        HIP_TRY(hipMemcpy(out, lv.Y + traj * cnt, cnt * sizeof(double), hipMemcpyDeviceToHost));
                         return ASLAM_OK;
                 }
-                const T *src = which == 0 ? lv.G + traj * NP * NP : which == 1 ? lv.S + traj * NP * NP : lv.Linv + traj * cnt;
                 std::vector<T> tmp(cnt);
-                HIP_TRY(hipMemcpy(tmp.data(), src, cnt * sizeof(T), hipMemcpyDeviceToHost));
+                HIP_TRY(hipMemcpy(tmp.data(), lv.*m + traj * cnt, cnt * sizeof(T), hipMemcpyDeviceToHost));
                 std::copy(tmp.begin(), tmp.end(), out);
                 return ASLAM_OK;
         });
@@ -1334,13 +1280,11 @@ int aslam_debug_ukf(aslam_ctx *c, int traj, int which, double *out, int *rows, i
 {
         if (sync_ctx(c) != ASLAM_OK)
                 return ASLAM_ERR_HIP;
-        const size_t NP = c->NP, MP = c->ukf.MP;
-        const double *src = which == 0 ? c->ukf.D + traj * NP * MP : which == 1 ? c->ukf.DZ + traj * NP * MP
-                            : which == 2 ? c->ukf.Tc + traj * NP * NP : c->ukf.K + traj * NP * NP;
-        const size_t cnt = which < 2 ? NP * MP : NP * NP;
-        *rows = (int)NP;
-        *cols = which < 2 ? (int)MP : (int)NP;
-        HIP_TRY(hipMemcpy(out, src, cnt * sizeof(double), hipMemcpyDeviceToHost));
+        double *UkfView::*const m = which == 0 ? &UkfView::D : which == 1 ? &UkfView::DZ : which == 2 ? &UkfView::Tc : &UkfView::K;
+        const size_t cnt = per_filter(c->ukf, m, c->NP);
+        *rows = c->NP;
+        *cols = (int)(cnt / (size_t)c->NP);
+        HIP_TRY(hipMemcpy(out, c->ukf.*m + traj * cnt, cnt * sizeof(double), hipMemcpyDeviceToHost));
         return ASLAM_OK;
 }
 #endif
@@ -1495,9 +1439,9 @@ int aslam_get_launch_info(aslam_ctx *c, int *stream_groups, int *chol_resident, 
         if (stream_groups)
                 *stream_groups = c->large ? c->lh.last_groups : 0;
         if (chol_resident)
-                *chol_resident = c->large && c->lh.last_plan.chain == LargeChain::F32_RESIDENT;
+                *chol_resident = c->large && c->lh.last_resident;
         if (launches_per_callback)
-                *launches_per_callback = c->large ? c->lh.last_plan.launches : 1;
+                *launches_per_callback = c->large ? c->lh.last_launches : 1;
         return ASLAM_OK;
 }
 

@@ -37,7 +37,7 @@ constexpr int LARGE_WAIT_CAP = 2048; // wait-list (LDS)
 constexpr int LARGE_NP_MAX = 1088;   // 17 blocks of 64: n <= 1087
 constexpr int LARGE_NB_MAX = LARGE_NP_MAX / LB;
 
-template <typename T> struct LargeView
+template <typename T> struct LargeView // (its arrays, their sizes per filter and which must start zero: for_each_array below, behind LPlanes)
 {
         int NP;     // row stride, multiple of LB
         double *P;  // [B][NP][NP]  always binary64 (fp32 mode: only G, S, L, V and the MFMA products are binary32)
@@ -122,6 +122,21 @@ struct LPlanes
         /// plane 0 of block (k, j) (row stride NP, plane stride NP * NP)
         __host__ __device__ unsigned short *block(int b, int NP, int k, int j) const { return Lq(b, NP) + (size_t)(64 * k) * NP + 64 * j; }
 };
+/// the per-filter arrays of a LargeView, in allocation order; G, S and Vw must be zero when a filter starts: the kernels rely on padding they
+/// never write (see for_each_array(DevView &) in small_common.h).  Vw and Lpl are null in contexts whose plan does not need them
+template <typename T, typename F> void for_each_array(LargeView<T> &v, F &&f)
+{
+        const size_t np = (size_t)v.NP;
+        f(v.P, np * np, false);
+        f(v.G, np * np, true);
+        f(v.S, np * np, true);
+        f(v.Hc, (np / 2) * 4, false);
+        f(v.Y, np, false);
+        f(v.Linv, (size_t)LARGE_NB_MAX * LB * LB, false);
+        f(v.Lpl, LPlanes::per_filter(v.NP), false);
+        f(v.Vw, np * np, true);
+}
+
 /// position of column c (0 .. 63) of a block inside a permuted plane row: 32 h + 8 g + 4 w + r holds column 32 h + 16 w + 4 g + r
 __host__ __device__ __forceinline__ int lplane_pos(int c)
 {

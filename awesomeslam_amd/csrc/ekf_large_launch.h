@@ -1,6 +1,8 @@
 // ekf_large_launch.h -- host side of the large-state EKF (n > 143, or fp32), included by aslam_core.hip: the environment knobs, the launch
 // plan (which of the four kernel chains a callback runs: large_plan() is the ONE place that decides it -- aslam_create, the launcher and
 // aslam_kernel_info read its result), views shifted to a group of filters, the chain launcher and the split of a batch into stream groups.
+// The list of the arrays a filter owns is for_each_array(), next to each view's struct (DevView: small_common.h, LargeView: ekf_large.h):
+// to add an array, add the member and one line there -- aslam_create, shifted(), aslam_reset and the clear list of restore follow.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -103,27 +105,53 @@ struct LargeHost
         LargeKnobs knobs;
         hipStream_t aux[LARGE_GROUPS_MAX - 1] = {};
         hipEvent_t ev_fork = nullptr, ev_join[LARGE_GROUPS_MAX - 1] = {};
-        int last_groups = 0;     // stream groups that received work (1 = the caller's stream alone; 0 = nothing launched yet)
-        LargePlan last_plan = {}; // the plan of that launch
+        int last_groups = 0;        // stream groups that received work (1 = the caller's stream alone; 0 = nothing launched yet)
+        int last_launches = 0;      // kernel launches per callback and stream group of that launch (large_stats included)
+        bool last_resident = false; // that launch ran LargeChain::F32_RESIDENT
 };
 
-// the kernels index the filter through blockIdx: a group of filters starting at b0 gets views shifted to b0
-inline DevView shifted(DevView d, size_t b, bool trace)
+/// which filters a launch covers: one trajectory (MODE_STEP with sa.traj >= 0; the views then start at it, so the kernels get traj = 0) or the
+/// whole batch of B (sa.traj < 0 is the batched step)
+struct LaunchSlice
 {
-        const size_t np = (size_t)d.NP, T_ = (size_t)d.T;
-        d.X += b * np;
-        d.Z += b * np;
-        d.A += 2 * b;
-        d.n += b;
-        d.flags += b;
-        d.status += b;
-        d.sens += b * (size_t)d.max_obs * 2;
-        d.sens_n += b;
-        d.wait_rb += b * (size_t)d.max_wait * 2;
-        d.wait_cnt += b * (size_t)d.max_wait;
-        d.wait_n += b;
-        d.prm += b;
-        d.step_in += b; // [3][B]: the stride stays the whole batch
+        int first, count;
+        StepArgs sa;
+};
+template <int MODE> LaunchSlice launch_slice(StepArgs sa, int B)
+{
+        if (MODE != MODE_STEP || sa.traj < 0)
+                return {0, B, sa};
+        const int first = sa.traj;
+        sa.traj = 0;
+        return {first, 1, sa};
+}
+
+// the kernels index the filter through blockIdx: a group of filters starting at b gets views whose per-filter arrays (for_each_array next to
+// each view's struct) start there.  Arrays the context does not own stay null
+struct ShiftBy
+{
+        size_t b;
+        template <typename T> void operator()(T *&p, size_t per, bool) const
+        {
+                if (p)
+                        p += b * per;
+        }
+};
+
+/// LargeView<T>, UkfLargeView (np: the NP a UKF view does not carry itself).  A DevView has more than its arrays to shift: shifted_dev
+template <typename V, typename... NP> V shifted(V v, size_t b, NP... np)
+{
+        static_assert(!std::is_same<V, DevView>::value && !std::is_same<V, StatsView>::value, "shifted_dev / shifted_stats");
+        for_each_array(v, np..., ShiftBy{b});
+        return v;
+}
+
+/// a DevView: its per-filter arrays, step_in ([3][B]: the stride stays the whole batch) and, in replay, the bound trace ([B][T]-shaped)
+inline DevView shifted_dev(DevView d, size_t b, bool trace)
+{
+        const size_t T_ = (size_t)d.T;
+        for_each_array(d, ShiftBy{b});
+        d.step_in += b;
         if (trace)
         {
                 d.tr_pose += 2 * b * T_;
@@ -137,24 +165,8 @@ inline DevView shifted(DevView d, size_t b, bool trace)
         return d;
 }
 
-template <typename T> LargeView<T> shifted(LargeView<T> v, size_t b)
-{
-        const size_t np = (size_t)v.NP;
-        v.P += b * np * np;
-        v.G += b * np * np;
-        v.S += b * np * np;
-        v.Hc += b * (np / 2) * 4;
-        v.Linv += b * LARGE_NB_MAX * LB * LB;
-        if (v.Lpl)
-                v.Lpl += b * LPlanes::per_filter((int)np);
-        if (v.Vw)
-                v.Vw += b * np * np;
-        v.Y += b * np;
-        return v;
-}
-
 /// the per-callback arrays are [B][nsteps]-shaped, the last-callback record [B][2]
-inline StatsView shifted(StatsView sv, size_t b, int nsteps)
+inline StatsView shifted_stats(StatsView sv, size_t b, int nsteps)
 {
         if (sv.nis)
                 sv.nis += b * (size_t)nsteps;
@@ -179,6 +191,26 @@ template <typename T> struct LargeGroup
         StatsView sv; // statistics asked for with this launch (all null: none, and no large_stats launch)
 };
 
+/// The blocked left-looking loop over the NB block columns of a view: the one-wave factorisation of the diagonal block (with its inverse), then
+/// the panel launch that eliminates the block column.  s_only = 0: over the stacked [S; G; vector rows] (the factor-and-solve of a callback);
+/// s_only = 1: over S alone, where the last block column has nothing below it (last_panel = false).  Returns the launches issued
+template <typename T>
+int launch_left_looking(const DevView &dv, const LargeView<T> &v, int NB, int gb, int *skip, hipStream_t st, int s_only, bool last_panel)
+{
+        int count = 0;
+        for (int k = 0; k < NB; ++k)
+        {
+                hipLaunchKernelGGL(large_potrf_inv_tiles<T>, dim3(gb), dim3(256), 0, st, dv, v, k, skip);
+                ++count;
+                if (k + 1 < NB || last_panel)
+                {
+                        hipLaunchKernelGGL(large_update_panel<T>, dim3(((s_only ? NB : 2 * NB) - k) / 2, 1, gb), dim3(256), 0, st, dv, v, k, s_only, skip);
+                        ++count;
+                }
+        }
+        return count;
+}
+
 /// callback s of one group: front end + predict, G, S, blocked factorisation of [S; G; Y^T], P -= V V^T, X += V q
 template <typename T, int MODE>
 void launch_large_chain(const LargePlan &plan, const LargeGroup<T> &g, size_t lds, int64_t t0, int s, int nsteps, StepArgs sa)
@@ -193,11 +225,7 @@ void launch_large_chain(const LargePlan &plan, const LargeGroup<T> &g, size_t ld
         const dim3 syrk_grid(8 * (ntile * (ntile + 1) / 2) * ((gb + 7) / 8));
         if constexpr (sizeof(T) == 8)
         { // F64_LEFT
-                for (int k = 0; k < NB; ++k)
-                {
-                        hipLaunchKernelGGL(large_potrf_inv_tiles<T>, dim3(gb), dim3(256), 0, g.st, g.dv, g.v, k, g.skip);
-                        hipLaunchKernelGGL(large_update_panel<T>, dim3((2 * NB - k) / 2, 1, gb), dim3(256), 0, g.st, g.dv, g.v, k, 0, g.skip);
-                }
+                launch_left_looking(g.dv, g.v, NB, gb, g.skip, g.st, 0, true);
                 hipLaunchKernelGGL(large_syrk<T>, syrk_grid, dim3(256), 0, g.st, g.dv, g.v, gb, g.skip);
                 hipLaunchKernelGGL((large_x_update<T, MODE>), dim3((NP + 3) / 4, gb), dim3(256), 0, g.st, g.dv, g.v, s, nsteps, g.poses, g.dims, g.skip);
                 if (g.sv.any())
@@ -228,12 +256,7 @@ void launch_large_chain(const LargePlan &plan, const LargeGroup<T> &g, size_t ld
                         vv.G = g.v.Vw; // V is there, row n = q included (large_right_step has solved the rows of G on its way)
                         break;
                 default: // F32_LEFT
-                        for (int k = 0; k < NB; ++k)
-                        {
-                                hipLaunchKernelGGL(large_potrf_inv_tiles<T>, dim3(gb), dim3(256), 0, g.st, g.dv, g.v, k, g.skip);
-                                if (k + 1 < NB)
-                                        hipLaunchKernelGGL(large_update_panel<T>, dim3((NB - k) / 2, 1, gb), dim3(256), 0, g.st, g.dv, g.v, k, 1, g.skip);
-                        }
+                        launch_left_looking(g.dv, g.v, NB, gb, g.skip, g.st, 1, false);
                         hipLaunchKernelGGL(large_trsm_pipe<LARGE_NB_MAX>, dim3(8 * ((gb + 7) / 8) * NB), dim3(256), 0, g.st, g.dv, g.v, gb, g.skip);
                 }
                 if (plan.syrk_running)
@@ -253,7 +276,7 @@ void launch_large_chain(const LargePlan &plan, const LargeGroup<T> &g, size_t ld
 
 /// `nsteps` callbacks of a large-state context: one trajectory (MODE_STEP with sa.traj >= 0) or the whole batch, which from max(32, 8 x groups)
 /// filters on is split into stream groups.  The enqueue order (callbacks outermost, groups innermost) is what the rates were measured with.
-/// `sv`: statistics to write (one launch more per callback, reported in last_plan.launches), all null for none
+/// `sv`: statistics to write (one launch more per callback, reported in last_launches), all null for none
 template <int MODE, typename T>
 hipError_t launch_large(LargeHost &h, const DevView &dv, const LargeView<T> &lv, int *skipped, int64_t t0, int nsteps, double *poses, int32_t *dims,
                         StepArgs sa, hipStream_t st, StatsView sv = {})
@@ -261,22 +284,21 @@ hipError_t launch_large(LargeHost &h, const DevView &dv, const LargeView<T> &lv,
         const size_t lds = LargeLds::bytes(dv.NP);
         if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(large_frontend_kernel<T, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
                 return e;
-        const bool one = MODE == MODE_STEP && sa.traj >= 0; // sa.traj < 0: the batched step
-        const int first = one ? sa.traj : 0, Bz = one ? 1 : dv.B;
-        sa.traj = one ? 0 : sa.traj; // (the views of the group start at the trajectory)
+        const LaunchSlice sl = launch_slice<MODE>(sa, dv.B);
+        const int first = sl.first, Bz = sl.count;
         const LargePlan plan = large_plan(sizeof(T) == 4, dv.NP, dv.B, Bz, h.knobs);
         const bool split = Bz >= std::max(32, 8 * h.knobs.groups); // (one group below 32 filters, as with the former default of four groups)
         const int NG = split ? h.knobs.groups : 1;
         const int per = split ? ((Bz + NG - 1) / NG + 7) & ~7 : Bz; // multiples of 8: large_syrk deals filters to the 8 XCDs
         LargeGroup<T> g[LARGE_GROUPS_MAX];
-        h.last_plan = plan;
-        h.last_plan.launches += sv.any() ? 1 : 0; // large_stats
+        h.last_launches = plan.launches + (sv.any() ? 1 : 0); // large_stats
+        h.last_resident = plan.chain == LargeChain::F32_RESIDENT;
         h.last_groups = 0;
         for (int q = 0; q < NG; ++q)
         {
                 const int o = std::min(q * per, Bz);
                 const size_t b0 = (size_t)(first + o);
-                g[q] = {shifted(dv, b0, MODE == MODE_REPLAY), shifted(lv, b0), skipped + b0, poses, dims, std::min(per, Bz - o), q == 0 ? st : h.aux[q - 1], shifted(sv, b0, nsteps)};
+                g[q] = {shifted_dev(dv, b0, MODE == MODE_REPLAY), shifted(lv, b0), skipped + b0, poses, dims, std::min(per, Bz - o), q == 0 ? st : h.aux[q - 1], shifted_stats(sv, b0, nsteps)};
                 if (MODE == MODE_REPLAY && poses)
                         g[q].poses += b0 * (size_t)nsteps * 3;
                 if (MODE == MODE_REPLAY && dims)
@@ -291,7 +313,7 @@ hipError_t launch_large(LargeHost &h, const DevView &dv, const LargeView<T> &lv,
         for (int s = 0; s < nsteps; ++s)
                 for (int q = 0; q < NG; ++q)
                         if (g[q].nb > 0)
-                                launch_large_chain<T, MODE>(plan, g[q], lds, t0, s, nsteps, sa);
+                                launch_large_chain<T, MODE>(plan, g[q], lds, t0, s, nsteps, sl.sa);
         for (int q = 1; q < NG && e == hipSuccess; ++q)
                 if ((e = hipEventRecord(h.ev_join[q - 1], h.aux[q - 1])) == hipSuccess)
                         e = hipStreamWaitEvent(st, h.ev_join[q - 1], 0);

@@ -77,6 +77,31 @@ struct DevView
         unsigned long long *dbg; // diagnostic builds only (-DASLAM_STAMPS): per-phase cycle sums of workgroup 0
 };
 
+/// The per-filter arrays of a DevView (host side): f(pointer, elements per filter, zero) once per array, in the order aslam_create allocates
+/// them.  `zero` marks scratch that must be zero when a filter starts; there is none here (what aslam_reset writes into these arrays is the
+/// reference's initialize(), not a table).  This function and its three siblings (LargeView: ekf_large.h, UkfView: ukf_small.h, UkfLargeView:
+/// ukf_large.h) are the ONE list of what a filter owns: allocation, the views shifted to a filter, reset, the clear list of restore and the
+/// diagnostic getters are all derived from them, so a new array is a member of its view and one line in that view's function.
+/// Not per-filter slabs, and handled where they are used: the bound trace ([B][T]-shaped, not owned, shifted for replay only), step_in
+/// ([3][B]: the stride is the batch), dbg (one block per context) and StatsView (its strides depend on nsteps).
+template <typename F> void for_each_array(DevView &d, F &&f)
+{
+        const size_t np = (size_t)d.NP, mo = (size_t)d.max_obs, mw = (size_t)d.max_wait;
+        f(d.X, np, false);
+        f(d.Z, np, false);
+        f(d.P, np * np, false); // (null in a large-state context: LargeView::P)
+        f(d.A, 2, false);
+        f(d.n, 1, false);
+        f(d.flags, 1, false);
+        f(d.status, 1, false);
+        f(d.sens, mo * 2, false);
+        f(d.sens_n, 1, false);
+        f(d.wait_rb, mw * 2, false);
+        f(d.wait_cnt, mw, false);
+        f(d.wait_n, 1, false);
+        f(d.prm, 1, false);
+}
+
 #ifdef ASLAM_STAMPS
 #define ASLAM_STAMP(i)                                                                                                 \
         do                                                                                                             \

@@ -40,6 +40,18 @@ struct UkfLargeView
         double *sc;   // [B][8]       vx, az, dt of the callback (front end), 1 / (1 - q.q) (ukf_large_gain)
 };
 
+/// the per-filter arrays of a UkfLargeView, in allocation order (NP: the context's; see for_each_array(DevView &) in small_common.h).  D and DZ
+/// must be zero when a filter starts: the weighted products read their padding columns (ukf_large_wabt)
+template <typename F> void for_each_array(UkfLargeView &u, int NP, F &&f)
+{
+        const size_t np = (size_t)NP, mp = (size_t)u.MP;
+        f(u.D, np * mp, true);
+        f(u.DZ, np * mp, true);
+        f(u.XP, 3 * mp, false);
+        f(u.Xbar, np, false);
+        f(u.sc, 8, false);
+}
+
 /// updateWeights (ukf.h:73-81: binary32 lambda and weight) and w = sqrt(lambda + N + 2) (ukf.cpp:284), as ukf_small.h forms them
 struct UkfWeights
 {

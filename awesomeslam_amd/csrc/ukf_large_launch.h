@@ -1,6 +1,7 @@
 // ukf_large_launch.h -- host side of the large-state UKF (ukf_large.h), included by aslam_core.hip: the launch plan (ukf_large_plan() is the ONE
 // place that says how many launches a callback is -- the launcher walks it, aslam_get_launch_info and aslam_kernel_info report it), views
-// shifted to a trajectory, and the chain launcher.  One stream: the caller's (no stream groups on this path).
+// shifted to a trajectory, and the chain launcher.  One stream: the caller's (no stream groups on this path).  The list of the arrays a filter
+// owns on this path is for_each_array(UkfLargeView &) in ukf_large.h: to add an array, add the member and one line there.
 #pragma once
 
 #include "ekf_large_launch.h"
@@ -35,17 +36,6 @@ inline UkfLargePlan ukf_large_plan(int NP)
         return p;
 }
 
-inline UkfLargeView shifted(UkfLargeView v, size_t b, int NP)
-{
-        const size_t np = (size_t)NP, mp = (size_t)v.MP;
-        v.D += b * np * mp;
-        v.DZ += b * np * mp;
-        v.XP += b * 3 * mp;
-        v.Xbar += b * np;
-        v.sc += b * 8;
-        return v;
-}
-
 /// `nsteps` callbacks of a large-state UKF context: one trajectory (MODE_STEP with sa.traj >= 0) or the whole batch
 template <int MODE>
 hipError_t launch_ukf_large(LargeHost &h, const DevView &dv0, const LargeView<double> &lv0, const UkfLargeView &uv0, int *skipped0, int64_t t0, int nsteps,
@@ -55,38 +45,27 @@ hipError_t launch_ukf_large(LargeHost &h, const DevView &dv0, const LargeView<do
         const size_t lds = LargeLds::bytes(NP);
         if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(ukf_large_frontend_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
                 return e;
-        const bool one = MODE == MODE_STEP && sa.traj >= 0; // sa.traj < 0: the batched step
-        const size_t first = one ? (size_t)sa.traj : 0;
-        const int gb = one ? 1 : dv0.B;
-        sa.traj = one ? 0 : sa.traj; // (the views start at the trajectory)
-        const DevView dv = shifted(dv0, first, MODE == MODE_REPLAY);
+        const LaunchSlice sl = launch_slice<MODE>(sa, dv0.B);
+        const size_t first = (size_t)sl.first;
+        const int gb = sl.count;
+        const DevView dv = shifted_dev(dv0, first, MODE == MODE_REPLAY);
         const LargeView<double> lv = shifted(lv0, first);
         const UkfLargeView uv = shifted(uv0, first, NP);
         int *skip = skipped0 + first;
-        const StatsView sv = shifted(sv0, first, nsteps); // statistics to write (large_stats: one launch more per callback), all null for none
+        const StatsView sv = shifted_stats(sv0, first, nsteps); // statistics to write (large_stats: one launch more per callback), all null for none
         const UkfLargePlan plan = ukf_large_plan(NP);
         const int NB = plan.NB;
         const int ntile = (NP + 127) / 128;
         const int fgroups = (gb + 7) / 8; // ukf_large_wabt and large_syrk deal filters to the 8 XCDs
-        h.last_plan = {};
-        h.last_plan.chain = LargeChain::F64_LEFT;
-        h.last_plan.launches = plan.launches + (sv.any() ? 1 : 0);
+        h.last_launches = plan.launches + (sv.any() ? 1 : 0);
+        h.last_resident = false;
         h.last_groups = 1;
         for (int s = 0; s < nsteps; ++s)
         {
                 int count = 0;
-                hipLaunchKernelGGL((ukf_large_frontend_kernel<MODE>), dim3(gb), dim3(SMALL_WG), lds, st, dv, lv, uv, t0 + s, s, nsteps, poses, dims, sa, skip);
+                hipLaunchKernelGGL((ukf_large_frontend_kernel<MODE>), dim3(gb), dim3(SMALL_WG), lds, st, dv, lv, uv, t0 + s, s, nsteps, poses, dims, sl.sa, skip);
                 count += plan.frontend;
-                for (int k = 0; k < NB; ++k) // L = chol(P) in S
-                {
-                        hipLaunchKernelGGL(large_potrf_inv_tiles<double>, dim3(gb), dim3(256), 0, st, dv, lv, k, skip);
-                        ++count;
-                        if (k + 1 < NB)
-                        {
-                                hipLaunchKernelGGL(large_update_panel<double>, dim3((NB - k) / 2, 1, gb), dim3(256), 0, st, dv, lv, k, 1, skip);
-                                ++count;
-                        }
-                }
+                count += launch_left_looking(dv, lv, NB, gb, skip, st, 1, false); // L = chol(P) in S
                 hipLaunchKernelGGL(ukf_large_sigma_pose, dim3(gb), dim3(256), 0, st, dv, lv, uv, skip);
                 hipLaunchKernelGGL(ukf_large_points, dim3(NP / 2, gb), dim3(256), 0, st, dv, lv, uv, skip);
                 count += plan.sigma;
@@ -95,12 +74,7 @@ hipError_t launch_ukf_large(LargeHost &h, const DevView &dv0, const LargeView<do
                         hipLaunchKernelGGL(ukf_large_wabt, dim3(8 * ukf_wabt_tiles(NP, mode) * fgroups), dim3(256), 0, st, dv, lv, uv, mode, gb, skip);
                         ++count;
                 }
-                for (int k = 0; k < NB; ++k) // S+ = L L^T, W = Tc L^-T, q = L^-1 z, t = L^-1 (Z - Zpred)
-                {
-                        hipLaunchKernelGGL(large_potrf_inv_tiles<double>, dim3(gb), dim3(256), 0, st, dv, lv, k, skip);
-                        hipLaunchKernelGGL(large_update_panel<double>, dim3((2 * NB - k) / 2, 1, gb), dim3(256), 0, st, dv, lv, k, 0, skip);
-                        count += 2;
-                }
+                count += launch_left_looking(dv, lv, NB, gb, skip, st, 0, true); // S+ = L L^T, W = Tc L^-T, q = L^-1 z, t = L^-1 (Z - Zpred)
                 hipLaunchKernelGGL((ukf_large_gain<MODE>), dim3((NP + 3) / 4, gb), dim3(256), 0, st, dv, lv, uv, s, nsteps, poses, dims, skip);
                 hipLaunchKernelGGL(large_syrk<double>, dim3(8 * (ntile * (ntile + 1) / 2) * fgroups), dim3(256), 0, st, dv, lv, gb, skip);
                 hipLaunchKernelGGL(ukf_large_rank1, dim3((NP + 3) / 4, gb), dim3(256), 0, st, dv, lv, uv, skip);

@@ -35,6 +35,17 @@ struct UkfView
         double *K;  // [B][NP][NP]
 };
 
+/// the per-filter arrays of a UkfView, in allocation order (NP: the context's; see for_each_array(DevView &) in small_common.h).  All four must
+/// be zero when a filter starts: the kernels rely on never-written padding staying zero
+template <typename F> void for_each_array(UkfView &u, int NP, F &&f)
+{
+        const size_t np = (size_t)NP, mp = (size_t)u.MP;
+        f(u.D, np * mp, true);
+        f(u.DZ, np * mp, true);
+        f(u.Tc, np * np, true);
+        f(u.K, np * np, true);
+}
+
 template <int NT> struct UkfLayout
 {
         typedef SmallLayout<NT> LY;

@@ -209,8 +209,12 @@ def test_fork_and_permute(case, built):
 
 
 # ---- 4. dirty slots ----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case,big,small", [("ekf-L64", 64, 8), ("ukf-L64", 64, 8), ("ekf-L80-f64", 80, 80), ("ekf-L80-f32", 80, 80),
-                                            ("ukf-L80-large", 80, 80)])
+# (case, L of the trace that dirties the slots, L of the trace they then run): the three large-state chains at n = 163 (NP = 192: more than one
+# 64-block) and the two single-CU families
+DIRTY = [("ekf-L64", 64, 8), ("ukf-L64", 64, 8), ("ekf-L80-f64", 80, 80), ("ekf-L80-f32", 80, 80), ("ukf-L80-large", 80, 80)]
+
+
+@pytest.mark.parametrize("case,big,small", DIRTY)
 def test_dirty_slots(case, big, small, built):
     """Slots that have run the big trace to its final n receive records of a SMALLER n (cut at k = 21 in a context of this configuration)
     and continue their trace exactly as a freshly created context restored from the same blob does."""
@@ -245,6 +249,55 @@ def test_dirty_slots(case, big, small, built):
     assert df[:, -1].tolist() == [N_FINAL[small]] * 3
     if big == small:  # (the same configuration as test 1: the continuation is context A's, too)
         assert np.array_equal(pf, reference(case, 21)[1])
+
+
+@pytest.mark.parametrize("case,big,small", DIRTY)
+def test_reset_equals_a_fresh_context(case, big, small, built):
+    """A context that has run the big trace to its final n and is reset() replays the small trace exactly as a freshly created context does:
+    reset and create leave the same state AND the same scratch (one list of the arrays that must start zero serves both, and restore).
+    Where big == small the second run takes the same trace in filter order [2, 0, 1], so every slot reruns with ANOTHER filter's stale
+    scratch; a rerun of the same trace would find the values it is about to write."""
+    tr_small = trace(small, trace(big).max_obs)
+    if big == small:
+        tr_small = tr_small.select([2, 0, 1])
+
+    def replay_small(core):
+        core.set_trace(tr_small)
+        pg, dg = run(core, 0, T)
+        out = (pg, dg, [final(core, b) for b in range(3)], core.snapshot())
+        status = [core.status(b) for b in range(3)]
+        core.close()
+        return out + (status,)
+
+    pf, df, ff, sf, stf = replay_small(make(case))
+    core = make(case)
+    core.set_trace(trace(big))
+    run(core, 0, T)
+    assert [core.dim(b) for b in range(3)] == [N_FINAL[big]] * 3
+    core.reset()
+    assert [core.dim(b) for b in range(3)] == [3] * 3
+    pr, dr, fr, sr, st_r = replay_small(core)
+    assert stf == [0] * 3 and st_r == [0] * 3
+    assert np.array_equal(pr, pf) and np.array_equal(dr, df)
+    assert all(same(a, b) for a, b in zip(fr, ff)) and sr.tobytes() == sf.tobytes()
+    assert df[:, -1].tolist() == [N_FINAL[small]] * 3
+
+
+# aslam_get_layout of the eight CASES at batch 3 (max_obs of the case's trace, max_wait 512): (padded dimension, HBM bytes).  The values are
+# those of the commit before the arrays were allocated from one list per view; the list must allocate what the hand-written calls did.
+LAYOUT = {
+    "ekf-L8": (32, 45120), "ekf-L20": (80, 176736), "ekf-L64": (144, 524928), "ukf-L8": (32, 217152), "ukf-L64": (144, 3621504),
+    "ekf-L80-f64": (192, 4369164), "ekf-L80-f32": (192, 3754764), "ukf-L80-large": (192, 8089164),
+}
+
+
+@pytest.mark.parametrize("case", list(CASES))
+def test_allocation_is_unchanged(case, built):
+    core = make(case)
+    got = core.layout()
+    core.close()
+    print(f"layout {case}: {got}")
+    assert got == LAYOUT[case]
 
 
 # ---- 5. migration ------------------------------------------------------------------------------------------------------------------
