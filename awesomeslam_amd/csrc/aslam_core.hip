@@ -1462,10 +1462,10 @@ int aslam_kernel_info(aslam_ctx *c, char *name, int name_cap, int *grid, int *bl
                                       ukf_large_plan(c->NP).launches);
                 else
 #endif
-                if (plan.chain == LargeChain::F32_RESIDENT) // (launches 3 - 5 are named; the X update is launch 6)
-                        std::snprintf(buf, sizeof(buf), "%s + %s + large_syrk_bf16x3 (%d-launch chain per callback, %d stream groups)",
+                if (plan.chain == LargeChain::F32_RESIDENT) // (the Cholesky, the TRSM and the syrk are named; the X update is launch 5, in front of the syrk, with the border, else launch 6)
+                        std::snprintf(buf, sizeof(buf), "%s + %s + large_syrk_bf16x3%s (%d-launch chain per callback, %d stream groups)",
                                       plan.chol16 ? "large_chol_bf16" : "large_chol_resident", plan.trsm16 ? "large_trsm_bf16" : "large_trsm_pipe<17>",
-                                      plan.launches, c->lh.knobs.groups);
+                                      plan.border ? " + border" : "", plan.launches, c->lh.knobs.groups);
                 else if (plan.chain == LargeChain::F32_RIGHT)
                         std::snprintf(buf, sizeof(buf), "large_right_step + large_syrk_bf16x3 (%d-launch chain per callback: one right-looking launch per block column)", plan.launches);
                 else if (plan.chain == LargeChain::F32_LEFT)

@@ -17,6 +17,10 @@
 //   large_syrk       P <- P - V V^T        ( = (I - K H) P, ekf.cpp:310, since K H P = V V^T for symmetric P ),
 //                    128x128 tiles, lower half mirrored, one filter's tiles on one XCD
 //   large_x_update   X <- X + V (L^-1 Y)   ( = X + K Y, ekf.cpp:309 )
+// The binary32 mode with many filters per launch runs the same steps as SIX launches (ekf_large_launch.h): front end, G and S, large_chol_bf16,
+// large_trsm_bf16 (ekf_large_trsm16.h), large_x_update_rows, large_syrk_bf16x3.  There a state of n = n0 + t, n0 a multiple of 64 and t <= 3 -- the
+// benchmark's n = 1027 = 16 x 64 + 3 -- is factored and solved over its n0 / 64 full blocks only, and the t x t tail is a BORDER solved in binary64 by
+// large_x_update_rows, which for that reason runs in front of the syrk: large_border() below is the one rule every kernel and the launch plan read.
 //
 // Unlike the single-CU kernel this path does not go through measurement coordinates: in fp32 the H / H^-1 change of
 // basis would cost eps * cond(H)^2 per callback; G, S, V are formed directly (2.33 n^3 flops all the same).
@@ -49,6 +53,7 @@ template <typename T> struct LargeView // (its arrays, their sizes per filter an
         T *Vw;      // [B][NP][NP]  binary32 mode, few-filter chain (large_right_step): V is written HERE, not over G (every block of G is read by many workgroups of a launch); else nullptr
         unsigned short *Lpl; // binary32 mode with the bf16-pipe TRSM: LPlanes::base (bf16 planes of L and of the inverses, written by large_chol_resident), else nullptr
         int xrows;  // vector rows that ride in G behind the n state rows through the factorisation: 1 (EKF: Y^T), 2 (large-state UKF: z^T and the innovation, ukf_large.h)
+        int border; // 1: this launch solves a short tail past the last full 64-block as a binary64 border (large_border below; set per launch from LargePlan::border), else 0
 };
 
 // ---- MFMA traits -------------------------------------------------------------------------------------------------
@@ -147,6 +152,36 @@ __host__ __device__ __forceinline__ int lplane_pos(int c)
 __host__ __device__ __forceinline__ int large_blocks(int n, int xrows = 1)
 {
         return (n + xrows + LB - 1) / LB;
+}
+
+/// The border rule (binary32 resident chain on the bf16 pipe, LargeView::border).  n = n0 + t with n0 = 64 floor(n / 64): a tail of t <= 3 rows past the
+/// last full 64-block (n is odd: t = 1 or 3; n = 1027 = 16 x 64 + 3 is the benchmark's size) would cost a whole block row and block column of the
+/// factorisation, of the solve and of the staging of P -= V V^T.  Instead, with S = [S11 S21^T; S21 S22] and G = [G1 G2]:
+///     L11 = chol(S11)                       large_chol_bf16 over nbc = n0 / 64 block rows
+///     [V1; l] = [G1; S21] L11^-T            large_trsm_bf16 over nbc block columns; S21 rides in rows n+1 .. n+t of G (large_build_GS puts it there)
+///     C = S22 - l l^T = L22 L22^T           t x t, binary64: large_x_update_rows, which reads every row of V anyway
+///     V2 = (G2 - V1 l^T) L22^-T             large_x_update_rows; stored over G2, row n included
+/// so that V = [V1 V2] is the V of the full factorisation up to rounding and every consumer (the syrk, q.q, ln det S) reads it as before.
+/// `t` = 0: no border for this n (the whole chain runs over large_blocks(n) blocks, as without the rule).
+struct LargeBorder
+{
+        int t;   // border width: 0 (none), 1 or 3
+        int nbc; // block columns the Cholesky factors and the TRSM sweeps: n0 / 64 with a border, else large_blocks(n)
+};
+__host__ __device__ __forceinline__ LargeBorder large_border(int n, int enabled)
+{
+        const int n0 = n & ~(LB - 1), t = n - n0;
+        const bool on = enabled && n0 >= LB && (t == 1 || t == 3);
+        return {on ? t : 0, on ? n0 / LB : large_blocks(n)};
+}
+constexpr int BORDER_MAX = 3;  // widest border
+// Rows n+1 .. n+t of G are spare (n + 1 + t <= n0 + 7 < n0 + 64 <= NP; nothing downstream reads them as V: the syrk stores no row >= n, large_stats and
+// the X update read row n and rows < n).  Row n+1+k carries row k of S21 in columns < n0 and, in columns n0 + BORDER_SAVE + m, a copy of column n0 + k
+// of the rows of G2 every workgroup of the X update needs while their owners overwrite them with V2: m = 0 .. 2 the pose rows, m = 3 row n (Y^T).
+constexpr int BORDER_SAVE = 8, BORDER_SAVE_ROWS = 4;
+__host__ __device__ __forceinline__ bool border_spare(const LargeBorder &bd, int n, int row, int col) // an entry of G that large_build_GS* must not clear
+{
+        return bd.t && row > n && row <= n + bd.t && (col < LB * bd.nbc || (col >= LB * bd.nbc + BORDER_SAVE && col < LB * bd.nbc + BORDER_SAVE + BORDER_SAVE_ROWS));
 }
 
 // ---- LDS layout of the front-end workgroup (runtime NP) -----------------------------------------------------------
@@ -359,6 +394,18 @@ template <typename T> __global__ __launch_bounds__(256) void large_build_GS(DevV
         const int r0 = pose ? 0 : 3 + 2 * RP * ((int)blockIdx.x - 1); // first row of this workgroup
         if (r0 >= na)
                 return;
+        // the border (large_border): rows n0 .. n-1 of S (S21 in columns < n0) also go to rows n+1 .. n+t of G, where the TRSM solves them into l, and
+        // the entries of G2 the X update needs from other rows than its own are copied next to them
+        const LargeBorder bd = large_border(n, lv.border);
+        const int n0 = LB * bd.nbc;
+        auto put_l = [&](int r, int c, double v) { // S(r, c), a row of S21
+                if (bd.t && r >= n0 && c < n0)
+                        G[(size_t)(r + bd.t + 1) * NP + c] = (T)v;
+        };
+        auto save_g2 = [&](int m, int c, T v) { // G(pose row m, c) (m = 3: Y(c)) for c in n0 .. n-1
+                if (bd.t && c >= n0 && c < n)
+                        G[(size_t)(n + 1 + c - n0) * NP + n0 + BORDER_SAVE + m] = v;
+        };
         int nlive = 0; // leading row pairs that are landmarks (rows < n; n is odd, so a pair never straddles n)
         if (!pose)
         {
@@ -379,7 +426,10 @@ template <typename T> __global__ __launch_bounds__(256) void large_build_GS(DevV
                                 const double *Y = lv.Y + (size_t)b * NP;
                                 for (int c = tid; c < na; c += 256)
                                 {
-                                        grow[c] = (rr == n && c < n) ? (T)Y[c] : (T)0;
+                                        if (!border_spare(bd, n, rr, c))
+                                                grow[c] = (rr == n && c < n) ? (T)Y[c] : (T)0;
+                                        if (rr == n)
+                                                save_g2(3, c, (T)Y[c]);
                                         srow[c] = (c == rr) ? (T)1 : (T)0;
                                 }
                         }
@@ -440,8 +490,10 @@ template <typename T> __global__ __launch_bounds__(256) void large_build_GS(DevV
                                         const double ga = pa[rp][c], gb = pb[rp][c];
                                         G[(size_t)ra * NP + c] = (T)ga;
                                         G[(size_t)(ra + 1) * NP + c] = (T)gb;
-                                        S[(size_t)ra * NP + c] = (T)srow(ha0[rp], ha1[rp], false, g0, g1, g2, ga, gb);
-                                        S[(size_t)(ra + 1) * NP + c] = (T)srow(hb0[rp], hb1[rp], true, g0, g1, g2, ga, gb);
+                                        const double sa = srow(ha0[rp], ha1[rp], false, g0, g1, g2, ga, gb), sb = srow(hb0[rp], hb1[rp], true, g0, g1, g2, ga, gb);
+                                        S[(size_t)ra * NP + c] = (T)sa;
+                                        S[(size_t)(ra + 1) * NP + c] = (T)sb;
+                                        put_l(ra, c, sa), put_l(ra + 1, c, sb);
                                 }
                 }
         }
@@ -461,6 +513,9 @@ template <typename T> __global__ __launch_bounds__(256) void large_build_GS(DevV
                         G[ce] = (T)g0e, G[co] = (T)g0o;
                         G[NP + ce] = (T)g1e, G[NP + co] = (T)g1o;
                         G[2 * (size_t)NP + ce] = (T)g2e, G[2 * (size_t)NP + co] = (T)g2o;
+                        save_g2(0, ce, (T)g0e), save_g2(0, co, (T)g0o);
+                        save_g2(1, ce, (T)g1e), save_g2(1, co, (T)g1o);
+                        save_g2(2, ce, (T)g2e), save_g2(2, co, (T)g2o);
                         if (ce < LB)
                         {
                                 S[ce] = (T)g0e, S[co] = (T)g0o;
@@ -493,6 +548,8 @@ template <typename T> __global__ __launch_bounds__(256) void large_build_GS(DevV
                                                         uo += r_bearing; // ... and its bearing row
                                                 sa[ce] = (T)se, sa[co] = (T)so;
                                                 sb[ce] = (T)ue, sb[co] = (T)uo;
+                                                put_l(ra, ce, se), put_l(ra, co, so);
+                                                put_l(ra + 1, ce, ue), put_l(ra + 1, co, uo);
                                         }
                                 }
                 }
@@ -565,6 +622,12 @@ template <typename T> __global__ __launch_bounds__(256) void large_build_GS_tile
         const double r_xy = prm->r_xy, r_yaw = prm->r_yaw, r_range = prm->r_range, r_bearing = prm->r_bearing; // diagonal of R by row class (ekf.cpp:65,278)
         const int tid = threadIdx.x;
         const int r0 = LB * I - 1, c0 = LB * J - 1; // global index of halo row / column 0
+        const LargeBorder bd = large_border(n, lv.border); // (as large_build_GS: rows of S21 -> rows n+1 .. n+t of G, the copies of G2 next to them)
+        const int n0 = LB * bd.nbc;
+        auto save_g2 = [&](int m, int c_, T v) {
+                if (bd.t && c_ >= n0 && c_ < n)
+                        G[(size_t)(n + 1 + c_ - n0) * NP + n0 + BORDER_SAVE + m] = v;
+        };
         typedef double d2 __attribute__((ext_vector_type(2)));
         // ---- stage the block: 16-byte loads of the 64 aligned columns (32 lanes per row, 8 rows per pass), then the two halo columns
         {
@@ -657,7 +720,10 @@ template <typename T> __global__ __launch_bounds__(256) void large_build_GS_tile
         {
                 const int r = 4 * ps + rq, gr = LB * I + r; // block row r = halo row r + 1
                 const double g = g_at(r + 1);
-                G[(size_t)gr * NP + gc] = (T)g;
+                if (!border_spare(bd, n, gr, gc))
+                        G[(size_t)gr * NP + gc] = (T)g;
+                if (gr == n)
+                        save_g2(3, gc, (T)g);
                 double sv;
                 if (gr >= n)
                         sv = (gr == gc) ? 1.0 : 0.0; // padding rows: identity
@@ -679,6 +745,8 @@ template <typename T> __global__ __launch_bounds__(256) void large_build_GS_tile
                                 sv += even ? r_bearing : r_range;
                 }
                 S[(size_t)gr * NP + gc] = (T)sv;
+                if (bd.t && gr >= n0 && gr < n && gc < n0)
+                        G[(size_t)(gr + bd.t + 1) * NP + gc] = (T)sv;
         }
         // ---- G(J, I): row cr of J, column a of I, from the block read transposed
         if (I != J)
@@ -699,6 +767,8 @@ template <typename T> __global__ __launch_bounds__(256) void large_build_GS_tile
                         else
                                 g = gcol(even, uI, vI, tJ[cr][0], tJ[cr][1], tJ[cr][2], Pt[ao][cr + 1], Pt[ao + 1][cr + 1]);
                         G[(size_t)grow * NP + gcolx] = (T)g;
+                        if (grow < 3)
+                                save_g2(grow, gcolx, (T)g);
                 }
         }
 }
@@ -1086,14 +1156,17 @@ constexpr int XU_ROWS = ASLAM_XU_ROWS; // (rows per wave of large_x_update_rows;
 /// read of the upper triangle, and P stays exactly symmetric.  The slab of V is split into its three bf16 planes by the VALU on the way into LDS (8 bytes per thread, row and plane; unpadded 64-byte rows with XOR-swizzled k-groups),
 /// the operand of an MFMA is ONE 16-byte read (row l & 15, k = 8 (l >> 4) .. + 7).
 ///
-/// The X update (large_x_update_rows: X += V q, the diagonal and the pose columns of V V^T in binary64) follows this kernel on the same stream.  This kernel
-/// never touches the entries of P the other one writes (pose columns, pose rows, diagonal), so the two COULD run side by side -- round 4 measured both
+/// The X update (large_x_update_rows: X += V q, the diagonal and the pose columns of V V^T in binary64) runs on the same stream: IN FRONT OF this kernel in
+/// the default chain (LargePlan::border: it completes V there -- the columns V2 of a filter's border, which this kernel's K loop then reads like any other
+/// column), behind it otherwise.  This kernel
+/// never touches the entries of P the other one writes (pose columns, pose rows, diagonal), so the order is free and the two COULD run side by side -- round 4 measured both
 /// ways (the X update's workgroups inside this launch: 2436 us against 1997 + 324 per 256 filters; on a side stream: 31.7 k against 36.4 k filter-steps/s)
 /// and both lose: at this kernel's register footprint the latency-bound X-update workgroups take slots while the matrix pipes idle, and next to it they
 /// fight it for L2 (profiles/r04_experiments.md section 1).
 ///
-/// What the chain does around this kernel, then: V arrives in binary32 (the TRSM's output) and is split by the VALU on the way into LDS -- no kernel of the
-/// library writes bf16 planes of V -- and the X update is a launch of its own, launch 6 of the chain, behind this one.
+/// What the chain does around this kernel, then: V arrives in binary32 (the TRSM's output; with a border its last t columns from the X update) and is split
+/// by the VALU on the way into LDS -- no kernel of the library writes bf16 planes of V -- and the X update is a launch of its own: launch 5 of the default
+/// chain, in front of this one; launch 6, behind it, without the border.
 /// RUNNING = false is the default chain's kernel.  RUNNING = true (ASLAM_SYRK_RUNNING=1) is round 2's accumulation order, kept for comparison: every tile
 /// takes the general path and the six products of a slab are added straight into the running sum (profiles/r03_experiments.md).
 template <bool RUNNING>
@@ -1417,39 +1490,176 @@ __global__ __launch_bounds__(256) void large_x_update(DevView d, LargeView<T> lv
 /// every row of V is multiplied with -- q and the pose rows of V -- staged ONCE per workgroup in LDS (17 KB) for the XU_ROWS x 4 rows its waves
 /// walk.  With a wave per row and the shared rows read from memory every wave issued 25 loads of 16 bytes per lane for 4 KB of new data: 391 us
 /// per 256 filters against 217 us for round 2's single product (profiles/r03_experiments.md).  grid (ceil(NP / (4 XU_ROWS)), B), 256 threads.
-/// the body: workgroup `xb` of filter `b` (32 rows); sh = 4 x LARGE_NP_MAX floats of LDS
-template <int MODE>
-__device__ __forceinline__ void x_update_rows_body(float (*sh)[LARGE_NP_MAX], const DevView &d, const LargeView<float> &lv, int b, int xb, int n, int s, int nsteps,
-                                                   double *poses_out, int32_t *dims_out)
+///
+/// THE BORDER (large_border): for a filter with a tail of t <= 3 rows past its last full 64-block the Cholesky and the TRSM in front of this kernel
+/// have covered the n0 = n - t leading columns only, and this kernel -- which runs IN FRONT OF the syrk then -- finishes the factorisation:
+///   * every workgroup stages, for the columns < n0, q1 (row n), the pose rows of V1 and the t rows of l (rows n+1 .. n+t of G), and forms from them, in
+///     binary64,  C = S22 - l l^T = L22 L22^T,  L22^-1  and  V2 = (G2 - V1 l^T) L22^-T  of row n (q2) and of the pose rows.  Same code, same order in
+///     every workgroup (every thread, in fact): all of them hold bit-equal values.  The G2 of those four rows is read from the copies large_build_GS
+///     left in the spare rows (BORDER_SAVE), not from the rows themselves, which their owners overwrite with V2 meanwhile; nobody reads another row's
+///     columns >= n0.
+///   * per row a, t more dot products V1(a) . l_k in the same pass give V2(a), which is stored in binary32 over G2(a) (the K loop of the syrk then reads the
+///     border like any other column), and the V2 terms are added to V q, the diagonal and the pose columns.
+///     The pass always carries BORDER_MAX = 3 rows of l: with t = 1 two of them are staged as zeros and their dot products and LDS reads are wasted work
+///     (n mod 64 = 1 is not the benchmark's case; two more instantiations would remove it).
+///   * workgroup 0 of the filter stores q2 into row n, writes L22^-1 into block nbc of Linv (identity outside the t x t corner: large_stats reads the
+///     diagonal for ln det S) and raises ASLAM_ST_NOT_PD on a non-positive pivot of C, as the Cholesky does for its blocks.
+constexpr int XU_SH_ROWS = 4 + BORDER_MAX;                                      // staged rows: q, pose rows 0 .. 2 of V, l_0 .. l_2
+constexpr int XU_NDOT = 4 * BORDER_MAX + BORDER_MAX * (BORDER_MAX + 1) / 2;     // {q, pose rows} . l_k, then the lower triangle of l l^T
+
+/// what a workgroup knows of its filter's border; the same values in every thread
+struct XuBorder
+{
+        double Li[BORDER_MAX][BORDER_MAX]; // L22^-1 (lower triangle; beyond t: the identity)
+        float v2[4][BORDER_MAX];           // V2 of row n (q2) and of pose rows 0 .. 2, as stored (beyond t: 0)
+        bool ok;                           // every pivot of C was positive
+};
+
+/// stages the shared rows (columns < n0 only) and solves the border; contains the workgroup's one barrier
+__device__ __forceinline__ XuBorder x_update_border(float (*sh)[LARGE_NP_MAX], double (*red)[XU_NDOT], const LargeView<float> &lv, int b, int n, const LargeBorder &bd)
+{
+        constexpr int BM = BORDER_MAX;
+        const int NP = lv.NP, tid = threadIdx.x, t = bd.t, n0 = LB * bd.nbc;
+        const float *G = lv.G + (size_t)b * NP * NP, *S = lv.S + (size_t)b * NP * NP;
+        // S22 and the saved G2 first: their latency hides behind the staging
+        float s22[BM][BM], g2[4][BM];
+#pragma unroll
+        for (int i = 0; i < BM; ++i)
+#pragma unroll
+                for (int j = 0; j <= i; ++j)
+                        s22[i][j] = i < t ? S[(size_t)(n0 + i) * NP + n0 + j] : (i == j ? 1.f : 0.f);
+#pragma unroll
+        for (int k = 0; k < BM; ++k)
+#pragma unroll
+                for (int m = 0; m < 4; ++m)
+                        g2[m][k] = k < t ? G[(size_t)(n + 1 + k) * NP + n0 + BORDER_SAVE + ((m + 3) & 3)] : 0.f; // (here m = 0 is row n, the copies keep it last)
+        double dot[XU_NDOT];
+#pragma unroll
+        for (int i = 0; i < XU_NDOT; ++i)
+                dot[i] = 0.0;
+        for (int j = 4 * tid; j < n0; j += 4 * 256)
+        {
+                f4 r[XU_SH_ROWS];
+                r[0] = *reinterpret_cast<const f4 *>(G + (size_t)n * NP + j);
+#pragma unroll
+                for (int m = 0; m < 3; ++m)
+                        r[1 + m] = *reinterpret_cast<const f4 *>(G + (size_t)m * NP + j);
+#pragma unroll
+                for (int k = 0; k < BM; ++k)
+                        r[4 + k] = k < t ? *reinterpret_cast<const f4 *>(G + (size_t)(n + 1 + k) * NP + j) : (f4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int m = 0; m < XU_SH_ROWS; ++m)
+                        *reinterpret_cast<f4 *>(&sh[m][j]) = r[m];
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                {
+#pragma unroll
+                        for (int m = 0; m < 4; ++m)
+#pragma unroll
+                                for (int k = 0; k < BM; ++k)
+                                        dot[BM * m + k] = fma((double)r[m][e], (double)r[4 + k][e], dot[BM * m + k]);
+#pragma unroll
+                        for (int i = 0; i < BM; ++i)
+#pragma unroll
+                                for (int k = 0; k <= i; ++k)
+                                        dot[4 * BM + i * (i + 1) / 2 + k] = fma((double)r[4 + i][e], (double)r[4 + k][e], dot[4 * BM + i * (i + 1) / 2 + k]);
+                }
+        }
+#pragma unroll
+        for (int i = 0; i < XU_NDOT; ++i)
+                dot[i] = wave_sum_dpp(dot[i]);
+        if ((tid & 63) == 63)
+        {
+#pragma unroll
+                for (int i = 0; i < XU_NDOT; ++i)
+                        red[tid >> 6][i] = dot[i];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < XU_NDOT; ++i)
+                dot[i] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
+        // C = S22 - l l^T, its Cholesky factor and the inverse of that (rows >= t: the identity)
+        XuBorder bx;
+        double L[BM][BM];
+        bx.ok = true;
+#pragma unroll
+        for (int j = 0; j < BM; ++j)
+        {
+                double sjj = (double)s22[j][j] - dot[4 * BM + j * (j + 1) / 2 + j];
+#pragma unroll
+                for (int k = 0; k < j; ++k)
+                        sjj -= L[j][k] * L[j][k];
+                bx.ok = bx.ok && sjj > 0.0;
+                L[j][j] = sqrt(sjj); // (a non-positive pivot: flagged by workgroup 0 and the NaNs go on into Linv, V2, X and P -- "flag and go on", as chol64::factor_and_invert does for the blocks)
+#pragma unroll
+                for (int i = j + 1; i < BM; ++i)
+                {
+                        double sij = (double)s22[i][j] - dot[4 * BM + i * (i + 1) / 2 + j];
+#pragma unroll
+                        for (int k = 0; k < j; ++k)
+                                sij -= L[i][k] * L[j][k];
+                        L[i][j] = sij / L[j][j];
+                }
+        }
+        static_assert(BM == 3, "the inverse below is written out for 3 x 3");
+        bx.Li[0][0] = 1.0 / L[0][0], bx.Li[1][1] = 1.0 / L[1][1], bx.Li[2][2] = 1.0 / L[2][2];
+        bx.Li[1][0] = -(L[1][0] * bx.Li[0][0]) * bx.Li[1][1];
+        bx.Li[2][1] = -(L[2][1] * bx.Li[1][1]) * bx.Li[2][2];
+        bx.Li[2][0] = -(L[2][0] * bx.Li[0][0] + L[2][1] * bx.Li[1][0]) * bx.Li[2][2];
+        bx.Li[0][1] = bx.Li[0][2] = bx.Li[1][2] = 0.0;
+        // V2 = (G2 - V1 l^T) L22^-T of row n and of the pose rows
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+                for (int j = 0; j < BM; ++j)
+                {
+                        double v = 0.0;
+#pragma unroll
+                        for (int k = 0; k <= j; ++k)
+                                v += ((double)g2[m][k] - dot[BM * m + k]) * bx.Li[j][k];
+                        bx.v2[m][j] = (float)v;
+                }
+        return bx;
+}
+
+/// the XU_ROWS rows of one wave.  BORDER: the pass stops at n0; the row's G2 (columns n0 .. n0 + 3: 16 aligned bytes, zero from column n on) rides along
+/// with the loads of the row
+template <int MODE, bool BORDER>
+__device__ __forceinline__ void x_update_rows_loop(const float (*sh)[LARGE_NP_MAX], const XuBorder &bx, const DevView &d, const LargeView<float> &lv, int b, int xb, int n,
+                                                   int n0, int s, int nsteps, double *poses_out, int32_t *dims_out)
 {
         const int NP = lv.NP;
         const int tid = threadIdx.x, lane = tid & 63;
-        if (xb * 4 * XU_ROWS >= n)
-                return;
-        const float *G = lv.G + (size_t)b * NP * NP;
-        for (int j = 4 * tid; j < NP; j += 4 * 256)
-        {
-                *reinterpret_cast<f4 *>(&sh[0][j]) = *reinterpret_cast<const f4 *>(G + (size_t)n * NP + j);
-                *reinterpret_cast<f4 *>(&sh[1][j]) = *reinterpret_cast<const f4 *>(G + j);
-                *reinterpret_cast<f4 *>(&sh[2][j]) = *reinterpret_cast<const f4 *>(G + NP + j);
-                *reinterpret_cast<f4 *>(&sh[3][j]) = *reinterpret_cast<const f4 *>(G + 2 * (size_t)NP + j);
-        }
-        __syncthreads();
+        float *G = lv.G + (size_t)b * NP * NP;
         double *P = lv.P + (size_t)b * NP * NP;
         const int a0 = (xb * 4 + (tid >> 6)) * XU_ROWS;
         constexpr int NPASS = 5; // 5 x 64 lanes x 4 columns = 1280 >= LARGE_NP_MAX
-        auto load_row = [&](f4 (&v)[NPASS], int a) {
+        const int jlim = BORDER ? n0 : n;
+        auto load_row = [&](f4 (&v)[NPASS], f4 &g2, int a) {
                 const float *vr = G + (size_t)min(a, n - 1) * NP;
 #pragma unroll
                 for (int i = 0; i < NPASS; ++i)
                 {
                         const int j = 4 * lane + 256 * i;
-                        v[i] = j < n ? *reinterpret_cast<const f4 *>(vr + j) : (f4){0.f, 0.f, 0.f, 0.f}; // (columns n .. of every row of V are zero)
+                        v[i] = j < jlim ? *reinterpret_cast<const f4 *>(vr + j) : (f4){0.f, 0.f, 0.f, 0.f}; // (columns n .. of every row of V are zero)
                 }
+                if constexpr (BORDER)
+                        g2 = *reinterpret_cast<const f4 *>(vr + n0);
         };
+        // V2 of the pose rows, pinned in registers: selected by the row index below, and a select between members of a struct sends the whole struct
+        // to scratch memory
+        float pv[3][BORDER_MAX];
+#pragma unroll
+        for (int m = 0; m < 3; ++m)
+#pragma unroll
+                for (int k = 0; k < BORDER_MAX; ++k)
+                {
+                        pv[m][k] = bx.v2[1 + m][k];
+                        asm volatile("" : "+v"(pv[m][k]));
+                }
         // the loads of row a + 1 are issued before row a is multiplied: the kernel lives on bytes in flight
-        f4 vn[NPASS];
-        load_row(vn, a0);
+        f4 vn[NPASS], g2n = {0.f, 0.f, 0.f, 0.f};
+        load_row(vn, g2n, a0);
 #pragma unroll 1
         for (int r = 0; r < XU_ROWS; ++r)
         {
@@ -1457,20 +1667,24 @@ __device__ __forceinline__ void x_update_rows_body(float (*sh)[LARGE_NP_MAX], co
                 if (a >= n)
                         break; // wave-uniform
                 f4 v[NPASS];
+                const f4 g2 = g2n;
 #pragma unroll
                 for (int i = 0; i < NPASS; ++i)
                         v[i] = vn[i];
                 if (r + 1 < XU_ROWS)
-                        load_row(vn, a + 1);
-                double acc = 0.0, dd = 0.0, d0 = 0.0, d1 = 0.0, d2 = 0.0;
+                        load_row(vn, g2n, a + 1);
+                double acc = 0.0, dd = 0.0, d0 = 0.0, d1 = 0.0, d2 = 0.0, e0 = 0.0, e1 = 0.0, e2 = 0.0;
 #pragma unroll
                 for (int i = 0; i < NPASS; ++i)
                 {
                         const int j = 4 * lane + 256 * i;
-                        if (j >= n)
+                        if (j >= jlim)
                                 continue; // (beyond NP nothing was staged)
                         const f4 wi = *reinterpret_cast<const f4 *>(&sh[0][j]), p0 = *reinterpret_cast<const f4 *>(&sh[1][j]),
                                  p1 = *reinterpret_cast<const f4 *>(&sh[2][j]), p2 = *reinterpret_cast<const f4 *>(&sh[3][j]);
+                        f4 l0 = {0.f, 0.f, 0.f, 0.f}, l1 = l0, l2 = l0;
+                        if constexpr (BORDER)
+                                l0 = *reinterpret_cast<const f4 *>(&sh[4][j]), l1 = *reinterpret_cast<const f4 *>(&sh[5][j]), l2 = *reinterpret_cast<const f4 *>(&sh[6][j]);
 #pragma unroll
                         for (int e = 0; e < 4; ++e)
                         {
@@ -1480,11 +1694,45 @@ __device__ __forceinline__ void x_update_rows_body(float (*sh)[LARGE_NP_MAX], co
                                 d0 = fma(ve, (double)p0[e], d0);
                                 d1 = fma(ve, (double)p1[e], d1);
                                 d2 = fma(ve, (double)p2[e], d2);
+                                if constexpr (BORDER)
+                                {
+                                        e0 = fma(ve, (double)l0[e], e0);
+                                        e1 = fma(ve, (double)l1[e], e1);
+                                        e2 = fma(ve, (double)l2[e], e2);
+                                }
                         }
                 }
                 acc = wave_sum_dpp(acc), dd = wave_sum_dpp(dd), d0 = wave_sum_dpp(d0), d1 = wave_sum_dpp(d1), d2 = wave_sum_dpp(d2);
+                if constexpr (BORDER)
+                        e0 = wave_sum_dpp(e0), e1 = wave_sum_dpp(e1), e2 = wave_sum_dpp(e2);
                 if (lane == 63)
                 {
+                        if constexpr (BORDER)
+                        {
+                                // V2(a) = (G2(a) - V1(a) l^T) L22^-T, rounded to binary32 as it is stored; the pose rows take the values every
+                                // workgroup holds (the same expression over another order of summation)
+                                const double w0 = (double)g2[0] - e0, w1 = (double)g2[1] - e1, w2 = (double)g2[2] - e2;
+                                float x0 = (float)(w0 * bx.Li[0][0]), x1 = (float)(w0 * bx.Li[1][0] + w1 * bx.Li[1][1]),
+                                      x2 = (float)(w0 * bx.Li[2][0] + w1 * bx.Li[2][1] + w2 * bx.Li[2][2]);
+                                if (a < 3)
+                                {
+                                        x0 = a == 0 ? pv[0][0] : a == 1 ? pv[1][0] : pv[2][0];
+                                        x1 = a == 0 ? pv[0][1] : a == 1 ? pv[1][1] : pv[2][1];
+                                        x2 = a == 0 ? pv[0][2] : a == 1 ? pv[1][2] : pv[2][2];
+                                }
+                                *reinterpret_cast<f4 *>(G + (size_t)a * NP + n0) = (f4){x0, x1, x2, 0.f}; // (x_k = 0 for k >= t: column n .. stay zero)
+                                const float xs[BORDER_MAX] = {x0, x1, x2};
+#pragma unroll
+                                for (int k = 0; k < BORDER_MAX; ++k)
+                                {
+                                        const double ve = (double)xs[k];
+                                        acc = fma(ve, (double)bx.v2[0][k], acc);
+                                        dd = fma(ve, ve, dd);
+                                        d0 = fma(ve, (double)bx.v2[1][k], d0);
+                                        d1 = fma(ve, (double)bx.v2[2][k], d1);
+                                        d2 = fma(ve, (double)bx.v2[3][k], d2);
+                                }
+                        }
                         double *prow = P + (size_t)a * NP;
                         const double dp[3] = {d0, d1, d2};
                         // pose columns j < min(a, 3) with their mirror image; the diagonal entry itself
@@ -1508,15 +1756,69 @@ __device__ __forceinline__ void x_update_rows_body(float (*sh)[LARGE_NP_MAX], co
         }
 }
 
+/// the body: workgroup `xb` of filter `b` (32 rows); sh = XU_SH_ROWS x LARGE_NP_MAX floats of LDS, red = 4 x XU_NDOT doubles
+template <int MODE>
+__device__ __forceinline__ void x_update_rows_body(float (*sh)[LARGE_NP_MAX], double (*red)[XU_NDOT], const DevView &d, const LargeView<float> &lv, int b, int xb, int n,
+                                                   int s, int nsteps, double *poses_out, int32_t *dims_out)
+{
+        const int NP = lv.NP;
+        const int tid = threadIdx.x;
+        if (xb * 4 * XU_ROWS >= n)
+                return;
+        float *G = lv.G + (size_t)b * NP * NP;
+        const LargeBorder bd = large_border(n, lv.border);
+        const int n0 = LB * bd.nbc;
+        XuBorder bx = {};
+        if (bd.t)
+        {
+                bx = x_update_border(sh, red, lv, b, n, bd);
+                if (xb == 0)
+                {
+                        // row n of V, the border's block of Linv, the status
+                        float *Lb = lv.Linv + ((size_t)b * LARGE_NB_MAX + bd.nbc) * LB * LB;
+                        for (int e = tid; e < LB * LB; e += 256)
+                        {
+                                const int r = e >> 6, c = e & (LB - 1);
+                                double v = r == c ? 1.0 : 0.0;
+                                if (r < BORDER_MAX && c <= r)
+                                        v = r == 0 ? bx.Li[0][0] : r == 1 ? (c == 0 ? bx.Li[1][0] : bx.Li[1][1]) : (c == 0 ? bx.Li[2][0] : c == 1 ? bx.Li[2][1] : bx.Li[2][2]);
+                                Lb[e] = (float)v;
+                        }
+                        if (tid == 0)
+                        {
+                                *reinterpret_cast<f4 *>(G + (size_t)n * NP + n0) = (f4){bx.v2[0][0], bx.v2[0][1], bx.v2[0][2], 0.f}; // (columns n .. of every row are zero)
+                                if (!bx.ok)
+                                        atomicOr(&d.status[b], 4u); // ASLAM_ST_NOT_PD
+                        }
+                }
+        }
+        else
+        {
+                for (int j = 4 * tid; j < NP; j += 4 * 256)
+                {
+                        *reinterpret_cast<f4 *>(&sh[0][j]) = *reinterpret_cast<const f4 *>(G + (size_t)n * NP + j);
+                        *reinterpret_cast<f4 *>(&sh[1][j]) = *reinterpret_cast<const f4 *>(G + j);
+                        *reinterpret_cast<f4 *>(&sh[2][j]) = *reinterpret_cast<const f4 *>(G + NP + j);
+                        *reinterpret_cast<f4 *>(&sh[3][j]) = *reinterpret_cast<const f4 *>(G + 2 * (size_t)NP + j);
+                }
+                __syncthreads();
+        }
+        if (bd.t)
+                x_update_rows_loop<MODE, true>(sh, bx, d, lv, b, xb, n, n0, s, nsteps, poses_out, dims_out);
+        else
+                x_update_rows_loop<MODE, false>(sh, bx, d, lv, b, xb, n, n0, s, nsteps, poses_out, dims_out);
+}
+
 /// grid (ceil(NP / (4 XU_ROWS)), B), 256 threads
 template <int MODE>
 __global__ __launch_bounds__(256) void large_x_update_rows(DevView d, LargeView<float> lv, int s, int nsteps, double *poses_out, int32_t *dims_out, const int *skipped)
 {
-        __shared__ __attribute__((aligned(16))) float sh[4][LARGE_NP_MAX]; // q, pose rows 0 .. 2 of V
+        __shared__ __attribute__((aligned(16))) float sh[XU_SH_ROWS][LARGE_NP_MAX]; // q, pose rows 0 .. 2 of V, the rows of l (border)
+        __shared__ double red[4][XU_NDOT];
         const int b = blockIdx.y;
         if (skipped[b])
                 return;
-        x_update_rows_body<MODE>(sh, d, lv, b, (int)blockIdx.x, d.n[b], s, nsteps, poses_out, dims_out);
+        x_update_rows_body<MODE>(sh, red, d, lv, b, (int)blockIdx.x, d.n[b], s, nsteps, poses_out, dims_out);
 }
 
 /// The statistics of a callback (StatsView), launched behind the chain only when somebody asks for them: every chain leaves what they need.

@@ -1,6 +1,9 @@
 // ekf_large_launch.h -- host side of the large-state EKF (n > 143, or fp32), included by aslam_core.hip: the environment knobs, the launch
 // plan (which of the four kernel chains a callback runs: large_plan() is the ONE place that decides it -- aslam_create, the launcher and
 // aslam_kernel_info read its result), views shifted to a group of filters, the chain launcher and the split of a batch into stream groups.
+// The default binary32 chain (LargeChain::F32_RESIDENT on the bf16 pipe) solves a tail of <= 3 rows past the last full 64-block as a border
+// (large_border(), ekf_large.h): LargePlan::border says so, every group's view carries it to the kernels (LargeView::border), and the X update is
+// then launched in front of the syrk.  ASLAM_BORDER=0 is the chain without it.
 // The list of the arrays a filter owns is for_each_array(), next to each view's struct (DevView: small_common.h, LargeView: ekf_large.h):
 // to add an array, add the member and one line there -- aslam_create, shifted(), aslam_reset and the clear list of restore follow.
 #pragma once
@@ -34,6 +37,7 @@ struct LargeKnobs
         int bf16_pipe = 3;    // binary32 mode, resident chain: bit 0 the TRSM, bit 1 the Cholesky on the bf16 matrix pipe (large_trsm_bf16, large_chol_bf16: ekf_large_trsm16.h); ASLAM_BF16_PIPE=0: the fp32-MFMA pair (diagnostics: 1 = large_chol_resident writes the planes, 2 = large_trsm_pipe solves)
         int keep_l32 = 0;     // ASLAM_KEEP_L32=1 (tests/manual/large_residuals.py reads L back): large_chol_bf16 also stores the off-diagonal blocks of L in binary32
         int gs_tiles = 0;     // G, S by the row-pair kernel that reads all of P (large_build_GS); ASLAM_GS_TILES=1: from the lower block triangle of P (large_build_GS_tiles) -- bit-identical results, slower, kept for its test
+        int border = 1;       // default chain (bf16-pipe Cholesky and TRSM): a tail of <= 3 rows past the last full 64-block is solved as a binary64 border by the X update (large_border, ekf_large.h); ASLAM_BORDER=0: every block row and column through the sweeps, the X update behind the syrk -- kept for its agreement test
         int syrk_running = 0; // diagnostic (ASLAM_SYRK_RUNNING=1): round 2's accumulation order in large_syrk_bf16x3 (profiles/r03_experiments.md)
 };
 
@@ -50,6 +54,7 @@ inline LargeKnobs large_knobs_from_env()
         flag("ASLAM_KEEP_L32", k.keep_l32);
         flag("ASLAM_GS_TILES", k.gs_tiles);
         flag("ASLAM_SYRK_RUNNING", k.syrk_running);
+        flag("ASLAM_BORDER", k.border);
         return k;
 }
 
@@ -58,6 +63,7 @@ enum class LargeChain
 {
         F64_LEFT,     // NB x {large_potrf_inv_tiles, large_update_panel over S, G and Y^T}, large_syrk, large_x_update: 4 + 2 NB launches
         F32_RESIDENT, // Cholesky and TRSM as one launch each with the factor resident (bf16 pipe or fp32 MFMA), large_syrk_bf16x3, large_x_update_rows: 6
+                      // (LargePlan::border: large_x_update_rows, which then also solves the border, IN FRONT OF the syrk)
         F32_RIGHT,    // large_potrf_inv_tiles(0), NB x large_right_step (factors S and solves the rows of G into Vw together), syrk, X update: 5 + NB
         F32_LEFT      // NB x {large_potrf_inv_tiles, large_update_panel over S}, large_trsm_pipe, syrk, X update: 4 + 2 NB
 };
@@ -66,6 +72,7 @@ struct LargePlan
 {
         LargeChain chain;
         bool chol16, trsm16;         // F32_RESIDENT: large_chol_bf16 for large_chol_resident, large_trsm_bf16 for large_trsm_pipe
+        bool border;                 // F32_RESIDENT with chol16 && trsm16: large_border() applies (the kernels decide per filter from its n), the X update runs in front of the syrk
         bool chol_f32out;            // large_chol_bf16 also stores the off-diagonal blocks of L in binary32 (the bf16 TRSM reads L through its planes only)
         bool gs_tiles, syrk_running; // large_build_GS_tiles for large_build_GS; large_syrk_bf16x3<true> for <false>
         int launches;                // kernel launches per callback and stream group
@@ -90,6 +97,7 @@ inline LargePlan large_plan(bool f32, int NP, int batch, int filters, const Larg
                 p.chol16 = (k.bf16_pipe & 2) != 0;
                 p.trsm16 = (k.bf16_pipe & 1) != 0;
                 p.chol_f32out = !p.trsm16 || k.keep_l32;
+                p.border = p.chol16 && p.trsm16 && !k.keep_l32 && k.border != 0;
         }
         else if (p.need_Vw)
                 p.chain = LargeChain::F32_RIGHT, p.launches = 5 + NB;
@@ -259,16 +267,23 @@ void launch_large_chain(const LargePlan &plan, const LargeGroup<T> &g, size_t ld
                         launch_left_looking(g.dv, g.v, NB, gb, g.skip, g.st, 1, false);
                         hipLaunchKernelGGL(large_trsm_pipe<LARGE_NB_MAX>, dim3(8 * ((gb + 7) / 8) * NB), dim3(256), 0, g.st, g.dv, g.v, gb, g.skip);
                 }
+                // X += V q (+ the diagonal and the pose columns of V V^T in binary64) on the same stream as the syrk; the two write disjoint entries of P,
+                // so their order is free.  With the border the X update goes FIRST: it completes V (the columns V2 past the last full 64-block) for the
+                // syrk to read.  Without it, behind the syrk as ever.  Round 4 tried the two ways of running it NEXT TO the syrk -- its workgroups inside
+                // the syrk launch, and on a side stream of its own -- and both were slower: 2436 us against 1997 + 324 per 256 filters, and 31.7 k
+                // against 36.4 k filter-steps/s (profiles/r04_experiments.md section 1)
+                auto x_update = [&]() {
+                        hipLaunchKernelGGL((large_x_update_rows<MODE>), dim3((NP + 4 * XU_ROWS - 1) / (4 * XU_ROWS), gb), dim3(256), 0, g.st, g.dv, vv, s, nsteps,
+                                           g.poses, g.dims, g.skip);
+                };
+                if (plan.border)
+                        x_update();
                 if (plan.syrk_running)
                         hipLaunchKernelGGL((large_syrk_bf16x3<true>), syrk_grid, dim3(256), 0, g.st, g.dv, vv, gb, g.skip);
                 else
                         hipLaunchKernelGGL((large_syrk_bf16x3<false>), syrk_grid, dim3(256), 0, g.st, g.dv, vv, gb, g.skip);
-                // X += V q (+ the diagonal and the pose columns of V V^T in binary64) BEHIND the syrk on the same stream.  Round 4 tried the two ways of
-                // running it next to the syrk -- its workgroups inside the syrk launch, and on a side stream of its own (the two write disjoint entries
-                // of P) -- and both were slower: 2436 us against 1997 + 324 per 256 filters, and 31.7 k against 36.4 k filter-steps/s
-                // (profiles/r04_experiments.md section 1)
-                hipLaunchKernelGGL((large_x_update_rows<MODE>), dim3((NP + 4 * XU_ROWS - 1) / (4 * XU_ROWS), gb), dim3(256), 0, g.st, g.dv, vv, s, nsteps, g.poses,
-                                   g.dims, g.skip);
+                if (!plan.border)
+                        x_update();
                 if (g.sv.any())
                         hipLaunchKernelGGL(large_stats<T>, dim3(gb), dim3(256), 0, g.st, g.dv, vv, s, nsteps, g.sv, g.skip);
         }
@@ -299,6 +314,7 @@ hipError_t launch_large(LargeHost &h, const DevView &dv, const LargeView<T> &lv,
                 const int o = std::min(q * per, Bz);
                 const size_t b0 = (size_t)(first + o);
                 g[q] = {shifted_dev(dv, b0, MODE == MODE_REPLAY), shifted(lv, b0), skipped + b0, poses, dims, std::min(per, Bz - o), q == 0 ? st : h.aux[q - 1], shifted_stats(sv, b0, nsteps)};
+                g[q].v.border = plan.border; // (per launch: a one-trajectory step of a resident context runs another chain)
                 if (MODE == MODE_REPLAY && poses)
                         g[q].poses += b0 * (size_t)nsteps * 3;
                 if (MODE == MODE_REPLAY && dims)

@@ -528,6 +528,8 @@ __device__ __forceinline__ void sweep16(f4 (&cdiag)[4], Regs &R, Pipe &pp, unsig
 
 /// V = G L^-T on the bf16 pipe.  grid (8 * ceil(B / 8) * NP / 64), 256 threads; wave w of a workgroup owns 16 rows of G; in place: G -> V.
 /// Same workgroup -> (filter, row block) map as large_trsm_pipe (a filter's workgroups share one XCD).
+/// With a border (large_border, ekf_large.h) every row block sweeps the nbc factored block columns only: columns n0 .. of G stay as they are (G2), and the
+/// last row block, rows n0 .. n0 + 63, holds the tail rows of G, Y^T and -- rows n+1 .. n+t -- S21, which comes out as l.
 template <int NBMAX, bool STAMP = false>
 __global__ __launch_bounds__(256, 1) void large_trsm_bf16(DevView d, LargeView<float> lv, t16::Planes pl, int nfilters, const int *skipped)
 {
@@ -556,7 +558,7 @@ __global__ __launch_bounds__(256, 1) void large_trsm_bf16(DevView d, LargeView<f
         Regs R;
         f4 c[4];
         asm volatile("; ASLAM_STRIP_LIVE_BEGIN vmem: global_store_dwordx4=4" ::: "memory"); // (tools/check_vmcnt_protocol.py: what Pipe's counts assume)
-        sweep16<STAMP, false>(c, R, pp, lds, gl[wv], pl, b, nb, nb, NP, rows, tid);
+        sweep16<STAMP, false>(c, R, pp, lds, gl[wv], pl, b, large_border(n, lv.border).nbc, nb, NP, rows, tid);
         asm volatile("; ASLAM_STRIP_LIVE_END" ::: "memory");
         if constexpr (STAMP)
                 if (tid == 0 && blockIdx.x == 0)
@@ -583,7 +585,7 @@ __global__ __launch_bounds__(256, 1) void large_chol_bf16(DevView d, LargeView<f
         if (skipped[b])
                 return;
         const int n = d.n[b], NP = lv.NP;
-        const int nb = large_blocks(n);
+        const int nbc = large_border(n, lv.border).nbc; // with a border: the full 64-blocks only (the tail is factored by large_x_update_rows)
         const int tid0 = threadIdx.x;
         const int wv = __builtin_amdgcn_readfirstlane(tid0 >> 6);
         float *Sb = lv.S + (size_t)b * NP * NP;
@@ -597,7 +599,7 @@ __global__ __launch_bounds__(256, 1) void large_chol_bf16(DevView d, LargeView<f
         Pipe pp;
         Regs R;
 #pragma unroll 1
-        for (int I = 0; I < nb; ++I)
+        for (int I = 0; I < nbc; ++I)
         {
                 // one opaque re-definition of the thread index per block row: hipcc otherwise hoists every tid-derived address of the loop body out
                 // of the loop, runs out of VGPRs and parks the overflow in AGPRs -- the strip's (tools/check_agpr_strip.py)
@@ -612,7 +614,7 @@ __global__ __launch_bounds__(256, 1) void large_chol_bf16(DevView d, LargeView<f
                         asm volatile("; ASLAM_STRIP_LIVE_BEGIN vmem: global_store_dwordx4=4 buffer_store_dwordx4=6" ::: "memory"); // (tools/check_vmcnt_protocol.py)
                 else
                         asm volatile("; ASLAM_STRIP_LIVE_BEGIN vmem: buffer_store_dwordx4=6" ::: "memory");
-                sweep16<false, true, F32OUT>(c, R, pp, lds, gl[wv], pl, b, I, nb, NP, rows, tid);
+                sweep16<false, true, F32OUT>(c, R, pp, lds, gl[wv], pl, b, I, nbc, NP, rows, tid);
                 asm volatile("; ASLAM_STRIP_LIVE_END" ::: "memory");
                 // every DMA piece still in flight targets the buffers the tiles are about to take
                 asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
