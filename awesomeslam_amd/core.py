@@ -28,12 +28,13 @@ CORE_SYMBOLS = (
     "aslam_get_layout", "aslam_kernel_info", "aslam_get_launch_info",
     "aslam_replay_stats", "aslam_innovation_enable", "aslam_get_innovation",
     "aslam_params_default", "aslam_set_params", "aslam_get_params",
+    "aslam_remove_landmarks", "aslam_select_beyond",
 )
 NODE_SYMBOLS = (
     "aslam_node_create", "aslam_node_create_at", "aslam_node_destroy", "aslam_node_error", "aslam_node_sensor", "aslam_node_odom",
     "aslam_node_odom_now", "aslam_node_dim", "aslam_node_get", "aslam_node_wait", "aslam_node_core",
     "aslam_host_narrow_odom", "aslam_node_enable_innovation", "aslam_node_innovation",
-    "aslam_node_set_params", "aslam_node_get_params",
+    "aslam_node_set_params", "aslam_node_get_params", "aslam_node_remove_landmarks",
 )
 TRACE_FILE_SYMBOLS = (
     "aslam_trace_file_open", "aslam_trace_file_close", "aslam_trace_file_error", "aslam_trace_file_dims",
@@ -181,6 +182,8 @@ def core_lib():
         L.aslam_get_layout.argtypes = [vp, pi, ctypes.POINTER(ctypes.c_int64)]
         L.aslam_kernel_info.argtypes = [vp, ctypes.c_char_p, ci, pi, pi, pi]
         L.aslam_get_launch_info.argtypes = [vp, pi, pi, pi]
+        L.aslam_remove_landmarks.argtypes = [vp, vp, ci, ci, vp]
+        L.aslam_select_beyond.argtypes = [vp, pd, vp, ci, vp]
         # include/aslam_snapshot.h
         p32, p64 = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)
         L.aslam_snapshot_record_bytes.restype = ctypes.c_int64
@@ -220,6 +223,7 @@ def node_lib():
         L.aslam_node_innovation.argtypes = [vp, pd, pd]
         L.aslam_node_set_params.argtypes = [vp, ctypes.POINTER(Params)]
         L.aslam_node_get_params.argtypes = [vp, ctypes.POINTER(Params)]
+        L.aslam_node_remove_landmarks.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ci]
         # include/aslam_trace_file.h
         L.aslam_trace_file_error.restype = ctypes.c_char_p
         L.aslam_trace_file_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
@@ -360,6 +364,7 @@ class Core:
         self.filter = filter
         self.batch = int(batch)
         self.max_obs = int(max_obs)
+        self.max_landmark_count = int(max_landmark_count)
         cfg = Config(FILTERS[filter], dtype, int(max_landmark_count), int(batch), int(max_obs), int(max_wait),
                      int(device), int(flags))
         h = ctypes.c_void_p()
@@ -575,6 +580,59 @@ class Core:
         """restore() from a file written by save()."""
         self.restore(np.fromfile(path, np.uint8), records, trajs)
 
+    # ---- removing landmarks (aslam_remove_landmarks / aslam_select_beyond)
+    def landmark_capacity(self):
+        """Landmarks a filter of this context can hold: the least row length of a mask."""
+        return max(0, (self.max_landmark_count - 2) // 2)
+
+    def remove_landmarks(self, mask_or_indices, traj=None, stream=None):
+        """Remove landmarks from running filters; survivors keep their order and their values bit for bit, everything else a filter is stays.
+        `mask_or_indices`: a [batch, L] bool / uint8 array (entry (b, i) != 0 removes landmark i of filter b; L at least landmark_capacity()),
+        a uint8 torch tensor of that shape on the device, or, with `traj`, a list of landmark indices of that one filter.  Returns the new
+        dimensions [batch].  A refused call (AslamError) leaves the context unchanged."""
+        if traj is not None:
+            idx = np.asarray(mask_or_indices, np.int64).reshape(-1)
+            L = max(self.landmark_capacity(), 1)
+            if not 0 <= int(traj) < self.batch:
+                raise ValueError("traj out of range")
+            if idx.size and (idx.min() < 0 or idx.max() >= L):
+                raise ValueError(f"landmark index out of range (capacity {L})")
+            mask = np.zeros((self.batch, L), np.uint8)
+            mask[int(traj), idx] = 1
+            mask_or_indices = mask
+        if hasattr(mask_or_indices, "data_ptr"):
+            m = mask_or_indices
+            if m.dim() != 2 or m.shape[0] != self.batch or m.element_size() != 1 or not m.is_contiguous():
+                raise ValueError("a device mask is a contiguous [batch, L] uint8 / bool tensor")
+            self.remove_landmarks_ptr(m.data_ptr(), m.shape[1], True, stream)
+        else:
+            m = np.ascontiguousarray(np.asarray(mask_or_indices) != 0, np.uint8)
+            if m.ndim != 2 or m.shape[0] != self.batch:
+                raise ValueError("a mask is [batch, L]")
+            self.remove_landmarks_ptr(m.ctypes.data, m.shape[1], False, stream)
+        return np.array([self.dim(b) for b in range(self.batch)])
+
+    def remove_landmarks_ptr(self, mask_ptr, ld, is_device, stream=None):
+        """aslam_remove_landmarks as it is: a raw pointer (int or None) to a [batch][ld] u8 mask."""
+        _chk(core_lib().aslam_remove_landmarks(self._h, mask_ptr, int(ld), 1 if is_device else 0, stream))
+
+    def select_beyond(self, max_range, mask_ptr, ld, stream=None):
+        """Device mask [batch][ld] u8 at `mask_ptr` <- 1 where a landmark lies farther than max_range (a scalar, or one value per filter) from
+        its filter's own pose, 0 elsewhere (aslam_select_beyond).  Asynchronous on `stream`."""
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(max_range, np.float64), (self.batch,)))
+        _chk(core_lib().aslam_select_beyond(self._h, _ptr(r, ctypes.c_double), mask_ptr, int(ld), stream))
+
+    def prune_beyond(self, max_range, stream=None):
+        """select_beyond + remove_landmarks with a device mask that never leaves the GPU.  Returns the landmarks removed per filter [batch]."""
+        import torch
+
+        before = np.array([self.dim(b) for b in range(self.batch)])
+        ld = (max(self.landmark_capacity(), 1) + 15) // 16 * 16
+        mask = torch.empty((self.batch, ld), dtype=torch.uint8, device="cuda")
+        self.select_beyond(max_range, mask.data_ptr(), ld, stream)
+        after = self.remove_landmarks(mask, stream=stream)  # (synchronises: `mask` may go)
+        return (before - after) // 2
+
     def layout(self):
         npad, nbytes = ctypes.c_int(), ctypes.c_int64()
         _chk(core_lib().aslam_get_layout(self._h, ctypes.byref(npad), ctypes.byref(nbytes)))
@@ -669,6 +727,13 @@ class Node:
         p = Params()
         node_lib().aslam_node_get_params(self._h, ctypes.byref(p))
         return p
+
+    def remove_landmarks(self, indices):
+        """FilterNode::removeLandmarks: forget these landmarks (0-based indices) between two callbacks.  Returns the new dimension."""
+        idx = np.ascontiguousarray(indices, np.int32).reshape(-1)
+        if node_lib().aslam_node_remove_landmarks(self._h, _ptr(idx, ctypes.c_int32), len(idx)) != 0:
+            raise AslamError(node_lib().aslam_node_error().decode())
+        return self.N
 
     def wait_list(self, cap=4096):
         r, b, c = np.empty(cap, np.float32), np.empty(cap, np.float32), np.empty(cap, np.uint32)

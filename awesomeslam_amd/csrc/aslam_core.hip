@@ -24,6 +24,7 @@
 #include "ekf_large_launch.h"
 #include "scan_front.h"
 #include "snapshot.h"
+#include "prune.h"
 #if ASLAM_HAVE_UKF
 #include "ukf_small.h"
 #include "ukf_large.h"
@@ -1187,6 +1188,150 @@ int aslam_restore(aslam_ctx *c, const int32_t *records, const int32_t *trajs, in
         c->last_stream = st;
         hipLaunchKernelGGL(snapshot_unpack, snap_grid((int64_t)c->NP * c->NP / 2, count), dim3(SNAP_WG), 0, st, snap_ctx(c),
                            reinterpret_cast<const SnapDesc *>(c->snap_dev), count, src);
+        HIP_TRY(hipGetLastError());
+        return ASLAM_OK;
+}
+
+/* ---- removing landmarks (prune.h) ------------------------------------------------------------------------------------ */
+namespace
+{
+/// snap_reserve that keeps the first `keep` bytes of the old block when it has to grow
+int snap_reserve_keep(aslam_ctx *c, size_t bytes, size_t keep)
+{
+        if (bytes <= c->snap_cap)
+                return ASLAM_OK;
+        void *q = nullptr;
+        HIP_TRY(hipMalloc(&q, bytes));
+        hipError_t e = keep ? hipMemcpy(q, c->snap_dev, keep, hipMemcpyDeviceToDevice) : hipSuccess;
+        if (e != hipSuccess)
+        {
+                (void)hipFree(q);
+                HIP_TRY(e);
+        }
+        if (c->snap_dev)
+                (void)hipFree(c->snap_dev);
+        c->snap_dev = static_cast<char *>(q);
+        c->snap_cap = bytes;
+        return ASLAM_OK;
+}
+
+/// rows a mask must have: the landmarks a filter of this context can hold, (max_landmark_count - 3) / 2 rounded up
+int landmark_capacity(const aslam_ctx *c)
+{
+        return std::max(0, (c->cfg.max_landmark_count - 2) / 2);
+}
+
+/// null, or which of the arguments the two calls share is refused
+const char *bad_mask(const aslam_ctx *c, const void *mask, int ld, int is_device)
+{
+        if (!c)
+                return "null context";
+        if (!mask)
+                return "null mask";
+        if (ld < landmark_capacity(c))
+                return "ld is smaller than the context's landmark capacity, (max_landmark_count - 3) / 2 rounded up";
+        if (is_device && ((uintptr_t)mask & 15))
+                return "a device mask must be 16-byte aligned";
+        return nullptr;
+}
+} // namespace
+
+int aslam_select_beyond(aslam_ctx *c, const double *max_range, uint8_t *mask_dev, int ld, void *stream)
+{
+        if (const char *e = bad_mask(c, mask_dev, ld, 1))
+                return fail(ASLAM_ERR_ARG, std::string("aslam_select_beyond: ") + e);
+        if (!max_range)
+                return fail(ASLAM_ERR_ARG, "aslam_select_beyond: null max_range");
+        const int B = c->cfg.batch;
+        std::vector<double> r2((size_t)B);
+        for (int b = 0; b < B; ++b)
+        {
+                if (!std::isfinite(max_range[b]) || max_range[b] <= 0.0)
+                        return fail(ASLAM_ERR_ARG, "aslam_select_beyond: max_range[" + std::to_string(b) + "] must be finite and positive");
+                r2[b] = max_range[b] * max_range[b];
+        }
+        int rc = sync_ctx(c);
+        if (rc == ASLAM_OK)
+                rc = snap_reserve(c, (size_t)snap_pad64(8 * (int64_t)B));
+        if (rc != ASLAM_OK)
+                return rc;
+        HIP_TRY(hipMemcpy(c->snap_dev, r2.data(), sizeof(double) * B, hipMemcpyHostToDevice));
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        c->last_stream = st;
+        hipLaunchKernelGGL(prune_select_beyond, dim3((unsigned)B), dim3(PRUNE_WAVE), 0, st, (const double *)c->dv.X, (const int *)c->dv.n, c->NP,
+                           reinterpret_cast<const double *>(c->snap_dev), mask_dev, ld);
+        HIP_TRY(hipGetLastError());
+        return ASLAM_OK;
+}
+
+int aslam_remove_landmarks(aslam_ctx *c, const uint8_t *mask, int ld, int is_device, void *stream)
+{
+        if (const char *e = bad_mask(c, mask, ld, is_device))
+                return fail(ASLAM_ERR_ARG, std::string("aslam_remove_landmarks: ") + e);
+        int rc = sync_ctx(c);
+        if (rc != ASLAM_OK)
+                return rc;
+        const int B = c->cfg.batch;
+        const size_t NP = (size_t)c->NP;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        // staging: descriptors | what prune_map reports | the survivor lists | a host mask's copy | the records
+        const size_t o_meta = (size_t)snap_pad64((int64_t)sizeof(SnapDesc) * B);
+        const size_t o_src = o_meta + (size_t)snap_pad64((int64_t)sizeof(PruneMeta) * B);
+        const size_t o_mask = o_src + (size_t)snap_pad64((int64_t)(sizeof(int) * NP) * B);
+        const size_t o_blob = o_mask + (is_device ? 0 : (size_t)snap_pad64((int64_t)B * ld));
+        if ((rc = snap_reserve(c, o_blob)) != ASLAM_OK)
+                return rc;
+        const uint8_t *mdev = mask;
+        if (!is_device)
+        {
+                HIP_TRY(hipMemcpy(c->snap_dev + o_mask, mask, (size_t)B * ld, hipMemcpyHostToDevice));
+                mdev = reinterpret_cast<const uint8_t *>(c->snap_dev + o_mask);
+        }
+        c->last_stream = st;
+        hipLaunchKernelGGL(prune_map, dim3((unsigned)B), dim3(PRUNE_WAVE), 0, st, mdev, ld, (const int *)c->dv.n, (const int *)c->dv.sens_n,
+                           (const int *)c->dv.wait_n, c->NP, reinterpret_cast<int *>(c->snap_dev + o_src),
+                           reinterpret_cast<PruneMeta *>(c->snap_dev + o_meta));
+        HIP_TRY(hipGetLastError());
+        // the one copy and the one synchronisation of the call: n, n_new and the list sizes of the batch
+        std::vector<PruneMeta> meta((size_t)B);
+        HIP_TRY(hipMemcpyAsync(meta.data(), c->snap_dev + o_meta, sizeof(PruneMeta) * B, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        std::vector<SnapDesc> desc;
+        int n_max = 3;
+        for (int b = 0; b < B; ++b)
+        {
+                const PruneMeta &m = meta[b];
+                if (m.n < 3 || !(m.n & 1) || m.n >= c->cfg.max_landmark_count || (size_t)m.n > NP)
+                        return fail(ASLAM_ERR_STATE, "a filter of the context has an invalid dimension");
+                if (m.n_new < 3 || !(m.n_new & 1) || m.n_new > m.n)
+                        return fail(ASLAM_ERR_STATE, "aslam_remove_landmarks: the survivor count of filter " + std::to_string(b) + " is invalid");
+                if (m.n_new == m.n)
+                        continue; // loses nothing: not touched at all
+                desc.push_back(SnapDesc{0, b, m.n_new, std::min(std::max(m.sens_n, 0), c->dv.max_obs), std::min(std::max(m.wait_n, 0), c->dv.max_wait), {0, 0}});
+                n_max = std::max(n_max, m.n_new);
+        }
+        const int count = (int)desc.size();
+        if (count == 0)
+                return ASLAM_OK;
+        int64_t off = 64 + snap_pad64(8 * (int64_t)count);
+        for (SnapDesc &d : desc)
+        {
+                d.off = off;
+                off += snap_pad64(snap_record_bytes(d.n, d.sens_n, d.wait_n));
+        }
+        const int64_t total = off;
+        if ((rc = snap_reserve_keep(c, o_blob + (size_t)total, o_blob)) != ASLAM_OK)
+                return rc;
+        HIP_TRY(hipMemcpy(c->snap_dev, desc.data(), sizeof(SnapDesc) * count, hipMemcpyHostToDevice));
+        if (!is_device)
+                mdev = nullptr; // (the block may have moved; the mask is not read again)
+        const SnapDesc *ddev = reinterpret_cast<const SnapDesc *>(c->snap_dev);
+        char *blob = c->snap_dev + o_blob;
+        const SnapCtx sc = snap_ctx(c);
+        hipLaunchKernelGGL(prune_pack, snap_grid((int64_t)n_max * (n_max + 1) / 2, count), dim3(SNAP_WG), 0, st, sc, ddev, count, (uint32_t)c->cfg.filter,
+                           (uint64_t)total, reinterpret_cast<const int *>(c->snap_dev + o_src), blob);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(snapshot_unpack, snap_grid((int64_t)c->NP * c->NP / 2, count), dim3(SNAP_WG), 0, st, sc, ddev, count, (const char *)blob);
         HIP_TRY(hipGetLastError());
         return ASLAM_OK;
 }

@@ -169,6 +169,43 @@ void FilterNode::setParams(const aslam_params &p)
         prm = p;
 }
 
+// aslam_remove_landmarks is bound weakly like the entry points above: a core without it refuses the call, at run time.
+extern "C" {
+int aslam_remove_landmarks(aslam_ctx *, const uint8_t *, int, int, void *) __attribute__((weak));
+}
+
+void FilterNode::removeLandmarks(const std::vector<int> &indices)
+{
+        if (!aslam_remove_landmarks)
+                throw std::runtime_error("this core cannot remove landmarks");
+        const int mapped = (int)(N - 3) / 2;
+        std::vector<uint8_t> mask((size_t)std::max(mapped, (MAX_LANDMARK_COUNT - 2) / 2), 0);
+        for (int i : indices)
+        {
+                if (i < 0 || i >= mapped)
+                        throw std::runtime_error("removeLandmarks: landmark index " + std::to_string(i) + " out of range");
+                mask[i] = 1;
+        }
+        if (indices.empty())
+                return;
+        check(aslam_remove_landmarks(ctx, mask.data(), (int)mask.size(), 0, nullptr), "aslam_remove_landmarks");
+        // the host copies of X and Z, compacted the same way (nothing else is kept per landmark: the wait-list and the stored message stay)
+        uint32_t kept = 3;
+        for (int i = 0; i < mapped; ++i)
+        {
+                if (mask[i])
+                        continue;
+                for (int k = 0; k < 2; ++k, ++kept)
+                {
+                        param_X[kept] = param_X[3 + 2 * i + k];
+                        param_Z[kept] = param_Z[3 + 2 * i + k];
+                }
+        }
+        N = kept;
+        param_X.resize(N);
+        param_Z.resize(N);
+}
+
 Landmarks FilterNode::landmarks() const
 {
         Landmarks out;
@@ -453,6 +490,22 @@ int aslam_node_set_params(aslam_node *n, const aslam_params *p)
                 if (!p)
                         throw std::runtime_error("null argument");
                 n->impl->setParams(*p);
+                return 0;
+        }
+        catch (const std::exception &e)
+        {
+                g_node_err = e.what();
+                return -1;
+        }
+}
+
+int aslam_node_remove_landmarks(aslam_node *n, const int32_t *indices, int count)
+{
+        try
+        {
+                if (!n || count < 0 || (count && !indices))
+                        throw std::runtime_error("null argument");
+                n->impl->removeLandmarks(std::vector<int>(indices, indices + count));
                 return 0;
         }
         catch (const std::exception &e)

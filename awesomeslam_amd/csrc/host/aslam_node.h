@@ -114,6 +114,11 @@ class FilterNode
         {
                 return prm;
         }
+        /// Forget the landmarks with these indices (0-based, as landmarks() lists them): aslam_remove_landmarks on the core, and the host copies
+        /// of X and Z compacted the same way -- survivors keep their order.  Between two callbacks.  The wait-list and the stored sensor message
+        /// stay: a later sighting of a removed landmark is an unassociated observation like any other (see aslam_core.h).  Throws on an index
+        /// out of range (nothing is removed then) and with a core that lacks the entry point (bound weakly, like the innovation record).
+        void removeLandmarks(const std::vector<int> &indices);
 
       private:
         int filter;
@@ -181,6 +186,8 @@ int aslam_node_innovation(const aslam_node *n, double *nis, double *logdet);
 /* FilterNode::setParams / params(): 0, or -1 with aslam_node_error() (a refused field, or a core without run-time parameters). */
 int aslam_node_set_params(aslam_node *n, const aslam_params *params);
 int aslam_node_get_params(const aslam_node *n, aslam_params *params);
+/* FilterNode::removeLandmarks: 0, or -1 with aslam_node_error() (an index out of range, a core that cannot remove landmarks). */
+int aslam_node_remove_landmarks(aslam_node *n, const int32_t *indices, int count);
 /* Narrow `count` recorded odometry messages ([count][8]: px,py,qw,qx,qy,qz,vx,wz) the way cbOdom/updateZandA do
  * (ekf.cpp:139-142): pose[count][2], yaw[count] = quat2euler(...) as binary32, twist[count][2]. */
 void aslam_host_narrow_odom(int64_t count, const double *odom, double *pose, float *yaw, double *twist);

@@ -1,0 +1,170 @@
+// prune.h -- aslam_remove_landmarks / aslam_select_beyond (include/aslam_core.h): take landmarks out of running filters on the device.
+//
+//   prune_select_beyond   mask[b][i] = 1 where landmark i of filter b lies farther than max_range[b] from the filter's own pose
+//   prune_map             mask row + n of the filter -> the survivor list src[b][0 .. n_new) (source index of every kept row) and n_new[b]
+//   prune_pack            one complete record of snapshot.h per pruned filter, X, Z and P gathered through src: what snapshot_pack would
+//                         have written had the filter never held the removed landmarks
+//
+// The records then go through snapshot_unpack, unchanged, into their own slots: a slot whose dimension shrank is made a FRESH one exactly as
+// a restored slot is (zero padding, cleared scratch -- see the top of snapshot.h), and no second piece of code has to know what "fresh" means.
+// prune_pack takes every size from its descriptors, which the host validated; src holds indices below the padded dimension by construction
+// (prune_map clamps the landmark count it reads to what the padded row holds).
+#pragma once
+
+#include "snapshot.h"
+
+namespace aslam
+{
+constexpr int PRUNE_WAVE = 64;
+
+/// what prune_map reports per filter, for the one copy to the host
+struct PruneMeta
+{
+        int32_t n, n_new, sens_n, wait_n;
+};
+
+/// landmarks of a filter of dimension n, clamped to what a padded row of NP and a mask row of ld can name
+__device__ __forceinline__ int prune_landmarks(int n, int NP, int ld)
+{
+        int L = (n - 3) / 2;
+        const int cap = (NP - 3) / 2;
+        L = L > cap ? cap : L;
+        L = L > ld ? ld : L;
+        return L < 0 ? 0 : L;
+}
+
+/// grid: filters, block: one wave.  r2[b] = max_range[b]^2 (binary64, squared on the host).  The two products and the sum are rounded one by one
+/// (no FMA), so the comparison is defined bit for bit: dx*dx + dy*dy > r2.
+__global__ __launch_bounds__(PRUNE_WAVE) void prune_select_beyond(const double *__restrict__ X, const int *__restrict__ n, int NP,
+                                                                  const double *__restrict__ r2, uint8_t *__restrict__ mask, int ld)
+{
+        const int b = blockIdx.x;
+        const double *x = X + (size_t)b * NP;
+        const int L = prune_landmarks(n[b], NP, ld);
+        const double px = x[0], py = x[1], lim = r2[b];
+        uint8_t *row = mask + (size_t)b * ld;
+        for (int i = threadIdx.x; i < ld; i += PRUNE_WAVE)
+        {
+                uint8_t m = 0;
+                if (i < L)
+                {
+                        const double dx = x[3 + 2 * i] - px, dy = x[4 + 2 * i] - py;
+                        m = __dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)) > lim ? 1 : 0;
+                }
+                row[i] = m;
+        }
+}
+
+/// grid: filters, block: one wave.  src[b][0 .. n_new): 0, 1, 2, then 3 + 2i, 4 + 2i of every landmark i whose mask entry is 0, in order (ballot
+/// and popcount scan over chunks of 64 landmarks).  Mask entries at or beyond the filter's landmark count are not read.
+__global__ __launch_bounds__(PRUNE_WAVE) void prune_map(const uint8_t *__restrict__ mask, int ld, const int *__restrict__ n, const int *__restrict__ sens_n,
+                                                        const int *__restrict__ wait_n, int NP, int *__restrict__ src, PruneMeta *__restrict__ meta)
+{
+        const int b = blockIdx.x, lane = threadIdx.x;
+        const int nb = n[b];
+        const int L = prune_landmarks(nb, NP, ld);
+        const uint8_t *row = mask + (size_t)b * ld;
+        int *s = src + (size_t)b * NP;
+        if (lane < 3)
+                s[lane] = lane;
+        int kept = 0;
+        for (int i0 = 0; i0 < L; i0 += PRUNE_WAVE) // (L is the same in every lane: all of them reach the ballot)
+        {
+                const int i = i0 + lane;
+                const bool keep = i < L && row[i] == 0;
+                const unsigned long long votes = __ballot(keep);
+                if (keep)
+                {
+                        const int k = kept + __popcll(votes & ((1ull << lane) - 1ull));
+                        s[3 + 2 * k] = 3 + 2 * i;
+                        s[4 + 2 * k] = 4 + 2 * i;
+                }
+                kept += __popcll(votes);
+        }
+        if (lane == 0)
+                meta[b] = PruneMeta{nb, 3 + 2 * kept, sens_n[b], wait_n[b]};
+}
+
+/// The grid of snapshot_pack (row chunks x records).  d.n of a descriptor is the NEW dimension; src is indexed by the slot.  A double2 at an
+/// even column straddles two landmarks (column 3 + 2i is odd), so each half has a source of its own.
+__global__ __launch_bounds__(SNAP_WG) void prune_pack(SnapCtx c, const SnapDesc *__restrict__ desc, int count, uint32_t filter, uint64_t total,
+                                                      const int *__restrict__ src, char *__restrict__ blob)
+{
+        const int tid = threadIdx.x;
+        const size_t NP = (size_t)c.NP;
+        for (int f = blockIdx.y; f < count; f += gridDim.y)
+        {
+                const SnapDesc d = desc[f];
+                const int n = d.n, ld = n + 1, h = ld / 2;
+                const size_t slot = (size_t)d.slot;
+                const int *s = src + slot * NP;
+                char *rec = blob + d.off;
+                double2 *Pout = reinterpret_cast<double2 *>(rec + 64 + 16 * (size_t)ld);
+                const double *Pin = c.P + slot * NP * NP;
+                const int units = n * h;
+                for (int i = blockIdx.x * SNAP_WG + tid; i < units; i += gridDim.x * SNAP_WG)
+                {
+                        const int r = i / h, q = i - r * h;
+                        const double *prow = Pin + (size_t)s[r] * NP;
+                        double2 v;
+                        v.x = prow[s[2 * q]];
+                        v.y = 2 * q + 1 < n ? prow[s[2 * q + 1]] : 0.0;
+                        Pout[i] = v;
+                }
+                if (blockIdx.x != 0)
+                        continue;
+                // workgroup 0 of the record: X, Z, the lists, the record header, the table entry, the padding behind the record
+                double2 *Xout = reinterpret_cast<double2 *>(rec + 64);
+                for (int i = tid; i < 2 * h; i += SNAP_WG)
+                {
+                        const int q = i < h ? i : i - h;
+                        const double *in = (i < h ? c.X : c.Z) + slot * NP;
+                        double2 v;
+                        v.x = in[s[2 * q]];
+                        v.y = 2 * q + 1 < n ? in[s[2 * q + 1]] : 0.0;
+                        Xout[i] = v;
+                }
+                float *sens = reinterpret_cast<float *>(rec + 64 + 8 * (size_t)ld * (n + 2));
+                float *wrb = sens + 2 * d.sens_n;
+                uint32_t *wcnt = reinterpret_cast<uint32_t *>(wrb + 2 * d.wait_n);
+                for (int i = tid; i < 2 * d.sens_n; i += SNAP_WG)
+                        sens[i] = c.sens[slot * c.max_obs * 2 + i];
+                for (int i = tid; i < 2 * d.wait_n; i += SNAP_WG)
+                        wrb[i] = c.wait_rb[slot * c.max_wait * 2 + i];
+                for (int i = tid; i < d.wait_n; i += SNAP_WG)
+                        wcnt[i] = c.wait_cnt[slot * c.max_wait + i];
+                uint32_t *end = wcnt + d.wait_n;
+                const int tail = (int)((64 - (end - reinterpret_cast<uint32_t *>(rec)) * 4 % 64) % 64) / 4;
+                for (int i = tid; i < tail; i += SNAP_WG)
+                        end[i] = 0u;
+                if (tid == 0)
+                {
+                        SnapRecHeader r = {};
+                        r.n = n;
+                        r.flags = c.flags[slot] & SNAP_KNOWN_FLAGS;
+                        r.status = c.status[slot];
+                        r.sens_n = d.sens_n;
+                        r.wait_n = d.wait_n;
+                        r.ld = ld;
+                        r.A[0] = c.A[2 * slot];
+                        r.A[1] = c.A[2 * slot + 1];
+                        *reinterpret_cast<SnapRecHeader *>(rec) = r;
+                        reinterpret_cast<uint64_t *>(blob + 64)[f] = (uint64_t)d.off;
+                }
+                if (f == 0 && tid == 64)
+                {
+                        SnapBlobHeader bh = {};
+                        const char m[8] = {'A', 'S', 'L', 'S', 'N', 'P', '0', '1'};
+                        for (int i = 0; i < 8; ++i)
+                                bh.magic[i] = m[i];
+                        bh.version = SNAP_VERSION;
+                        bh.filter = filter;
+                        bh.count = (uint32_t)count;
+                        bh.total_bytes = total;
+                        *reinterpret_cast<SnapBlobHeader *>(blob) = bh;
+                        for (int i = count; i & 7; ++i)
+                                reinterpret_cast<uint64_t *>(blob + 64)[i] = 0;
+                }
+        }
+}
+} // namespace aslam

@@ -209,6 +209,26 @@ int aslam_innovation_enable(aslam_ctx *ctx, int on);
  * and after a callback in which slam() did not run */
 int aslam_get_innovation(aslam_ctx *ctx, int traj, double *nis, double *logdet);
 
+/* ---- removing landmarks from running filters ------------------------------------------------------- */
+/* mask [batch][ld] u8, host or device (is_device; a device mask 16-byte aligned): entry (b, i) != 0 removes landmark i of filter b.
+   Survivors keep their order and their values bit for bit (X, Z, rows and columns of P); N drops by 2 per removed landmark.  A, the init
+   flags, the status bits (sticky ones included), the stored sensor message, the wait-list and the parameters stay.  A filter that loses
+   nothing is not touched at all.  Synchronises the context first, then runs on `stream` like aslam_restore.
+   ld must be at least the context's landmark capacity, (max_landmark_count - 3) / 2 rounded up; entries at or beyond a filter's landmark
+   count are ignored.  One small device-to-host copy (the dimensions) and one synchronisation of `stream` happen inside the call; P never
+   leaves the device.  The last-callback innovation record of a pruned filter becomes NaN, as after aslam_restore.
+   An observation of a removed landmark no longer associates (nothing is left to associate it with): it goes to the wait-list like the
+   sighting of any unknown landmark and is promoted again, as a NEW landmark at the end of the state, after promote_count sightings.  The
+   wait-list itself is not edited: as for any sighting, an observation that falls within assoc_dist of an existing entry counts for that
+   entry, and an entry whose count has already passed promote_count does not promote a second time (the reference's rule, ekf.cpp:217-253).
+   ASLAM_ERR_ARG (the message names the argument) on a null argument, a too small ld or a misaligned device mask; a refused call leaves the
+   context unchanged. */
+int aslam_remove_landmarks(aslam_ctx *ctx, const uint8_t *mask, int ld, int is_device, void *stream);
+/* device mask [batch][ld] <- 1 where landmark i of filter b lies farther than max_range[b] (host array, [batch]) from X(0..1) of its filter,
+   0 everywhere else up to ld.  The comparison is dx*dx + dy*dy > max_range[b]^2 in binary64, each operation rounded on its own (no FMA).
+   Synchronises the context first, then runs on `stream`.  ASLAM_ERR_ARG as above, and on a max_range that is not finite or is <= 0. */
+int aslam_select_beyond(aslam_ctx *ctx, const double *max_range, uint8_t *mask_dev, int ld, void *stream);
+
 /* ---- read-back (synchronises the context's last stream) ------------------------------------------- */
 int aslam_get_dim(aslam_ctx *ctx, int traj, int *n);
 /* X[n], Z[n], P[n*n] row-major; any may be NULL */
