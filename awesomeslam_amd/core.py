@@ -29,12 +29,14 @@ CORE_SYMBOLS = (
     "aslam_replay_stats", "aslam_innovation_enable", "aslam_get_innovation",
     "aslam_params_default", "aslam_set_params", "aslam_get_params",
     "aslam_remove_landmarks", "aslam_select_beyond",
+    "aslam_get_sightings", "aslam_select_stale",
 )
 NODE_SYMBOLS = (
     "aslam_node_create", "aslam_node_create_at", "aslam_node_destroy", "aslam_node_error", "aslam_node_sensor", "aslam_node_odom",
     "aslam_node_odom_now", "aslam_node_dim", "aslam_node_get", "aslam_node_wait", "aslam_node_core",
     "aslam_host_narrow_odom", "aslam_node_enable_innovation", "aslam_node_innovation",
     "aslam_node_set_params", "aslam_node_get_params", "aslam_node_remove_landmarks",
+    "aslam_node_get_sightings", "aslam_node_remove_stale",
 )
 TRACE_FILE_SYMBOLS = (
     "aslam_trace_file_open", "aslam_trace_file_close", "aslam_trace_file_error", "aslam_trace_file_dims",
@@ -184,6 +186,8 @@ def core_lib():
         L.aslam_get_launch_info.argtypes = [vp, pi, pi, pi]
         L.aslam_remove_landmarks.argtypes = [vp, vp, ci, ci, vp]
         L.aslam_select_beyond.argtypes = [vp, pd, vp, ci, vp]
+        L.aslam_get_sightings.argtypes = [vp, ci, pu, pu, ci, pi, pu]
+        L.aslam_select_stale.argtypes = [vp, pu, vp, ci, vp]
         # include/aslam_snapshot.h
         p32, p64 = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)
         L.aslam_snapshot_record_bytes.restype = ctypes.c_int64
@@ -224,6 +228,8 @@ def node_lib():
         L.aslam_node_set_params.argtypes = [vp, ctypes.POINTER(Params)]
         L.aslam_node_get_params.argtypes = [vp, ctypes.POINTER(Params)]
         L.aslam_node_remove_landmarks.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ci]
+        L.aslam_node_get_sightings.argtypes = [vp, pu, pu, ci, pu]
+        L.aslam_node_remove_stale.argtypes = [vp, ctypes.c_uint32]
         # include/aslam_trace_file.h
         L.aslam_trace_file_error.restype = ctypes.c_char_p
         L.aslam_trace_file_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
@@ -633,6 +639,59 @@ class Core:
         after = self.remove_landmarks(mask, stream=stream)  # (synchronises: `mask` may go)
         return (before - after) // 2
 
+    # ---- sighting records and the forgetting policy (aslam_get_sightings / aslam_select_stale)
+    def sightings(self, traj=0, padded=False):
+        """(last_seen [L] u32, hits [L] u32, clock) of filter `traj` (padded: landmark_capacity() entries, zero from L on): the clock counts the callbacks in which the association ran, last_seen[i]
+        is the clock of the last one that associated an observation with landmark i (of its promotion before the first), hits[i] counts them.
+        The age of a landmark is clock - last_seen[i] in unsigned 32-bit arithmetic.  Synchronises."""
+        cap = max(self.landmark_capacity(), 1)
+        seen, hits = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
+        k, clk = ctypes.c_int(), ctypes.c_uint32()
+        _chk(core_lib().aslam_get_sightings(self._h, int(traj), _ptr(seen, ctypes.c_uint32), _ptr(hits, ctypes.c_uint32), cap, ctypes.byref(k),
+                                            ctypes.byref(clk)))
+        k = cap if padded else min(k.value, cap)
+        return seen[:k], hits[:k], clk.value
+
+    def select_stale(self, max_age, mask_ptr, ld, stream=None):
+        """Device mask [batch][ld] u8 at `mask_ptr` <- 1 where a landmark was last sighted more than max_age callbacks ago (a scalar, or one value
+        per filter; 0xFFFFFFFF = never), 0 elsewhere (aslam_select_stale).  Asynchronous on `stream`."""
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(max_age, np.uint32), (self.batch,)))
+        _chk(core_lib().aslam_select_stale(self._h, _ptr(a, ctypes.c_uint32), mask_ptr, int(ld), stream))
+
+    def _device_mask(self):
+        import torch
+
+        ld = (max(self.landmark_capacity(), 1) + 15) // 16 * 16
+        return torch.empty((self.batch, ld), dtype=torch.uint8, device="cuda"), ld
+
+    def prune_stale(self, max_age, stream=None):
+        """select_stale + remove_landmarks with a device mask that never leaves the GPU.  Returns the landmarks removed per filter [batch]."""
+        before = np.array([self.dim(b) for b in range(self.batch)])
+        mask, ld = self._device_mask()
+        self.select_stale(max_age, mask.data_ptr(), ld, stream)
+        after = self.remove_landmarks(mask, stream=stream)  # (synchronises: `mask` may go)
+        return (before - after) // 2
+
+    def replay_forget(self, t0, nsteps, period, max_age, poses_ptr=None, dims_ptr=None, stream=None):
+        """replay() with a forgetting policy: after every `period` callbacks (the last chunk may be shorter, and is pruned too) the landmarks
+        last sighted more than `max_age` callbacks ago are removed -- a host loop over replay, select_stale and remove_landmarks, nothing more.
+        Returns the dimensions after each prune, [n_chunks][batch].  Synchronises once per chunk.
+        The output buffers are CHUNK-MAJOR: chunk c's [batch][len_c][3] poses (and [batch][len_c] dimensions) follow those of chunk c - 1; the
+        stride of a kernel's outputs is its launch's nsteps, and the kernels take no separate stride."""
+        t0, nsteps, period = int(t0), int(nsteps), int(period)
+        if period < 1:
+            raise ValueError("period must be at least 1")
+        mask, ld = self._device_mask()
+        dims, done = [], 0
+        while done < nsteps:
+            k = min(period, nsteps - done)
+            self.replay(t0 + done, k, None if poses_ptr is None else poses_ptr + 8 * 3 * self.batch * done,
+                        None if dims_ptr is None else dims_ptr + 4 * self.batch * done, stream)
+            self.select_stale(max_age, mask.data_ptr(), ld, stream)
+            dims.append(self.remove_landmarks(mask, stream=stream))
+            done += k
+        return np.array(dims, np.int64).reshape(len(dims), self.batch)
+
     def layout(self):
         npad, nbytes = ctypes.c_int(), ctypes.c_int64()
         _chk(core_lib().aslam_get_layout(self._h, ctypes.byref(npad), ctypes.byref(nbytes)))
@@ -734,6 +793,21 @@ class Node:
         if node_lib().aslam_node_remove_landmarks(self._h, _ptr(idx, ctypes.c_int32), len(idx)) != 0:
             raise AslamError(node_lib().aslam_node_error().decode())
         return self.N
+
+    def sightings(self):
+        """(last_seen, hits, clock) as Core.sightings, from the mirror's own association (FilterNode::lastSeen / hits / clock)."""
+        L = (self.N - 3) // 2
+        seen, hits = np.zeros(max(L, 1), np.uint32), np.zeros(max(L, 1), np.uint32)
+        clk = ctypes.c_uint32()
+        node_lib().aslam_node_get_sightings(self._h, _ptr(seen, ctypes.c_uint32), _ptr(hits, ctypes.c_uint32), L, ctypes.byref(clk))
+        return seen[:L], hits[:L], clk.value
+
+    def remove_stale(self, max_age):
+        """FilterNode::removeStale: forget the landmarks last sighted more than max_age callbacks ago.  Returns how many went."""
+        k = node_lib().aslam_node_remove_stale(self._h, int(max_age))
+        if k < 0:
+            raise AslamError(node_lib().aslam_node_error().decode())
+        return k
 
     def wait_list(self, cap=4096):
         r, b, c = np.empty(cap, np.float32), np.empty(cap, np.float32), np.empty(cap, np.uint32)

@@ -91,13 +91,14 @@ struct aslam_ctx
 
 namespace
 {
-template <typename T> int dev_alloc(aslam_ctx *c, T **p, size_t count, std::vector<void *> &pool)
+template <typename T> int dev_alloc(aslam_ctx *c, T **p, size_t count, std::vector<void *> &pool, bool counted = true)
 {
         void *q = nullptr;
         HIP_TRY(hipMalloc(&q, count * sizeof(T)));
         HIP_TRY(hipMemset(q, 0, count * sizeof(T)));
         pool.push_back(q);
-        c->hbm_bytes += (int64_t)(count * sizeof(T));
+        if (counted) // (aslam_get_layout reports state and scratch)
+                c->hbm_bytes += (int64_t)(count * sizeof(T));
         *p = static_cast<T *>(q);
         return ASLAM_OK;
 }
@@ -220,6 +221,30 @@ template <typename F> void for_each_scratch(aslam_ctx *c, F &&f)
 #endif
 }
 
+/// The sighting record of filter `traj` when the host changes its dimension from n_old to n_new (aslam_grow, aslam_set_state): new landmarks
+/// are growth (last seen now, never sighted), entries at or beyond a lower landmark count become 0
+int resize_sightings(aslam_ctx *c, int traj, int n_old, int n_new)
+{
+        const size_t H = (size_t)c->NP / 2;
+        const size_t L_old = (size_t)std::max(0, (n_old - 3) / 2), L_new = (size_t)(n_new - 3) / 2;
+        DevView &d = c->dv;
+        uint32_t *seen = d.lm_seen + traj * H, *hits = d.lm_hits + traj * H;
+        if (L_new > L_old)
+        {
+                uint32_t clk = 0;
+                HIP_TRY(hipMemcpy(&clk, d.clock + traj, sizeof(clk), hipMemcpyDeviceToHost));
+                const std::vector<uint32_t> now(L_new - L_old, clk);
+                HIP_TRY(hipMemcpy(seen + L_old, now.data(), sizeof(uint32_t) * now.size(), hipMemcpyHostToDevice));
+                HIP_TRY(hipMemset(hits + L_old, 0, sizeof(uint32_t) * now.size()));
+        }
+        else if (L_new < H)
+        {
+                HIP_TRY(hipMemset(seen + L_new, 0, sizeof(uint32_t) * (H - L_new)));
+                HIP_TRY(hipMemset(hits + L_new, 0, sizeof(uint32_t) * (H - L_new)));
+        }
+        return ASLAM_OK;
+}
+
 /// initialize() for the whole batch: ekf.cpp:49-71 / ukf.cpp:49-67
 int init_state(aslam_ctx *c)
 {
@@ -232,6 +257,9 @@ int init_state(aslam_ctx *c)
         HIP_TRY(hipMemset(d.status, 0, sizeof(uint32_t) * B));
         HIP_TRY(hipMemset(d.sens_n, 0, sizeof(int) * B));
         HIP_TRY(hipMemset(d.wait_n, 0, sizeof(int) * B));
+        HIP_TRY(hipMemset(d.clock, 0, sizeof(uint32_t) * B));
+        HIP_TRY(hipMemset(d.lm_seen, 0, sizeof(uint32_t) * B * (NP / 2)));
+        HIP_TRY(hipMemset(d.lm_hits, 0, sizeof(uint32_t) * B * (NP / 2)));
         std::vector<int> n(B, 3), fl(B, FLAG_INIT_X | FLAG_INIT_Z);
         std::vector<double> A(2 * B, 0.0);
         for (size_t b = 0; b < B; ++b)
@@ -422,6 +450,8 @@ int aslam_create(const aslam_config *cfg, aslam_ctx **out)
         for_each_array(d, [&](auto *&p, size_t per, bool) {
                 if (large && same_slot(p, d.P))
                         take_large();
+                else if (same_slot(p, d.clock) || same_slot(p, d.lm_seen) || same_slot(p, d.lm_hits))
+                        rc = rc == ASLAM_OK ? dev_alloc(c, &p, B * per, c->owned, false) : rc; // (bookkeeping, outside the reported bytes)
                 else
                         take(p, per);
                 if (same_slot(p, d.A))
@@ -567,6 +597,10 @@ int aslam_set_state(aslam_ctx *c, int traj, int n, const double *X, const double
         if (P && (rc = upload_P(c, traj, n, P)) != ASLAM_OK)
                 return rc;
         const int fl = 0; // a filter whose state was handed over is past both init flags
+        int n_old = 0;
+        HIP_TRY(hipMemcpy(&n_old, d.n + traj, sizeof(int), hipMemcpyDeviceToHost));
+        if (n != n_old && (rc = resize_sightings(c, traj, n_old, n)) != ASLAM_OK)
+                return rc;
         HIP_TRY(hipMemcpy(d.n + traj, &n, sizeof(int), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d.flags + traj, &fl, sizeof(int), hipMemcpyHostToDevice));
         return ASLAM_OK;
@@ -600,6 +634,8 @@ int aslam_grow(aslam_ctx *c, int traj, int n_new, const double *x_seed, const do
         HIP_TRY(hipMemcpy(d.Z + traj * NP + n_old, z_seed, sizeof(double) * k, hipMemcpyHostToDevice));
         // conservativeResizeLike(Identity * UKF_KP_LANDMARK_POSE): new rows (new columns of old rows are zero padding already)
         rc = grow_P_rows(c, traj, n_old, n_new);
+        if (rc == ASLAM_OK)
+                rc = resize_sightings(c, traj, n_old, n_new);
         if (rc != ASLAM_OK)
                 return rc;
         HIP_TRY(hipMemcpy(d.n + traj, &n_new, sizeof(int), hipMemcpyHostToDevice));
@@ -931,6 +967,26 @@ int aslam_get_status(aslam_ctx *c, int traj, uint32_t *status_bits)
         return ASLAM_OK;
 }
 
+int aslam_get_sightings(aslam_ctx *c, int traj, uint32_t *last_seen, uint32_t *hits, int cap, int *n_landmarks, uint32_t *clock)
+{
+        int n = 0;
+        int rc = aslam_get_dim(c, traj, &n);
+        if (rc != ASLAM_OK)
+                return rc;
+        const DevView &d = c->dv;
+        const size_t H = (size_t)c->NP / 2;
+        const int L = std::max(0, (n - 3) / 2), k = std::min((int)H, cap); // (beyond L the stored record is zero, and is handed out as it is)
+        if (last_seen && k > 0)
+                HIP_TRY(hipMemcpy(last_seen, d.lm_seen + traj * H, sizeof(uint32_t) * k, hipMemcpyDeviceToHost));
+        if (hits && k > 0)
+                HIP_TRY(hipMemcpy(hits, d.lm_hits + traj * H, sizeof(uint32_t) * k, hipMemcpyDeviceToHost));
+        if (clock)
+                HIP_TRY(hipMemcpy(clock, d.clock + traj, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (n_landmarks)
+                *n_landmarks = L;
+        return ASLAM_OK;
+}
+
 int aslam_get_layout(aslam_ctx *c, int *padded_dim, int64_t *hbm_bytes)
 {
         if (!c)
@@ -1189,6 +1245,10 @@ int aslam_restore(aslam_ctx *c, const int32_t *records, const int32_t *trajs, in
         hipLaunchKernelGGL(snapshot_unpack, snap_grid((int64_t)c->NP * c->NP / 2, count), dim3(SNAP_WG), 0, st, snap_ctx(c),
                            reinterpret_cast<const SnapDesc *>(c->snap_dev), count, src);
         HIP_TRY(hipGetLastError());
+        // (format v1 does not carry the sighting record: the restored slots start at clock 0, every landmark at age 0)
+        hipLaunchKernelGGL(sight_clear, dim3((unsigned)count), dim3(PRUNE_WAVE), 0, st, reinterpret_cast<const SnapDesc *>(c->snap_dev), c->NP,
+                           c->dv.clock, c->dv.lm_seen, c->dv.lm_hits);
+        HIP_TRY(hipGetLastError());
         return ASLAM_OK;
 }
 
@@ -1264,6 +1324,27 @@ int aslam_select_beyond(aslam_ctx *c, const double *max_range, uint8_t *mask_dev
         return ASLAM_OK;
 }
 
+int aslam_select_stale(aslam_ctx *c, const uint32_t *max_age, uint8_t *mask_dev, int ld, void *stream)
+{
+        if (const char *e = bad_mask(c, mask_dev, ld, 1))
+                return fail(ASLAM_ERR_ARG, std::string("aslam_select_stale: ") + e);
+        if (!max_age)
+                return fail(ASLAM_ERR_ARG, "aslam_select_stale: null max_age");
+        const int B = c->cfg.batch;
+        int rc = sync_ctx(c);
+        if (rc == ASLAM_OK)
+                rc = snap_reserve(c, (size_t)snap_pad64(4 * (int64_t)B));
+        if (rc != ASLAM_OK)
+                return rc;
+        HIP_TRY(hipMemcpy(c->snap_dev, max_age, sizeof(uint32_t) * B, hipMemcpyHostToDevice));
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        c->last_stream = st;
+        hipLaunchKernelGGL(prune_select_stale, dim3((unsigned)B), dim3(PRUNE_WAVE), 0, st, (const uint32_t *)c->dv.clock, (const uint32_t *)c->dv.lm_seen,
+                           (const int *)c->dv.n, c->NP, reinterpret_cast<const uint32_t *>(c->snap_dev), mask_dev, ld);
+        HIP_TRY(hipGetLastError());
+        return ASLAM_OK;
+}
+
 int aslam_remove_landmarks(aslam_ctx *c, const uint8_t *mask, int ld, int is_device, void *stream)
 {
         if (const char *e = bad_mask(c, mask, ld, is_device))
@@ -1332,6 +1413,10 @@ int aslam_remove_landmarks(aslam_ctx *c, const uint8_t *mask, int ld, int is_dev
                            (uint64_t)total, reinterpret_cast<const int *>(c->snap_dev + o_src), blob);
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(snapshot_unpack, snap_grid((int64_t)c->NP * c->NP / 2, count), dim3(SNAP_WG), 0, st, sc, ddev, count, (const char *)blob);
+        HIP_TRY(hipGetLastError());
+        // the sighting record follows its landmarks; the clock stays (a restore clears both, a prune must not: the kernel is launched here, not in the unpack)
+        hipLaunchKernelGGL(sight_compact, dim3((unsigned)B), dim3(PRUNE_WAVE), 0, st, reinterpret_cast<const int *>(c->snap_dev + o_src),
+                           reinterpret_cast<const PruneMeta *>(c->snap_dev + o_meta), c->NP, c->dv.lm_seen, c->dv.lm_hits);
         HIP_TRY(hipGetLastError());
         return ASLAM_OK;
 }

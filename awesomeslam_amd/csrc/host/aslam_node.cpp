@@ -64,7 +64,7 @@ float quat2euler(float w, float x, float y, float z)
 FilterNode::FilterNode(int filter_, int max_landmark_count, int device, double now_init)
     : filter(filter_), MAX_LANDMARK_COUNT(max_landmark_count), ctx(nullptr), N(3), init_z(true), init_x(true),
       last_time((float)now_init), // ekf.cpp:54: last_time = ros::Time::now().toSec(), a float member (ekf.h:98)
-      growth_refused(false), slam_ran(false), prm ASLAM_PARAMS_DEFAULT_INIT, param_X(3, 0.0), param_Z(3, 0.0), a00(1.0), a10(0.0)
+      growth_refused(false), slam_ran(false), prm ASLAM_PARAMS_DEFAULT_INIT, param_X(3, 0.0), param_Z(3, 0.0), a00(1.0), a10(0.0), sight_clock(0)
 {
         aslam_config cfg = {};
         cfg.filter = filter;
@@ -189,12 +189,14 @@ void FilterNode::removeLandmarks(const std::vector<int> &indices)
         if (indices.empty())
                 return;
         check(aslam_remove_landmarks(ctx, mask.data(), (int)mask.size(), 0, nullptr), "aslam_remove_landmarks");
-        // the host copies of X and Z, compacted the same way (nothing else is kept per landmark: the wait-list and the stored message stay)
+        // the host copies of X and Z and the sighting record, compacted the same way (the wait-list and the stored message stay)
         uint32_t kept = 3;
         for (int i = 0; i < mapped; ++i)
         {
                 if (mask[i])
                         continue;
+                lm_seen[(kept - 3) / 2] = lm_seen[i];
+                lm_hits[(kept - 3) / 2] = lm_hits[i];
                 for (int k = 0; k < 2; ++k, ++kept)
                 {
                         param_X[kept] = param_X[3 + 2 * i + k];
@@ -204,6 +206,18 @@ void FilterNode::removeLandmarks(const std::vector<int> &indices)
         N = kept;
         param_X.resize(N);
         param_Z.resize(N);
+        lm_seen.resize((N - 3) / 2);
+        lm_hits.resize((N - 3) / 2);
+}
+
+int FilterNode::removeStale(uint32_t max_age)
+{
+        std::vector<int> stale;
+        for (size_t i = 0; i < lm_seen.size(); ++i)
+                if (sight_clock - lm_seen[i] > max_age)
+                        stale.push_back((int)i);
+        removeLandmarks(stale);
+        return (int)stale.size();
 }
 
 Landmarks FilterNode::landmarks() const
@@ -225,6 +239,8 @@ void FilterNode::updateZ(const Odometry &msg, float delta_time)
         param_Z[2] = quat2euler(msg.qw, msg.qx, msg.qy, msg.qz);
 
         const uint32_t mapped = (N - 3) / 2;
+        sight_clock += 1;
+        std::vector<char> sighted(mapped, 0); // several observations on one landmark are one hit
         for (LaserData &obs : sensor_landmark)
         {
                 obs.bearing = normalizeAngle(obs.bearing);
@@ -248,12 +264,20 @@ void FilterNode::updateZ(const Odometry &msg, float delta_time)
                         {
                                 param_Z[3 + 2 * best] = obs.range;
                                 param_Z[4 + 2 * best] = obs.bearing;
+                                sighted[best] = 1;
                                 associated = true;
                         }
                 }
                 if (!associated)
                         updateNewLandmarkWait(obs);
         }
+
+        for (uint32_t k = 0; k < mapped; ++k)
+                if (sighted[k])
+                {
+                        lm_seen[k] = sight_clock;
+                        lm_hits[k] += 1;
+                }
 
         std::vector<LaserData> promoted;
         for (auto &entry : new_landmark_wait)
@@ -315,6 +339,8 @@ void FilterNode::updateNewLandmark(const std::vector<LaserData> &new_landmark)
         N = grown;
         param_X.resize(N, 0.0);
         param_Z.resize(N, 0.0);
+        lm_seen.resize((N - 3) / 2, sight_clock); // promoted now, never sighted as a landmark
+        lm_hits.resize((N - 3) / 2, 0u);
         for (size_t k = 0; k < new_landmark.size(); ++k)
         {
                 const uint32_t i = cacheN + 2 * (uint32_t)k;
@@ -507,6 +533,35 @@ int aslam_node_remove_landmarks(aslam_node *n, const int32_t *indices, int count
                         throw std::runtime_error("null argument");
                 n->impl->removeLandmarks(std::vector<int>(indices, indices + count));
                 return 0;
+        }
+        catch (const std::exception &e)
+        {
+                g_node_err = e.what();
+                return -1;
+        }
+}
+
+int aslam_node_get_sightings(const aslam_node *n, uint32_t *last_seen, uint32_t *hits, int cap, uint32_t *clock)
+{
+        const auto &s = n->impl->lastSeen();
+        const auto &h = n->impl->hits();
+        const int k = std::max(0, std::min<int>(cap, (int)s.size()));
+        if (last_seen)
+                std::copy(s.begin(), s.begin() + k, last_seen);
+        if (hits)
+                std::copy(h.begin(), h.begin() + k, hits);
+        if (clock)
+                *clock = n->impl->clock();
+        return (int)s.size();
+}
+
+int aslam_node_remove_stale(aslam_node *n, uint32_t max_age)
+{
+        try
+        {
+                if (!n)
+                        throw std::runtime_error("null argument");
+                return n->impl->removeStale(max_age);
         }
         catch (const std::exception &e)
         {

@@ -119,6 +119,23 @@ class FilterNode
         /// stay: a later sighting of a removed landmark is an unassociated observation like any other (see aslam_core.h).  Throws on an index
         /// out of range (nothing is removed then) and with a core that lacks the entry point (bound weakly, like the innovation record).
         void removeLandmarks(const std::vector<int> &indices);
+        /// The sighting record of aslam_core.h (aslam_get_sightings), kept here because this mirror does the association itself: the clock counts the
+        /// callbacks in which updateZ ran, lastSeen()[i] is the clock of the last one that associated an observation with landmark i (of its promotion
+        /// before the first), hits()[i] counts them.  removeLandmarks moves the records with their landmarks and keeps the clock.
+        uint32_t clock() const
+        {
+                return sight_clock;
+        }
+        const std::vector<uint32_t> &lastSeen() const
+        {
+                return lm_seen;
+        }
+        const std::vector<uint32_t> &hits() const
+        {
+                return lm_hits;
+        }
+        /// removeLandmarks of every landmark whose age, clock() - lastSeen()[i] in unsigned 32-bit arithmetic, exceeds max_age; returns how many went
+        int removeStale(uint32_t max_age);
 
       private:
         int filter;
@@ -136,6 +153,8 @@ class FilterNode
         std::vector<std::pair<LaserData, uint32_t>> new_landmark_wait;
         std::vector<double> param_X, param_Z; // host copies; P and the authoritative X are device-resident
         double a00, a10;                      // param.A(0,0), param.A(1,0) (EKF)
+        uint32_t sight_clock;
+        std::vector<uint32_t> lm_seen, lm_hits; // one entry per mapped landmark
 
         void updateZ(const Odometry &msg, float delta_time);
         void updateNewLandmarkWait(const LaserData &data);
@@ -188,6 +207,11 @@ int aslam_node_set_params(aslam_node *n, const aslam_params *params);
 int aslam_node_get_params(const aslam_node *n, aslam_params *params);
 /* FilterNode::removeLandmarks: 0, or -1 with aslam_node_error() (an index out of range, a core that cannot remove landmarks). */
 int aslam_node_remove_landmarks(aslam_node *n, const int32_t *indices, int count);
+/* FilterNode::lastSeen / hits / clock: up to `cap` entries into last_seen and hits (either may be NULL), the clock into *clock (may be NULL);
+ * returns the number of landmarks. */
+int aslam_node_get_sightings(const aslam_node *n, uint32_t *last_seen, uint32_t *hits, int cap, uint32_t *clock);
+/* FilterNode::removeStale: the number of landmarks removed, or -1 with aslam_node_error(). */
+int aslam_node_remove_stale(aslam_node *n, uint32_t max_age);
 /* Narrow `count` recorded odometry messages ([count][8]: px,py,qw,qx,qy,qz,vx,wz) the way cbOdom/updateZandA do
  * (ekf.cpp:139-142): pose[count][2], yaw[count] = quat2euler(...) as binary32, twist[count][2]. */
 void aslam_host_narrow_odom(int64_t count, const double *odom, double *pose, float *yaw, double *twist);

@@ -24,6 +24,9 @@ template <class Filter> struct Node
         ros::NodeHandle nh;
         ros::Subscriber sub_odom, sub_sensor_landmark;
         ros::Publisher pub_landmark;
+        // forgetting policy (~forget_after, ~forget_period; in callbacks): every forget_period counted callbacks the landmarks last sighted more than
+        // forget_after callbacks ago are removed (FilterNode::removeStale).  forget_after = 0, the default: never
+        uint32_t forget_after = 0, forget_period = 1;
 
         /// the reference's constructor (ekf.cpp:39-46): subscribe, advertise, initialize() -- whose `last_time = ros::Time::now().toSec()`
         /// (ekf.cpp:54) is the `now_init` of the mirror
@@ -42,6 +45,8 @@ template <class Filter> struct Node
                                         msg->twist.twist.linear.x,    msg->twist.twist.angular.z};
                 if (!filter.cbOdom(o, ros::Time::now().toSec()))
                         return; // no sensor message yet (ekf.cpp:76-77)
+                if (forget_after && filter.clock() % forget_period == 0)
+                        filter.removeStale(forget_after);
                 const aslam::Landmarks l = filter.landmarks(); // convertToLandmarkMsg, common.h:93-108
                 awesome_slam_msgs::Landmarks out;
                 out.x = l.x;
@@ -82,7 +87,12 @@ template <class Filter> int node_main(int argc, char **argv, const char *node_na
         ros::param::param("~promote_count", promote_count, (int)def.promote_count);
         prm.assoc_dist = (float)assoc_dist;
         prm.promote_count = promote_count < 0 ? 0u : (uint32_t)promote_count; // (0 is refused by setParams, with the field's name)
+        int forget_after = 0, forget_period = 1;
+        ros::param::param("~forget_after", forget_after, 0);
+        ros::param::param("~forget_period", forget_period, 1);
         Node<Filter> a(max_landmark_count, queue_size);
+        a.forget_after = forget_after < 0 ? 0u : (uint32_t)forget_after;
+        a.forget_period = forget_period < 1 ? 1u : (uint32_t)forget_period;
         a.filter.setParams(prm); // before the first callback: p0_pose applies
         std::cerr << banner;
         while (ros::ok())

@@ -64,6 +64,11 @@ struct DevView
         uint32_t *wait_cnt; // [B][max_wait]
         int *wait_n;        // [B]
         const aslam_params *prm; // [B] noise and association parameters (aslam_set_params)
+        // sighting record (aslam_get_sightings): written by small_frontend, read by nothing a filter computes.  Ages are clock - lm_seen in
+        // unsigned 32-bit arithmetic: right as long as no landmark goes unseen for 2^32 callbacks of its filter
+        uint32_t *clock;   // [B] callbacks of this filter in which updateZandA / updateZ ran
+        uint32_t *lm_seen; // [B][NP/2] clock of the last callback that associated an observation with landmark k (of its promotion before the first)
+        uint32_t *lm_hits; // [B][NP/2] callbacks that did
         // bound trace
         int64_t T;
         const double *tr_pose;
@@ -100,6 +105,9 @@ template <typename F> void for_each_array(DevView &d, F &&f)
         f(d.wait_cnt, mw, false);
         f(d.wait_n, 1, false);
         f(d.prm, 1, false);
+        f(d.clock, 1, false);
+        f(d.lm_seen, np / 2, false);
+        f(d.lm_hits, np / 2, false);
 }
 
 #ifdef ASLAM_STAMPS
@@ -144,7 +152,7 @@ struct StepArgs
 struct SmallShared
 {
         int n, flags, sn, wn, nnew, grew, grow_from, any_miss, any_promote, obs_new, nobs, skip;
-        uint32_t status;
+        uint32_t status, clock;
         float vx, az, dt, yaw;
         double px, py, tvx, twz, a00, a10;
         aslam_params prm;     // this filter's parameters: read from HBM once at launch start (small_load), wave-uniform LDS reads at the use sites
@@ -1186,6 +1194,8 @@ template <int MODE> __device__ __forceinline__ void small_load(const DevView &d,
                 sm.status = d.status[b];
                 sm.sn = d.sens_n[b];
                 sm.wn = d.wait_n[b];
+                if (MODE == MODE_REPLAY)
+                        sm.clock = d.clock[b];
                 sm.a00 = d.A[2 * b];
                 sm.a10 = d.A[2 * b + 1];
                 sm.prm = d.prm[b];
@@ -1232,6 +1242,7 @@ template <int MODE> __device__ __forceinline__ void small_store(const DevView &d
                 {
                         d.sens_n[b] = sm.sn;
                         d.wait_n[b] = sm.wn;
+                        d.clock[b] = sm.clock;
                 }
                 for (int j = tid; j < sm.sn; j += SMALL_WG)
                 {
@@ -1391,10 +1402,16 @@ __device__ __forceinline__ bool small_frontend(const DevView &d, const SmallLds 
                 sZ[0] = sm.px;
                 sZ[1] = sm.py;
                 sZ[2] = (double)sm.yaw;
+                sm.clock += 1; // this callback counts: the first one has clock 1
         }
         __syncthreads();
         const int n0 = sm.n;
         const int nl = (n0 - 3) / 2;
+        // the sighting record of this filter (DevView::lm_seen / lm_hits).  The count of this thread's first landmark is fetched here, a whole scan
+        // ahead of its use, so that the read-modify-write behind the scan's barrier is a store alone on the path
+        const uint32_t clk = sm.clock;
+        uint32_t *const seen = d.lm_seen + (size_t)b * (d.NP / 2), *const hits = d.lm_hits + (size_t)b * (d.NP / 2);
+        const uint32_t hits0 = tid < nl ? hits[tid] : 0u;
         const float assoc_dist = sm.prm.assoc_dist; // MIN_DIST_THRESH (config.h:43)
         for (int j = tid; j < sm.sn; j += SMALL_WG)
         {
@@ -1574,6 +1591,16 @@ __device__ __forceinline__ bool small_frontend(const DevView &d, const SmallLds 
                         sZ[4 + sCid[j]] = (double)sSb[j];
                 }
         }
+        // sighted landmarks (at least one observation associated: exactly the ones whose Z entries were just rewritten), straight to HBM, before
+        // the wait-list walk reuses sNew for the promotions
+        for (int k = tid; k < nl; k += SMALL_WG)
+        {
+                if (sNew[k] >= 0)
+                {
+                        seen[k] = clk;
+                        hits[k] = (k == tid ? hits0 : hits[k]) + 1u;
+                }
+        }
         FE_STAMP(8); // combine + Z
         if (sm.any_miss)
         {
@@ -1728,6 +1755,8 @@ __device__ __forceinline__ bool small_frontend(const DevView &d, const SmallLds 
                                                 sZ[n0 + 2 * k + 1] = zb;
                                                 sX[n0 + 2 * k] = sZ[0] + zr * cos(sZ[2] + zb);
                                                 sX[n0 + 2 * k + 1] = sZ[1] + zr * sin(sZ[2] + zb);
+                                                seen[nl + k] = clk; // promoted now, never sighted as a landmark
+                                                hits[nl + k] = 0u;
                                         }
                                         sm.grow_from = n0;
                                         sm.n = nn;

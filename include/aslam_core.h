@@ -212,8 +212,9 @@ int aslam_get_innovation(aslam_ctx *ctx, int traj, double *nis, double *logdet);
 /* ---- removing landmarks from running filters ------------------------------------------------------- */
 /* mask [batch][ld] u8, host or device (is_device; a device mask 16-byte aligned): entry (b, i) != 0 removes landmark i of filter b.
    Survivors keep their order and their values bit for bit (X, Z, rows and columns of P); N drops by 2 per removed landmark.  A, the init
-   flags, the status bits (sticky ones included), the stored sensor message, the wait-list and the parameters stay.  A filter that loses
-   nothing is not touched at all.  Synchronises the context first, then runs on `stream` like aslam_restore.
+   flags, the status bits (sticky ones included), the stored sensor message, the wait-list, the parameters and the sighting clock stay; the
+   sighting records (below) move with their landmarks.  The mask is not read after the call returns.  A filter that loses nothing is not
+   touched at all.  Synchronises the context first, then runs on `stream` like aslam_restore.
    ld must be at least the context's landmark capacity, (max_landmark_count - 3) / 2 rounded up; entries at or beyond a filter's landmark
    count are ignored.  One small device-to-host copy (the dimensions) and one synchronisation of `stream` happen inside the call; P never
    leaves the device.  The last-callback innovation record of a pruned filter becomes NaN, as after aslam_restore.
@@ -229,6 +230,27 @@ int aslam_remove_landmarks(aslam_ctx *ctx, const uint8_t *mask, int ld, int is_d
    Synchronises the context first, then runs on `stream`.  ASLAM_ERR_ARG as above, and on a max_range that is not finite or is <= 0. */
 int aslam_select_beyond(aslam_ctx *ctx, const double *max_range, uint8_t *mask_dev, int ld, void *stream);
 
+/* ---- sighting records: when to remove a landmark --------------------------------------------------- */
+/* Every filter keeps a clock and two numbers per landmark, written on the device by the front end of aslam_replay and read by nothing a
+   filter computes:
+     clock       callbacks of this filter in which updateZandA / updateZ ran (a callback that returns before the first sensor message does
+                 not count); the first counted callback has clock 1
+     last_seen   clock of the last callback in which the association walk gave landmark i at least one observation -- the callbacks that
+                 rewrite Z(3+2i), Z(4+2i); a re-walked stored message counts, as it does for the reference's wait-list counts -- or, before
+                 the first such callback, the clock of its promotion
+     hits        callbacks in which it was sighted (several observations in one callback are one hit; a fresh landmark has 0)
+   The age of a landmark is clock - last_seen in unsigned 32-bit arithmetic, which is right as long as no landmark goes unseen for 2^32
+   callbacks.  aslam_reset zeroes everything.  aslam_grow and an aslam_set_state that raises the dimension enter the new landmarks as
+   promoted now (last_seen = clock, hits = 0); an aslam_set_state that lowers it zeroes the entries beyond.  aslam_remove_landmarks keeps the
+   clock and moves the records with their landmarks.  aslam_restore sets clock and records of the restored slots to 0 (every landmark at age
+   0): snapshot format 1 does not carry them.  The per-callback seam (aslam_*_step) runs no association and leaves all of it alone. */
+/* last_seen[cap], hits[cap] (either may be NULL), *n_landmarks, *clock of filter traj; synchronises like the getters */
+/* (min(cap, padded_dim / 2) entries are written: those at or beyond *n_landmarks are the zeros the record holds there) */
+int aslam_get_sightings(aslam_ctx *ctx, int traj, uint32_t *last_seen, uint32_t *hits, int cap, int *n_landmarks, uint32_t *clock);
+/* device mask [batch][ld] <- 1 where clock[b] - lm_seen[b][i] > max_age[b] (host array [batch]; 0xFFFFFFFF = never), 0 elsewhere up to ld */
+int aslam_select_stale(aslam_ctx *ctx, const uint32_t *max_age, uint8_t *mask_dev, int ld, void *stream);
+/* (the mask is aslam_remove_landmarks' and aslam_select_beyond's: the same shape, synchronisation and ASLAM_ERR_ARG refusals) */
+
 /* ---- read-back (synchronises the context's last stream) ------------------------------------------- */
 int aslam_get_dim(aslam_ctx *ctx, int traj, int *n);
 /* X[n], Z[n], P[n*n] row-major; any may be NULL */
@@ -239,7 +261,8 @@ int aslam_get_landmarks(aslam_ctx *ctx, int traj, double *x, double *y, int *n_l
 /* wait-list: up to `cap` entries of (range, bearing, count); *size = entries held */
 int aslam_get_wait(aslam_ctx *ctx, int traj, float *range, float *bearing, uint32_t *count, int cap, int *size);
 int aslam_get_status(aslam_ctx *ctx, int traj, uint32_t *status_bits);
-/* padded row length of the device layout (multiple of 16) and bytes of HBM held, for reporting */
+/* padded row length of the device layout (multiple of 16) and bytes of HBM held by the filters' state and scratch, for reporting (the
+   sighting records, 4 + 4 * padded_dim bytes per filter, are not in the count) */
 int aslam_get_layout(aslam_ctx *ctx, int *padded_dim, int64_t *hbm_bytes);
 /* name + launch geometry of the kernel aslam_replay uses for this context (for profiles / bench reports) */
 int aslam_kernel_info(aslam_ctx *ctx, char *name, int name_cap, int *grid, int *block, int *lds_bytes);
