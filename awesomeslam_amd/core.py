@@ -30,13 +30,14 @@ CORE_SYMBOLS = (
     "aslam_params_default", "aslam_set_params", "aslam_get_params",
     "aslam_remove_landmarks", "aslam_select_beyond",
     "aslam_get_sightings", "aslam_select_stale",
+    "aslam_sighted_update_enable", "aslam_get_sighted", "aslam_ekf_step_sighted", "aslam_ekf_step_batch_sighted",
 )
 NODE_SYMBOLS = (
     "aslam_node_create", "aslam_node_create_at", "aslam_node_destroy", "aslam_node_error", "aslam_node_sensor", "aslam_node_odom",
     "aslam_node_odom_now", "aslam_node_dim", "aslam_node_get", "aslam_node_wait", "aslam_node_core",
     "aslam_host_narrow_odom", "aslam_node_enable_innovation", "aslam_node_innovation",
     "aslam_node_set_params", "aslam_node_get_params", "aslam_node_remove_landmarks",
-    "aslam_node_get_sightings", "aslam_node_remove_stale",
+    "aslam_node_get_sightings", "aslam_node_remove_stale", "aslam_node_set_sighted_only",
 )
 TRACE_FILE_SYMBOLS = (
     "aslam_trace_file_open", "aslam_trace_file_close", "aslam_trace_file_error", "aslam_trace_file_dims",
@@ -188,6 +189,11 @@ def core_lib():
         L.aslam_select_beyond.argtypes = [vp, pd, vp, ci, vp]
         L.aslam_get_sightings.argtypes = [vp, ci, pu, pu, ci, pi, pu]
         L.aslam_select_stale.argtypes = [vp, pu, vp, ci, vp]
+        pb = ctypes.POINTER(ctypes.c_uint8)
+        L.aslam_sighted_update_enable.argtypes = [vp, ci]
+        L.aslam_get_sighted.argtypes = [vp, ci, pb, ci, pi]
+        L.aslam_ekf_step_sighted.argtypes = [vp, ci, cf, cf, cf, pd, pb, cd, cd, pd, vp]
+        L.aslam_ekf_step_batch_sighted.argtypes = [vp, pf, pf, pf, pd, ci, pb, ci, pd, pd, pd, ci, vp]
         # include/aslam_snapshot.h
         p32, p64 = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)
         L.aslam_snapshot_record_bytes.restype = ctypes.c_int64
@@ -230,6 +236,7 @@ def node_lib():
         L.aslam_node_remove_landmarks.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ci]
         L.aslam_node_get_sightings.argtypes = [vp, pu, pu, ci, pu]
         L.aslam_node_remove_stale.argtypes = [vp, ctypes.c_uint32]
+        L.aslam_node_set_sighted_only.argtypes = [vp, ci]
         # include/aslam_trace_file.h
         L.aslam_trace_file_error.restype = ctypes.c_char_p
         L.aslam_trace_file_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
@@ -417,9 +424,17 @@ class Core:
         z_seed = np.ascontiguousarray(z_seed, np.float64)
         _chk(core_lib().aslam_grow(self._h, traj, int(n_new), _ptr(x_seed, ctypes.c_double), _ptr(z_seed, ctypes.c_double)))
 
-    def ekf_step(self, traj, vx, az, dt, Z, a00, a10, stream=None):
+    def ekf_step(self, traj, vx, az, dt, Z, a00, a10, stream=None, sighted=None):
+        """`sighted` ([n_landmarks] bool / uint8, optional): the mask of this callback (aslam_ekf_step_sighted)."""
         Z = np.ascontiguousarray(Z, np.float64)
         X = np.empty(len(Z))
+        if sighted is not None:
+            m = np.zeros(max((len(Z) - 3) // 2, 1), np.uint8)
+            m[: (len(Z) - 3) // 2] = np.asarray(sighted)[: (len(Z) - 3) // 2] != 0
+            _chk(core_lib().aslam_ekf_step_sighted(self._h, traj, float(np.float32(vx)), float(np.float32(az)), float(np.float32(dt)),
+                                                   _ptr(Z, ctypes.c_double), _ptr(m, ctypes.c_uint8), float(a00), float(a10),
+                                                   _ptr(X, ctypes.c_double), stream))
+            return X
         _chk(core_lib().aslam_ekf_step(self._h, traj, float(np.float32(vx)), float(np.float32(az)), float(np.float32(dt)),
                                        _ptr(Z, ctypes.c_double), float(a00), float(a10), _ptr(X, ctypes.c_double), stream))
         return X
@@ -431,15 +446,22 @@ class Core:
                                        _ptr(Z, ctypes.c_double), _ptr(X, ctypes.c_double), stream))
         return X
 
-    def step_batch(self, vx, az, dt, Z, a00=None, a10=None, X_out=None, stream=None):
+    def step_batch(self, vx, az, dt, Z, a00=None, a10=None, X_out=None, stream=None, sighted=None):
         """slam() for all filters of the context in one launch chain.  vx, az, dt: [batch] float32; Z: [batch, ldz] float64;
         a00, a10: [batch] float64 (EKF).  Asynchronous: the arrays are used until `stream` is synchronised; X_out ([batch, ldx]
-        float64, optional) is valid only after that.  Arrays are taken as they are (no copies): pass C-contiguous ones."""
+        float64, optional) is valid only after that.  Arrays are taken as they are (no copies): pass C-contiguous ones.
+        `sighted` ([batch, ld] uint8, EKF, optional): the masks of this callback (aslam_ekf_step_batch_sighted)."""
         for a, t in ((vx, np.float32), (az, np.float32), (dt, np.float32), (Z, np.float64)):
             assert a.dtype == t and a.flags.c_contiguous and a.shape[0] == self.batch
         ldx = 0 if X_out is None else X_out.shape[1]
         if self.filter == "ekf":
             assert a00.dtype == np.float64 and a10.dtype == np.float64
+            if sighted is not None:
+                assert sighted.dtype == np.uint8 and sighted.flags.c_contiguous and sighted.shape[0] == self.batch
+                _chk(core_lib().aslam_ekf_step_batch_sighted(self._h, _ptr(vx, ctypes.c_float), _ptr(az, ctypes.c_float), _ptr(dt, ctypes.c_float),
+                                                             _ptr(Z, ctypes.c_double), Z.shape[1], _ptr(sighted, ctypes.c_uint8), sighted.shape[1],
+                                                             _ptr(a00, ctypes.c_double), _ptr(a10, ctypes.c_double), _ptr(X_out, ctypes.c_double), ldx, stream))
+                return
             _chk(core_lib().aslam_ekf_step_batch(self._h, _ptr(vx, ctypes.c_float), _ptr(az, ctypes.c_float), _ptr(dt, ctypes.c_float),
                                                  _ptr(Z, ctypes.c_double), Z.shape[1], _ptr(a00, ctypes.c_double), _ptr(a10, ctypes.c_double),
                                                  _ptr(X_out, ctypes.c_double), ldx, stream))
@@ -497,6 +519,19 @@ class Core:
         a, b = ctypes.c_double(), ctypes.c_double()
         _chk(core_lib().aslam_get_innovation(self._h, traj, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
+
+    # ---- sighted-only update (aslam_sighted_update_enable / aslam_get_sighted)
+    def sighted_only(self, on=True):
+        """Update with the rows of the landmarks sighted in each callback alone (EKF contexts; off by default; kept by reset())."""
+        _chk(core_lib().aslam_sighted_update_enable(self._h, 1 if on else 0))
+
+    def sighted(self, traj=0):
+        """The mask [L] uint8 the last callback of filter `traj` used (written with the mode off as well); synchronises."""
+        cap = max(self.landmark_capacity(), 1)
+        m = np.zeros(cap, np.uint8)
+        k = ctypes.c_int()
+        _chk(core_lib().aslam_get_sighted(self._h, int(traj), _ptr(m, ctypes.c_uint8), cap, ctypes.byref(k)))
+        return m[: min(k.value, cap)]
 
     # ---- read-back
     def dim(self, traj=0):
@@ -775,6 +810,11 @@ class Node:
         if node_lib().aslam_node_innovation(self._h, ctypes.byref(a), ctypes.byref(b)) != 0:
             raise AslamError(node_lib().aslam_node_error().decode())
         return a.value, b.value
+
+    def set_sighted_only(self, on=True):
+        """FilterNode::setSightedOnly: update with the rows of the landmarks each callback's own association sighted (EKF nodes)."""
+        if node_lib().aslam_node_set_sighted_only(self._h, 1 if on else 0) != 0:
+            raise AslamError(node_lib().aslam_node_error().decode())
 
     def set_params(self, params):
         """FilterNode::setParams: a Params or a dict of overrides of the defaults.  Before the first callback (p0_pose applies then)."""

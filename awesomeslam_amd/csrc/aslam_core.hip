@@ -79,6 +79,8 @@ struct aslam_ctx
         // aslam_innovation_enable: [batch][2] (nis, logdet) of every filter's last callback, allocated by the first enable; off by default
         double *innov = nullptr;
         bool innov_on = false;
+        // aslam_sighted_update_enable: the EKF update takes the rows of the landmarks sighted in the callback alone (dv.sighted); off by default
+        bool sighted_on = false;
         // aslam_set_params: the host copy of dv.prm ([batch] records in HBM); aslam_grow and init_state read p0_landmark / p0_pose from it
         std::vector<aslam_params> params;
         aslam_params *params_dev = nullptr;
@@ -260,6 +262,7 @@ int init_state(aslam_ctx *c)
         HIP_TRY(hipMemset(d.clock, 0, sizeof(uint32_t) * B));
         HIP_TRY(hipMemset(d.lm_seen, 0, sizeof(uint32_t) * B * (NP / 2)));
         HIP_TRY(hipMemset(d.lm_hits, 0, sizeof(uint32_t) * B * (NP / 2)));
+        HIP_TRY(hipMemset(d.sighted, 0, sizeof(uint8_t) * B * (NP / 2)));
         std::vector<int> n(B, 3), fl(B, FLAG_INIT_X | FLAG_INIT_Z);
         std::vector<double> A(2 * B, 0.0);
         for (size_t b = 0; b < B; ++b)
@@ -308,12 +311,16 @@ int launch(aslam_ctx *c, int grid, int64_t t0, int nsteps, double *poses, int32_
 #endif
         if (c->large)
                 return with_large_view(c, [&](auto &lv) -> int {
+                        c->lh.sighted = c->sighted_on;
                         HIP_TRY(launch_large<MODE>(c->lh, c->dv, lv, c->skipped, t0, nsteps, poses, dims, sa, st, sv));
                         return ASLAM_OK;
                 });
         if (c->cfg.filter == ASLAM_EKF)
                 return with_NT(c->NT, [&](auto nt) {
                         constexpr int NT = decltype(nt)::value;
+                        if (c->sighted_on) // the information-form instantiations (ekf_small.h); off: exactly the launches below
+                                return sv.any() ? launch_small<SmallLayout<NT>>(ekf_small_kernel<NT, MODE, true, true>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv)
+                                                : launch_small<SmallLayout<NT>>(ekf_small_kernel<NT, MODE, false, true>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv);
                         return sv.any() ? launch_small<SmallLayout<NT>>(ekf_small_kernel<NT, MODE, true>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv)
                                         : launch_small<SmallLayout<NT>>(ekf_small_kernel<NT, MODE, false>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv);
                 });
@@ -450,7 +457,7 @@ int aslam_create(const aslam_config *cfg, aslam_ctx **out)
         for_each_array(d, [&](auto *&p, size_t per, bool) {
                 if (large && same_slot(p, d.P))
                         take_large();
-                else if (same_slot(p, d.clock) || same_slot(p, d.lm_seen) || same_slot(p, d.lm_hits))
+                else if (same_slot(p, d.clock) || same_slot(p, d.lm_seen) || same_slot(p, d.lm_hits) || same_slot(p, d.sighted))
                         rc = rc == ASLAM_OK ? dev_alloc(c, &p, B * per, c->owned, false) : rc; // (bookkeeping, outside the reported bytes)
                 else
                         take(p, per);
@@ -645,7 +652,9 @@ int aslam_grow(aslam_ctx *c, int traj, int n_new, const double *x_seed, const do
 namespace
 {
 /// one callback of one trajectory: Z (and the EKF's A) to the device, the launch, optional read-back of X (synchronises then)
-int step_one(aslam_ctx *c, int filter, int traj, float vx, float az, float dt, const double *Z, const double *A, double *X_out, void *stream)
+/// `sighted`: the host's mask of this callback ([n_landmarks], aslam_ekf_step_sighted), or null: under the mode every landmark counts as sighted
+int step_one(aslam_ctx *c, int filter, int traj, float vx, float az, float dt, const double *Z, const double *A, double *X_out, void *stream,
+             const uint8_t *sighted = nullptr)
 {
         int rc = check_traj(c, traj);
         if (rc != ASLAM_OK)
@@ -664,6 +673,11 @@ int step_one(aslam_ctx *c, int filter, int traj, float vx, float az, float dt, c
         HIP_TRY(hipMemcpyAsync(d.Z + traj * NP, Z, sizeof(double) * n, hipMemcpyHostToDevice, st));
         if (A)
                 HIP_TRY(hipMemcpyAsync(d.A + 2 * traj, A, 2 * sizeof(double), hipMemcpyHostToDevice, st));
+        const size_t nlm = (size_t)(n - 3) / 2;
+        if (sighted && nlm)
+                HIP_TRY(hipMemcpyAsync(d.sighted + traj * (NP / 2), sighted, nlm, hipMemcpyHostToDevice, st));
+        else if (c->sighted_on && filter == ASLAM_EKF && nlm)
+                HIP_TRY(hipMemsetAsync(d.sighted + traj * (NP / 2), 1, nlm, st));
         StepArgs sa{traj, vx, az, dt};
         rc = launch<MODE_STEP>(c, 1, 0, 1, nullptr, nullptr, sa, st, innovation_view(c));
         if (rc != ASLAM_OK)
@@ -693,8 +707,9 @@ namespace
 {
 /// the batched per-callback seam: inputs of all filters to the device (asynchronously, straight from the caller's arrays), one launch
 /// chain for the whole batch, optional read-back of X; no synchronisation
+/// `sighted` [batch][lds]: as in step_one
 int step_batch(aslam_ctx *c, int filter, const float *vx, const float *az, const float *dt, const double *Z, int ldz, const double *a00,
-               const double *a10, double *X_out, int ldx, void *stream)
+               const double *a10, double *X_out, int ldx, void *stream, const uint8_t *sighted = nullptr, int lds = 0)
 {
         if (!c)
                 return fail(ASLAM_ERR_ARG, "null context");
@@ -718,6 +733,10 @@ int step_batch(aslam_ctx *c, int filter, const float *vx, const float *az, const
                 HIP_TRY(hipMemcpy2DAsync(d.A, 2 * sizeof(double), a00, sizeof(double), sizeof(double), B, hipMemcpyHostToDevice, st));
                 HIP_TRY(hipMemcpy2DAsync(d.A + 1, 2 * sizeof(double), a10, sizeof(double), sizeof(double), B, hipMemcpyHostToDevice, st));
         }
+        if (sighted)
+                HIP_TRY(hipMemcpy2DAsync(d.sighted, NP / 2, sighted, lds, (size_t)std::min(lds, NP / 2), B, hipMemcpyHostToDevice, st));
+        else if (c->sighted_on && filter == ASLAM_EKF)
+                HIP_TRY(hipMemsetAsync(d.sighted, 1, (size_t)B * (NP / 2), st)); // (the kernels read the entries of a filter's own landmarks alone)
         StepArgs sa{-1, 0.f, 0.f, 0.f};
         int rc = launch<MODE_STEP>(c, B, 0, 1, nullptr, nullptr, sa, st, innovation_view(c));
         if (rc != ASLAM_OK)
@@ -733,6 +752,23 @@ int aslam_ekf_step_batch(aslam_ctx *c, const float *vx, const float *az, const f
                          const double *a10, double *X_out, int ldx, void *stream)
 {
         return step_batch(c, ASLAM_EKF, vx, az, dt, Z, ldz, a00, a10, X_out, ldx, stream);
+}
+
+int aslam_ekf_step_sighted(aslam_ctx *c, int traj, float vx, float az, float dt, const double *Z, const uint8_t *sighted, double a00, double a10,
+                           double *X_out, void *stream)
+{
+        if (!sighted)
+                return fail(ASLAM_ERR_ARG, "sighted is required");
+        const double A[2] = {a00, a10};
+        return step_one(c, ASLAM_EKF, traj, vx, az, dt, Z, A, X_out, stream, sighted);
+}
+
+int aslam_ekf_step_batch_sighted(aslam_ctx *c, const float *vx, const float *az, const float *dt, const double *Z, int ldz, const uint8_t *sighted,
+                                 int ld, const double *a00, const double *a10, double *X_out, int ldx, void *stream)
+{
+        if (!sighted || ld < 1)
+                return fail(ASLAM_ERR_ARG, "sighted with a positive row stride is required");
+        return step_batch(c, ASLAM_EKF, vx, az, dt, Z, ldz, a00, a10, X_out, ldx, stream, sighted, ld);
 }
 
 int aslam_ukf_step_batch(aslam_ctx *c, const float *vx, const float *az, const float *dt, const double *Z, int ldz, double *X_out, int ldx,
@@ -829,6 +865,36 @@ int aslam_innovation_enable(aslam_ctx *c, int on)
         if (on && !c->innov_on && (rc = clear_innovation(c)) != ASLAM_OK)
                 return rc;
         c->innov_on = on != 0;
+        return ASLAM_OK;
+}
+
+int aslam_sighted_update_enable(aslam_ctx *c, int on)
+{
+        if (!c)
+                return fail(ASLAM_ERR_ARG, "null context");
+        if (c->cfg.filter != ASLAM_EKF)
+                return fail(ASLAM_ERR_UNSUPPORTED, "the sighted-only update exists for the EKF alone: the UKF contexts (either size) have no such mode");
+        int rc = sync_ctx(c);
+        if (rc != ASLAM_OK)
+                return rc;
+        c->sighted_on = on != 0;
+        return ASLAM_OK;
+}
+
+int aslam_get_sighted(aslam_ctx *c, int traj, uint8_t *sighted, int cap, int *n_landmarks)
+{
+        int n = 0;
+        int rc = aslam_get_dim(c, traj, &n); // (checks the arguments and synchronises)
+        if (rc != ASLAM_OK)
+                return rc;
+        const size_t H = (size_t)c->NP / 2;
+        const int L = std::max(0, (n - 3) / 2), k = std::min(L, cap);
+        if (sighted && cap > 0)
+                std::memset(sighted, 0, (size_t)cap);
+        if (sighted && k > 0)
+                HIP_TRY(hipMemcpy(sighted, c->dv.sighted + traj * H, (size_t)k, hipMemcpyDeviceToHost));
+        if (n_landmarks)
+                *n_landmarks = L;
         return ASLAM_OK;
 }
 
@@ -1249,6 +1315,8 @@ int aslam_restore(aslam_ctx *c, const int32_t *records, const int32_t *trajs, in
         hipLaunchKernelGGL(sight_clear, dim3((unsigned)count), dim3(PRUNE_WAVE), 0, st, reinterpret_cast<const SnapDesc *>(c->snap_dev), c->NP,
                            c->dv.clock, c->dv.lm_seen, c->dv.lm_hits);
         HIP_TRY(hipGetLastError());
+        for (int i = 0; i < count; ++i) // (nor the mask of the last callback)
+                HIP_TRY(hipMemsetAsync(c->dv.sighted + (size_t)desc[i].slot * (c->NP / 2), 0, (size_t)c->NP / 2, st));
         return ASLAM_OK;
 }
 
@@ -1418,6 +1486,9 @@ int aslam_remove_landmarks(aslam_ctx *c, const uint8_t *mask, int ld, int is_dev
         hipLaunchKernelGGL(sight_compact, dim3((unsigned)B), dim3(PRUNE_WAVE), 0, st, reinterpret_cast<const int *>(c->snap_dev + o_src),
                            reinterpret_cast<const PruneMeta *>(c->snap_dev + o_meta), c->NP, c->dv.lm_seen, c->dv.lm_hits);
         HIP_TRY(hipGetLastError());
+        // the mask of the last callback indexes landmarks that have moved: zero in every filter that lost one
+        for (const SnapDesc &q : desc)
+                HIP_TRY(hipMemsetAsync(c->dv.sighted + (size_t)q.slot * (c->NP / 2), 0, (size_t)c->NP / 2, st));
         return ASLAM_OK;
 }
 
@@ -1703,10 +1774,15 @@ int aslam_kernel_info(aslam_ctx *c, char *name, int name_cap, int *grid, int *bl
                 else
                         std::snprintf(buf, sizeof(buf), "large_update_panel<double> (%d-launch chain per callback, %d stream groups)", plan.launches, c->lh.knobs.groups);
                 lds = LargeLds::bytes(c->NP);
+                if (c->sighted_on && c->cfg.filter == ASLAM_EKF)
+                {
+                        const std::string with = std::string("large_build_GS<T,sighted> + ") + buf;
+                        std::snprintf(buf, sizeof(buf), "%s", with.c_str());
+                }
         }
         else if (c->cfg.filter == ASLAM_EKF)
         {
-                std::snprintf(buf, sizeof(buf), "ekf_small_kernel<%d,0>", c->NT);
+                std::snprintf(buf, sizeof(buf), c->sighted_on ? "ekf_small_kernel<%d,0,false,true>" : "ekf_small_kernel<%d,0>", c->NT);
                 lds = with_NT(c->NT, [](auto nt) -> size_t { return SmallLayout<decltype(nt)::value>::total; });
         }
 #if ASLAM_HAVE_UKF

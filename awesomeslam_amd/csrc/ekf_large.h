@@ -241,7 +241,9 @@ struct LargeLds
 // ------------------------------------------------------------------------------------------------------------------
 /// Per-filter front end + predict (one workgroup of SMALL_WG threads per filter).  `skipped` [B] is set to 1 when the
 /// callback returned early (no sensor message yet): the rest of the chain then leaves the filter alone.
-template <typename T, int MODE>
+/// SIGHTED (aslam_sighted_update_enable): Y is zeroed in the rows of the landmarks this callback did not sight (DevView::sighted, which the front
+/// end has just written in replay and the host has copied down for a step); large_build_GS<T, true> does the rest.
+template <typename T, int MODE, bool SIGHTED = false>
 __global__ __launch_bounds__(SMALL_WG) void large_frontend_kernel(DevView d, LargeView<T> lv, int64_t t, int s, int nsteps,
                                                                    double *poses_out, int32_t *dims_out, StepArgs sa, int *skipped)
 {
@@ -262,6 +264,8 @@ __global__ __launch_bounds__(SMALL_WG) void large_frontend_kernel(DevView d, Lar
         const unsigned long long stamp_rt0 = __builtin_amdgcn_s_memrealtime(); // 100 MHz: wall time inside the kernel
 #endif
         small_load<MODE>(d, L, b, tid, NP);
+        if (MODE == MODE_REPLAY && tid == 0)
+                small_mask_ptr(L) = d.sighted + (size_t)b * (NP / 2); // (read behind the front end's barriers)
         ASLAM_STAMP(0);
         if (MODE == MODE_REPLAY)
         {
@@ -316,6 +320,11 @@ __global__ __launch_bounds__(SMALL_WG) void large_frontend_kernel(DevView d, Lar
                 const double hb = atan2(ddy, ddx) - sX[2];
                 Yg[3 + 2 * i] = sZ[3 + 2 * i] - hr;
                 Yg[4 + 2 * i] = (double)normalizeAngle((float)(sZ[4 + 2 * i] - hb));
+                if constexpr (SIGHTED)
+                {
+                        if (!d.sighted[(size_t)b * (NP / 2) + i])
+                                Yg[3 + 2 * i] = 0.0, Yg[4 + 2 * i] = 0.0;
+                }
         }
         if (tid == 0)
         {
@@ -374,8 +383,14 @@ __global__ __launch_bounds__(SMALL_WG) void large_frontend_kernel(DevView d, Lar
 /// that is the one rounding of G).  Only the lower block triangle of S (with full diagonal blocks) is consumed downstream and written.  grid (1 + ceil((NP / 2) / GS_ROW_PAIRS), B), 256 threads: workgroup 0 the pose rows, the others GS_ROW_PAIRS landmark row pairs each.
 constexpr int GS_ROW_PAIRS = 2; // 4: slower (29.1 k against 29.7 k filter-steps/s on one stream), 1: 28.5 k
 
-template <typename T> __global__ __launch_bounds__(256) void large_build_GS(DevView d, LargeView<T> lv, const int *skipped)
+///
+/// SIGHTED (aslam_sighted_update_enable): the update with the rows M = pose rows + rows of the sighted landmarks alone, as the same chain.  For a
+/// row u outside M: column u of G is 0, row and column u of S are those of the identity (and Y_u = 0: the front end) -- in binary64, before any
+/// rounding, the copies for the border (put_l, save_g2) included.  L then has a unit row there and column u of V is 0: Cholesky, TRSM, border,
+/// X update, syrk and large_stats run unchanged, and ln det / NIS come out as those of S_M.  SIGHTED = false is the code it was.
+template <typename T, bool SIGHTED = false> __global__ __launch_bounds__(256) void large_build_GS(DevView d, LargeView<T> lv, const int *skipped)
 {
+        const uint8_t *const sgt = SIGHTED ? d.sighted + (size_t)blockIdx.y * (lv.NP / 2) : nullptr; // [landmark] of this filter
         const int b = blockIdx.y;
         if (skipped[b])
                 return;
@@ -456,6 +471,14 @@ template <typename T> __global__ __launch_bounds__(256) void large_build_GS(DevV
                         ha0[rp] = hr[0], ha1[rp] = hr[1], hb0[rp] = hr[2], hb1[rp] = hr[3]; // H rows ra (range) and ra+1 (bearing)
                 }
         }
+        bool row_in[RP]; // SIGHTED: rows ra, ra+1 of this pair are in M
+#pragma unroll
+        for (int rp = 0; rp < RP; ++rp)
+        {
+                row_in[rp] = true;
+                if constexpr (SIGHTED)
+                        row_in[rp] = (!pose && rp < nlive) ? sgt[(r0 + 2 * rp - 3) >> 1] != 0 : true;
+        }
         auto grow = [](double h00, double h01, double h10, double h11, double t0, double t1, double t2, double ta, double tb, double &ge,
                        double &go) {
                 ge = h00 * t0 + h01 * t1 - h00 * ta - h01 * tb;
@@ -490,7 +513,9 @@ template <typename T> __global__ __launch_bounds__(256) void large_build_GS(DevV
                                         const double ga = pa[rp][c], gb = pb[rp][c];
                                         G[(size_t)ra * NP + c] = (T)ga;
                                         G[(size_t)(ra + 1) * NP + c] = (T)gb;
-                                        const double sa = srow(ha0[rp], ha1[rp], false, g0, g1, g2, ga, gb), sb = srow(hb0[rp], hb1[rp], true, g0, g1, g2, ga, gb);
+                                        double sa = srow(ha0[rp], ha1[rp], false, g0, g1, g2, ga, gb), sb = srow(hb0[rp], hb1[rp], true, g0, g1, g2, ga, gb);
+                                        if (SIGHTED && !row_in[rp])
+                                                sa = 0.0, sb = 0.0; // (a pose column of a row outside M)
                                         S[(size_t)ra * NP + c] = (T)sa;
                                         S[(size_t)(ra + 1) * NP + c] = (T)sb;
                                         put_l(ra, c, sa), put_l(ra + 1, c, sb);
@@ -508,6 +533,13 @@ template <typename T> __global__ __launch_bounds__(256) void large_build_GS(DevV
                 grow(h00, h01, h10, h11, t00, t01, t02, p0[ce], p0[co], g0e, g0o);
                 grow(h00, h01, h10, h11, t10, t11, t12, p1[ce], p1[co], g1e, g1o);
                 grow(h00, h01, h10, h11, t20, t21, t22, p2[ce], p2[co], g2e, g2o);
+                bool col_in = true; // SIGHTED: columns ce, co are in M
+                if constexpr (SIGHTED)
+                {
+                        col_in = sgt[j] != 0;
+                        if (!col_in)
+                                g0e = g0o = g1e = g1o = g2e = g2o = 0.0;
+                }
                 if (pose)
                 {
                         G[ce] = (T)g0e, G[co] = (T)g0o;
@@ -533,6 +565,8 @@ template <typename T> __global__ __launch_bounds__(256) void large_build_GS(DevV
                                         double gae, gao, gbe, gbo;
                                         grow(h00, h01, h10, h11, ta0[rp], ta1[rp], ta2[rp], pa[rp][ce], pa[rp][co], gae, gao);
                                         grow(h00, h01, h10, h11, tb0[rp], tb1[rp], tb2[rp], pb[rp][ce], pb[rp][co], gbe, gbo);
+                                        if (SIGHTED && !col_in)
+                                                gae = gao = gbe = gbo = 0.0;
                                         T *ga = G + (size_t)ra * NP, *gb = ga + NP, *sa = S + (size_t)ra * NP, *sb = sa + NP;
                                         ga[ce] = (T)gae, ga[co] = (T)gao;
                                         gb[ce] = (T)gbe, gb[co] = (T)gbo;
@@ -542,10 +576,19 @@ template <typename T> __global__ __launch_bounds__(256) void large_build_GS(DevV
                                                        so = srow(ha0[rp], ha1[rp], false, g0o, g1o, g2o, gao, gbo);
                                                 double ue = srow(hb0[rp], hb1[rp], true, g0e, g1e, g2e, gae, gbe),
                                                        uo = srow(hb0[rp], hb1[rp], true, g0o, g1o, g2o, gao, gbo);
+                                                if (SIGHTED && !(col_in && row_in[rp]))
+                                                {
+                                                        se = so = ue = uo = 0.0; // rows and columns outside M: those of the identity
+                                                        if (ce == ra)
+                                                                se = 1.0, uo = 1.0;
+                                                }
+                                                else
+                                                {
                                                 if (ce == ra)
                                                         se += r_range; // R on the diagonal: the range row of the pair ...
                                                 if (co == ra + 1)
                                                         uo += r_bearing; // ... and its bearing row
+                                                }
                                                 sa[ce] = (T)se, sa[co] = (T)so;
                                                 sb[ce] = (T)ue, sb[co] = (T)uo;
                                                 put_l(ra, ce, se), put_l(ra, co, so);

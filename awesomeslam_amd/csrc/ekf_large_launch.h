@@ -116,6 +116,7 @@ struct LargeHost
         int last_groups = 0;        // stream groups that received work (1 = the caller's stream alone; 0 = nothing launched yet)
         int last_launches = 0;      // kernel launches per callback and stream group of that launch (large_stats included)
         bool last_resident = false; // that launch ran LargeChain::F32_RESIDENT
+        bool sighted = false;       // aslam_sighted_update_enable: the SIGHTED instantiations of the front end and of large_build_GS (which then also stands in for large_build_GS_tiles)
 };
 
 /// which filters a launch covers: one trajectory (MODE_STEP with sa.traj >= 0; the views then start at it, so the kernels get traj = 0) or the
@@ -221,14 +222,23 @@ int launch_left_looking(const DevView &dv, const LargeView<T> &v, int NB, int gb
 
 /// callback s of one group: front end + predict, G, S, blocked factorisation of [S; G; Y^T], P -= V V^T, X += V q
 template <typename T, int MODE>
-void launch_large_chain(const LargePlan &plan, const LargeGroup<T> &g, size_t lds, int64_t t0, int s, int nsteps, StepArgs sa)
+void launch_large_chain(const LargePlan &plan, const LargeGroup<T> &g, size_t lds, int64_t t0, int s, int nsteps, StepArgs sa, bool sighted)
 {
         const int NP = g.v.NP, NB = NP / LB, gb = g.nb;
+        if (sighted)
+        {
+                // the sighted-only update: the mask enters in these two launches alone (ASLAM_GS_TILES=1 has no masked form: large_build_GS runs)
+                hipLaunchKernelGGL((large_frontend_kernel<T, MODE, true>), dim3(gb), dim3(SMALL_WG), lds, g.st, g.dv, g.v, t0 + s, s, nsteps, g.poses, g.dims, sa, g.skip);
+                hipLaunchKernelGGL((large_build_GS<T, true>), dim3(1 + (NP / 2 + GS_ROW_PAIRS - 1) / GS_ROW_PAIRS, gb), dim3(256), 0, g.st, g.dv, g.v, g.skip);
+        }
+        else
+        {
         hipLaunchKernelGGL((large_frontend_kernel<T, MODE>), dim3(gb), dim3(SMALL_WG), lds, g.st, g.dv, g.v, t0 + s, s, nsteps, g.poses, g.dims, sa, g.skip);
         if (plan.gs_tiles)
                 hipLaunchKernelGGL(large_build_GS_tiles<T>, dim3(NB * (NB + 1) / 2, gb), dim3(256), 0, g.st, g.dv, g.v, g.skip);
         else
                 hipLaunchKernelGGL(large_build_GS<T>, dim3(1 + (NP / 2 + GS_ROW_PAIRS - 1) / GS_ROW_PAIRS, gb), dim3(256), 0, g.st, g.dv, g.v, g.skip);
+        }
         const int ntile = (NP + 127) / 128;
         const dim3 syrk_grid(8 * (ntile * (ntile + 1) / 2) * ((gb + 7) / 8));
         if constexpr (sizeof(T) == 8)
@@ -297,7 +307,8 @@ hipError_t launch_large(LargeHost &h, const DevView &dv, const LargeView<T> &lv,
                         StepArgs sa, hipStream_t st, StatsView sv = {})
 {
         const size_t lds = LargeLds::bytes(dv.NP);
-        if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(large_frontend_kernel<T, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
+        if (hipError_t e = h.sighted ? hipFuncSetAttribute(reinterpret_cast<const void *>(large_frontend_kernel<T, MODE, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
+                                     : hipFuncSetAttribute(reinterpret_cast<const void *>(large_frontend_kernel<T, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
                 return e;
         const LaunchSlice sl = launch_slice<MODE>(sa, dv.B);
         const int first = sl.first, Bz = sl.count;
@@ -329,7 +340,7 @@ hipError_t launch_large(LargeHost &h, const DevView &dv, const LargeView<T> &lv,
         for (int s = 0; s < nsteps; ++s)
                 for (int q = 0; q < NG; ++q)
                         if (g[q].nb > 0)
-                                launch_large_chain<T, MODE>(plan, g[q], lds, t0, s, nsteps, sl.sa);
+                                launch_large_chain<T, MODE>(plan, g[q], lds, t0, s, nsteps, sl.sa, h.sighted);
         for (int q = 1; q < NG && e == hipSuccess; ++q)
                 if ((e = hipEventRecord(h.ev_join[q - 1], h.aux[q - 1])) == hipSuccess)
                         e = hipStreamWaitEvent(st, h.ev_join[q - 1], 0);

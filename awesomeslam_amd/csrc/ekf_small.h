@@ -132,7 +132,13 @@ template <bool FWD> __device__ __forceinline__ void congruence_tiles(double *Lt,
 }
 
 /// STATS: also the innovation statistics of every callback and the pose block of P (StatsView); the STATS = false instantiations do not read `sv`.
-template <int NT, int MODE, bool STATS = false>
+/// SIGHTED (aslam_sighted_update_enable): the update uses the pose rows and the rows of the landmarks sighted in this callback only (DevView::sighted),
+/// M = {0, 1, 2} + {3 + 2k, 4 + 2k : k sighted}.  R - R S^-1 R needs a finite r_i in every row, so this instantiation works in the information form,
+/// exact in real arithmetic: with D = diag(1 / r_i for i in M, 0 otherwise)
+///     P~_new = (P~^-1 + D)^-1,        u = K~ Y = P~_new (D Y)
+/// -- two in-place inversions of the tiles (cholesky_inverse_tiles<NT, true>), D added to the diagonal between them, D Y riding through the second.
+/// D and D Y live in the front end's wait-list scratch (sWx, sWy: only read inside small_frontend).  The other instantiations keep their code.
+template <int NT, int MODE, bool STATS = false, bool SIGHTED = false>
 __global__ __launch_bounds__(SMALL_WG) void ekf_small_kernel(DevView d, int64_t t0, int nsteps, double *poses_out,
                                                               int32_t *dims_out, StepArgs sa, StatsView sv)
 {
@@ -143,6 +149,9 @@ __global__ __launch_bounds__(SMALL_WG) void ekf_small_kernel(DevView d, int64_t 
         double *const Lt = L.Lt, *const Dinv = L.Dinv, *const sX = L.sX, *const sZ = L.sZ, *const sY = L.sY, *const sU = L.sU,
                       *const sH = L.sH;
         SmallShared &sm = *L.sm;
+        // SIGHTED: D [NP], D Y [NP] and, from sD[NP] on, 64 partial products of the first factor's inverted diagonal (2 KB of scratch each)
+        double *const sD = reinterpret_cast<double *>(L.sWx), *const sDY = reinterpret_cast<double *>(L.sWy);
+        static_assert(!SIGHTED || (NP + 64) * 8 <= 4 * SMALL_WAIT_CAP, "D and D Y fit the wait-list scratch");
 
         const int tid_launch = threadIdx.x, tid = tid_launch;
         const int b = (MODE == MODE_STEP && sa.traj >= 0) ? sa.traj : (int)blockIdx.x; // sa.traj < 0: the batched step, one workgroup per filter
@@ -153,6 +162,8 @@ __global__ __launch_bounds__(SMALL_WG) void ekf_small_kernel(DevView d, int64_t 
 #endif
 
         small_load<MODE>(d, L, b, tid, NP);
+        if (MODE == MODE_REPLAY && tid == 0)
+                small_mask_ptr(L) = d.sighted + (size_t)b * NLM; // (read behind the front end's barriers)
         // P stays in LDS for the whole launch, as the lower 16x16 tiles of the symmetric matrix (the tile storage the solver
         // factors in place): HBM sees it once on the way in and once on the way out
         for (int idx = tid; idx < LY::NTILES * 256; idx += SMALL_WG)
@@ -251,15 +262,33 @@ __global__ __launch_bounds__(SMALL_WG) void ekf_small_kernel(DevView d, int64_t 
                         const double hb = atan2(ddy, ddx) - xp2;
                         sY[3 + 2 * i] = sZ[3 + 2 * i] - hr;
                         sY[4 + 2 * i] = (double)normalizeAngle((float)(sZ[4 + 2 * i] - hb));
+                        if constexpr (SIGHTED)
+                        {
+                                const bool in_view = d.sighted[(size_t)b * NLM + i] != 0; // (this callback's: the front end's store is behind its barrier)
+                                const double d0 = in_view ? 1.0 / sm.prm.r_range : 0.0, d1 = in_view ? 1.0 / sm.prm.r_bearing : 0.0;
+                                sD[3 + 2 * i] = d0, sD[4 + 2 * i] = d1;
+                                sDY[3 + 2 * i] = in_view ? d0 * sY[3 + 2 * i] : 0.0;
+                                sDY[4 + 2 * i] = in_view ? d1 * sY[4 + 2 * i] : 0.0;
+                        }
                 }
                 if (tid == 0)
                 {
                         sY[0] = sZ[0] - xp0;
                         sY[1] = sZ[1] - xp1;
                         sY[2] = (double)normalizeAngle((float)(sZ[2] - xp2));
+                        if constexpr (SIGHTED)
+                        {
+                                const double dxy = 1.0 / sm.prm.r_xy, dyaw = 1.0 / sm.prm.r_yaw;
+                                sD[0] = dxy, sD[1] = dxy, sD[2] = dyaw;
+                                sDY[0] = dxy * sY[0], sDY[1] = dxy * sY[1], sDY[2] = dyaw * sY[2];
+                        }
                 }
                 for (int i = n + tid; i < NP; i += SMALL_WG)
+                {
                         sY[i] = 0.0;
+                        if constexpr (SIGHTED)
+                                sD[i] = 0.0, sDY[i] = 0.0;
+                }
                 // P = A P A^T + Q (ekf.cpp:297) with A = I except A(0,0), A(1,0): on the symmetric storage that is columns 0, 1 of
                 // the rows below, and the 2x2 corner
                 __syncthreads(); // sY / sH are complete, nobody is still reading P
@@ -291,15 +320,69 @@ __global__ __launch_bounds__(SMALL_WG) void ekf_small_kernel(DevView d, int64_t 
                 ASLAM_STAMP(4);
                 // S = Pt + R = L L^T (ekf.cpp:300); Kt R = R - R S^-1 R -> the tiles (= (I - K H) P in measurement coordinates,
                 // ekf.cpp:301,310); u = Kt Y = Y - R S^-1 Y; R = diag of the filter's r_xy, r_yaw, r_range, r_bearing by row class
+                if constexpr (SIGHTED)
+                {
+                        // P~^-1 (nothing added, nothing of interest riding), then (P~^-1 + D)^-1 with D Y riding: tiles = P~_new, sU = u
+                        cholesky_inverse_tiles<NT, true>(Lt, Dinv, nt, n, sDY, sU, L.sTv, nullptr, tid, &sm.status);
+                        if constexpr (STATS)
+                        {
+                                // ln det P~ = -2 sum ln (1 / L_ii) of the first factor: every lane keeps the product of its entries, before the second factor takes the
+                                // inverted diagonal tiles (its first barrier is behind this read in every wave's program order); the one log is taken below
+                                if (__builtin_amdgcn_readfirstlane(tid_launch) >= SMALL_WG - 64)
+                                {
+                                        const int lane = tid & 63;
+                                        double dprod = 1.0;
+#pragma unroll
+                                        for (int k = 0; k < (NP + 63) / 64; ++k)
+                                        {
+                                                const int j = lane + 64 * k, jc = min(j, NP - 1);
+                                                const double di0 = Dinv[(jc >> 4) * TSZ + (jc & 15) * (TLD + 1)];
+                                                dprod *= j < n ? di0 : 1.0;
+                                        }
+                                        sD[NP + lane] = dprod;
+                                }
+                        }
+                        cholesky_inverse_tiles<NT, true>(Lt, Dinv, nt, n, sDY, sU, L.sTv, nullptr, tid, &sm.status, nullptr, sD);
+                }
+                else
+                {
 #ifdef ASLAM_STAMPS
                 cholesky_inverse_tiles<NT>(Lt, Dinv, nt, n, sY, sU, L.sTv, &sm.prm.r_xy, tid, &sm.status, (blockIdx.x == 0 && d.dbg) ? d.dbg + 16 : nullptr);
 #else
                 cholesky_inverse_tiles<NT>(Lt, Dinv, nt, n, sY, sU, L.sTv, &sm.prm.r_xy, tid, &sm.status);
 #endif
+                }
                 ASLAM_STAMP(5);
                 __syncthreads();
                 ASLAM_STAMP(6);
-                if constexpr (STATS)
+                if constexpr (STATS && SIGHTED)
+                {
+                        // the statistics of the selected rows, from the two factors:  NIS = Y_M^T S_M^-1 Y_M = sum_M y_i^2 / r_i - (D Y)^T u  (S_M^-1 = D_M - D_M P~_new D_M),
+                        // ln det S_M = sum_M ln r_i + ln det (P~^-1 + D) + ln det P~  (det (P~_MM + R_M) = det R_M det (I + D P~))
+                        if (__builtin_amdgcn_readfirstlane(tid_launch) >= SMALL_WG - 64)
+                        {
+                                const int lane = tid & 63;
+                                double tt = 0.0, dprod = sD[NP + lane], rprod = 1.0; // (at most six inverted pivots and three 1 / r_i per lane: one log of their product)
+#pragma unroll
+                                for (int k = 0; k < (NP + 63) / 64; ++k)
+                                {
+                                        const int j = lane + 64 * k, jc = min(j, NP - 1);
+                                        const double dy = sDY[jc], yy = sY[jc], uu = sU[jc], dd = sD[jc], di0 = Dinv[(jc >> 4) * TSZ + (jc & 15) * (TLD + 1)];
+                                        const bool live = j < n;
+                                        tt = fma(live ? dy : 0.0, yy - uu, tt);
+                                        dprod *= live ? di0 : 1.0;
+                                        rprod *= (live && dd > 0.0) ? dd : 1.0;
+                                }
+                                double ld = -log(dprod * dprod * rprod);
+                                tt = wave_sum_dpp(tt), ld = wave_sum_dpp(ld);
+                                if (lane == 63)
+                                {
+                                        const bool pd = !(sm.status & 4u); // ASLAM_ST_NOT_PD (sticky)
+                                        stats_put(sv, b, s, nsteps, pd ? tt : __builtin_nan(""), pd ? ld : __builtin_nan(""));
+                                }
+                        }
+                }
+                else if constexpr (STATS)
                 {
                         // NIS = Y^T S^-1 Y = |t|^2 with t = L^-1 Y (the scratch vector of the solve), ln det S = -2 sum ln (1 / L_ii) from the inverted
                         // diagonal tiles: both are still in LDS here (the congruence below takes the tile area over, behind the barrier of the X update).

@@ -144,6 +144,20 @@ void FilterNode::innovation(double &nis, double &logdet) const
                 nis = logdet = std::nan(""); // the core still holds the callback before
 }
 
+// The sighted-only update is bound weakly like the innovation record: a core without it refuses the mode, at run time.
+extern "C" {
+int aslam_sighted_update_enable(aslam_ctx *, int) __attribute__((weak));
+int aslam_ekf_step_sighted(aslam_ctx *, int, float, float, float, const double *, const uint8_t *, double, double, double *, void *) __attribute__((weak));
+}
+
+void FilterNode::setSightedOnly(bool on)
+{
+        if (!aslam_sighted_update_enable || !aslam_ekf_step_sighted)
+                throw std::runtime_error("this core has no sighted-only update");
+        check(aslam_sighted_update_enable(ctx, on ? 1 : 0), "aslam_sighted_update_enable"); // (refused for the UKF)
+        sighted_only = on;
+}
+
 // The parameter entry points are bound weakly for the same reason (and aslam_reset, which only setParams calls): with a core that lacks them
 // the mirror runs on the reference's constants, and anything else is refused.
 extern "C" {
@@ -208,6 +222,7 @@ void FilterNode::removeLandmarks(const std::vector<int> &indices)
         param_Z.resize(N);
         lm_seen.resize((N - 3) / 2);
         lm_hits.resize((N - 3) / 2);
+        lm_sighted.assign((N - 3) / 2, 0); // (the mask of the last callback indexed the old landmarks)
 }
 
 int FilterNode::removeStale(uint32_t max_age)
@@ -240,7 +255,8 @@ void FilterNode::updateZ(const Odometry &msg, float delta_time)
 
         const uint32_t mapped = (N - 3) / 2;
         sight_clock += 1;
-        std::vector<char> sighted(mapped, 0); // several observations on one landmark are one hit
+        std::vector<uint8_t> &sighted = lm_sighted; // several observations on one landmark are one hit; the mask of this callback
+        sighted.assign(mapped, 0);
         for (LaserData &obs : sensor_landmark)
         {
                 obs.bearing = normalizeAngle(obs.bearing);
@@ -341,6 +357,7 @@ void FilterNode::updateNewLandmark(const std::vector<LaserData> &new_landmark)
         param_Z.resize(N, 0.0);
         lm_seen.resize((N - 3) / 2, sight_clock); // promoted now, never sighted as a landmark
         lm_hits.resize((N - 3) / 2, 0u);
+        lm_sighted.resize((N - 3) / 2, 0); // initialised from this very reading: not sighted
         for (size_t k = 0; k < new_landmark.size(); ++k)
         {
                 const uint32_t i = cacheN + 2 * (uint32_t)k;
@@ -354,7 +371,14 @@ void FilterNode::updateNewLandmark(const std::vector<LaserData> &new_landmark)
 
 void FilterNode::slam(float vx, float az, float delta_time)
 {
-        if (filter == ASLAM_EKF)
+        if (filter == ASLAM_EKF && sighted_only)
+        {
+                lm_sighted.resize(std::max<size_t>(1, (N - 3) / 2), 0); // (a valid pointer with no landmark mapped yet)
+                check(aslam_ekf_step_sighted(ctx, 0, vx, az, delta_time, param_Z.data(), lm_sighted.data(), a00, a10, param_X.data(), nullptr),
+                      "aslam_ekf_step_sighted");
+                lm_sighted.resize((N - 3) / 2);
+        }
+        else if (filter == ASLAM_EKF)
                 check(aslam_ekf_step(ctx, 0, vx, az, delta_time, param_Z.data(), a00, a10, param_X.data(), nullptr),
                       "aslam_ekf_step");
         else
@@ -500,6 +524,20 @@ int aslam_node_enable_innovation(aslam_node *n, int on)
         try
         {
                 n->impl->enableInnovation(on != 0);
+                return 0;
+        }
+        catch (const std::exception &e)
+        {
+                g_node_err = e.what();
+                return -1;
+        }
+}
+
+int aslam_node_set_sighted_only(aslam_node *n, int on)
+{
+        try
+        {
+                n->impl->setSightedOnly(on != 0);
                 return 0;
         }
         catch (const std::exception &e)

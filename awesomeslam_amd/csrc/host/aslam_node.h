@@ -103,6 +103,13 @@ class FilterNode
         /// here, at run time ("this core has no innovation record"), not by the linker.
         void enableInnovation(bool on);
         void innovation(double &nis, double &logdet) const;
+        /// The sighted-only update (aslam_sighted_update_enable, aslam_core.h; EKF): slam() then uses the rows of the landmarks this callback's own
+        /// association sighted -- the mask updateZ records next to hits() -- through aslam_ekf_step_sighted.  Bound weakly, as the record above.
+        void setSightedOnly(bool on);
+        const std::vector<uint8_t> &sighted() const
+        {
+                return lm_sighted;
+        }
         /// The noise and association parameters (aslam_params, aslam_core.h; the reference's config.h constants by default).  The mirror's own
         /// association and wait-list use assoc_dist and promote_count; everything else lives in the core's record of this filter.  Meant to be
         /// called before the first callback: the core is then initialised again so that p0_pose applies; later calls change R, Q, var_a,
@@ -155,6 +162,8 @@ class FilterNode
         double a00, a10;                      // param.A(0,0), param.A(1,0) (EKF)
         uint32_t sight_clock;
         std::vector<uint32_t> lm_seen, lm_hits; // one entry per mapped landmark
+        std::vector<uint8_t> lm_sighted;        // the mask of the last callback's association, one entry per mapped landmark
+        bool sighted_only = false;
 
         void updateZ(const Odometry &msg, float delta_time);
         void updateNewLandmarkWait(const LaserData &data);
@@ -199,6 +208,8 @@ int aslam_node_wait(const aslam_node *n, float *range, float *bearing, uint32_t 
 aslam_ctx *aslam_node_core(const aslam_node *n);
 /* Switch the record of the last callback's innovation statistics on or off (off by default); 0, or -1 with aslam_node_error(). */
 int aslam_node_enable_innovation(aslam_node *n, int on);
+/* FilterNode::setSightedOnly (EKF nodes; off by default); 0, or -1 with aslam_node_error(). */
+int aslam_node_set_sighted_only(aslam_node *n, int on);
 /* y^T S^-1 y and ln |det S| of the last odometry callback's slam() (NaN when that callback returned early, or before the first one);
  * -1 with aslam_node_error() while the record is off. */
 int aslam_node_innovation(const aslam_node *n, double *nis, double *logdet);

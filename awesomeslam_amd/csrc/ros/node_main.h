@@ -8,6 +8,7 @@
 // the aslam_node.h calls -- nothing about ROS behaviour).
 #pragma once
 
+#include <type_traits>
 #include <awesome_slam_msgs/Landmarks.h>
 #include <nav_msgs/Odometry.h>
 #include <ros/ros.h>
@@ -94,6 +95,14 @@ template <class Filter> int node_main(int argc, char **argv, const char *node_na
         a.forget_after = forget_after < 0 ? 0u : (uint32_t)forget_after;
         a.forget_period = forget_period < 1 ? 1u : (uint32_t)forget_period;
         a.filter.setParams(prm); // before the first callback: p0_pose applies
+        if constexpr (std::is_same<Filter, aslam::EKFSlam>::value)
+        {
+                // ~sighted_only (EKF executable): update with the landmarks each callback sighted, not with the stale readings of the rest
+                bool sighted_only = false;
+                ros::param::param("~sighted_only", sighted_only, false);
+                if (sighted_only)
+                        a.filter.setSightedOnly(true);
+        }
         std::cerr << banner;
         while (ros::ok())
         {

@@ -80,6 +80,9 @@ struct DevView
         const float *tr_obs;
         const float *step_in;    // [3][B] vx, az, dt of a batched step (aslam_*_step_batch)
         unsigned long long *dbg; // diagnostic builds only (-DASLAM_STAMPS): per-phase cycle sums of workgroup 0
+        // the mask of the last callback (aslam_get_sighted): 1 where the association walk gave landmark k an observation.  Written by the replay front
+        // end of the EKF families every callback and by the *_step_sighted seams; read by the kernels only under aslam_sighted_update_enable
+        uint8_t *sighted;  // [B][NP/2]
 };
 
 /// The per-filter arrays of a DevView (host side): f(pointer, elements per filter, zero) once per array, in the order aslam_create allocates
@@ -108,6 +111,7 @@ template <typename F> void for_each_array(DevView &d, F &&f)
         f(d.clock, 1, false);
         f(d.lm_seen, np / 2, false);
         f(d.lm_hits, np / 2, false);
+        f(d.sighted, np / 2, false);
 }
 
 #ifdef ASLAM_STAMPS
@@ -822,9 +826,15 @@ __device__ __forceinline__ void cholesky_forward_rows(const double *Src, double 
 /// r_i is set far above its P~_ii loses correspondingly more).
 /// In: tiles = P~ (lower).  Out: tiles = lower part of Kt R (zero padding), U = Kt Y.  Same three wave roles and look-ahead
 /// as cholesky_forward_rows; `Tv`: LDS scratch of 16*NT doubles.  Ends with a barrier.
-template <int NT>
+///
+/// PLAIN (the sighted-only update of ekf_small.h, which applies it twice): the same factorisation and the same products, but the inverse itself.
+/// In: tiles = a symmetric positive definite M (lower), `addend`: a vector added to its diagonal first (null: nothing; padding rows get 1 either
+/// way).  Out: tiles = lower part of (M + diag(addend))^-1 (zero padding), U = (M + diag(addend))^-1 Y; Dinv keeps the inverted diagonal tiles of
+/// the factor (ln det).  r4 is not read.
+template <int NT, bool PLAIN = false>
 __device__ __forceinline__ void cholesky_inverse_tiles(double *Lt, double *Dinv, int nt, int n_true, const double *Y, double *U,
-                                                       double *Tv, const double *r4, int tid, uint32_t *status, unsigned long long *wave_busy = nullptr)
+                                                       double *Tv, const double *r4, int tid, uint32_t *status, unsigned long long *wave_busy = nullptr,
+                                                       const double *addend = nullptr)
 {
 #ifdef ASLAM_STAMPS
         // diagnostic builds: per role, shader cycles busy between the barriers of the factorisation loop (slot 0) and, for the diagonal wave, inside the
@@ -838,7 +848,12 @@ __device__ __forceinline__ void cholesky_inverse_tiles(double *Lt, double *Dinv,
         constexpr int DW = NT;
         const int wave = role_of_wave(__builtin_amdgcn_readfirstlane(tid >> 6), DW), lane = tid & 63;
         const int li = lane & 15, lg = lane >> 4;
-        if (tid < 16 * nt)
+        if constexpr (PLAIN)
+        {
+                if (tid < 16 * nt)
+                        *tile_elem(Lt, tid, tid) += (tid < n_true) ? (addend ? addend[tid] : 0.0) : 1.0; // padding decouples
+        }
+        else if (tid < 16 * nt)
                 *tile_elem(Lt, tid, tid) += (tid < n_true) ? meas_r(r4, tid) : 1.0; // S = P~ + R; padding decouples
         __syncthreads();
         if (wave < nt)
@@ -905,7 +920,9 @@ __device__ __forceinline__ void cholesky_inverse_tiles(double *Lt, double *Dinv,
                                         Lt[tile_index(cb, rb) * TSZ + (lg + 4 * q) * TLD + li] = acc[cb][q];
                         }
                 }
-                const double r_u = (16 * rb + li < n_true) ? meas_r(r4, 16 * rb + li) : 1.0; // r_i of this lane's row of U (in flight across the barrier)
+                double r_u = 1.0;
+                if constexpr (!PLAIN)
+                        r_u = (16 * rb + li < n_true) ? meas_r(r4, 16 * rb + li) : 1.0; // r_i of this lane's row of U (in flight across the barrier)
                 __syncthreads(); // [A] L^-1 complete, t published
                 // U = Kt Y = Y - R S^-1 Y = Y - R L^-T t: this wave's rows of L^-T are its accumulators
                 {
@@ -923,7 +940,7 @@ __device__ __forceinline__ void cholesky_inverse_tiles(double *Lt, double *Dinv,
                         pu += __shfl_xor(pu, 16);
                         pu += __shfl_xor(pu, 32);
                         if (lg == 0)
-                                U[16 * rb + li] = Y[16 * rb + li] - r_u * pu;
+                                U[16 * rb + li] = PLAIN ? pu : Y[16 * rb + li] - r_u * pu; // (PLAIN: S^-1 Y itself)
                 }
                 WB(2); // (row-block roles: everything behind the factorisation loop -- L^-1 to the tiles, the L^-T L^-1 product, r I - r^2 S^-1)
         }
@@ -1016,6 +1033,28 @@ __device__ __forceinline__ void cholesky_inverse_tiles(double *Lt, double *Dinv,
 #ifdef ASLAM_STAMPS
                 tp1_ = __builtin_amdgcn_s_memtime();
 #endif
+                if constexpr (PLAIN)
+                {
+                        __syncthreads(); // [B] nobody reads L^-1 any more
+#pragma unroll
+                        for (int qq = 0; qq < TPW; ++qq)
+                        {
+                                if (orb[qq] >= 0)
+                                {
+                                        const int rbq = orb[qq], jbq = ojb[qq];
+                                        double *const T = Lt + tile_index(rbq, jbq) * TSZ + li;
+#pragma unroll
+                                        for (int q = 0; q < 4; ++q)
+                                        {
+                                                const int i = 16 * rbq + lg + 4 * q, j = 16 * jbq + li;
+                                                if (j <= i) // (a diagonal tile keeps its lower entries only)
+                                                        T[(lg + 4 * q) * TLD] = (i < n_true) ? out[qq][q] : 0.0;
+                                        }
+                                }
+                        }
+                }
+                else
+                {
                 const double r_rng = r4[2], r_brg = r4[3]; // (in flight across the barrier)
                 __syncthreads(); // [B] nobody reads L^-1 any more
                 // r_i r_j of this lane's entries without a look-up per entry (profiles/params.md): the tile offsets and 4 q are even, so row
@@ -1074,6 +1113,7 @@ __device__ __forceinline__ void cholesky_inverse_tiles(double *Lt, double *Dinv,
                                 }
                         }
                 }
+                } // !PLAIN
         }
 #ifdef ASLAM_STAMPS
         if (wave_busy && lane == 0)
@@ -1173,6 +1213,15 @@ template <int NT> __device__ __forceinline__ SmallLds small_carve(unsigned char 
         L.sLm = reinterpret_cast<float *>(smem + LY::oLm);
         L.sm = reinterpret_cast<SmallShared *>(smem + LY::oSm);
         return L;
+}
+
+/// This filter's row of DevView::sighted, kept in LDS for the launch (the EKF kernels put it there behind small_load): four spare floats of the association scratch --
+/// entries 0 .. 11 of sPd are the wait-list walk's, the staging area of small_prefetch_intake starts at 16.  The front end writes the mask of
+/// every callback through it; as a kernel argument alive in scalar registers for the whole launch the pointer cost the single-CU EKF kernels
+/// a register (and with it four more bytes of scratch per lane) in front of every phase.
+__device__ __forceinline__ uint8_t *&small_mask_ptr(const SmallLds &L)
+{
+        return *reinterpret_cast<uint8_t **>(L.sPd + 12);
 }
 
 /// Bring filter `b` from HBM into LDS (vectors, scalars, stored sensor message, wait-list).
@@ -1593,8 +1642,11 @@ __device__ __forceinline__ bool small_frontend(const DevView &d, const SmallLds 
         }
         // sighted landmarks (at least one observation associated: exactly the ones whose Z entries were just rewritten), straight to HBM, before
         // the wait-list walk reuses sNew for the promotions
+        uint8_t *const sgt = small_mask_ptr(L); // the mask of this callback (read by the kernels only under aslam_sighted_update_enable)
         for (int k = tid; k < nl; k += SMALL_WG)
         {
+                if (IS_EKF)
+                        sgt[k] = sNew[k] >= 0 ? 1 : 0; // the mask of this callback (the UKF contexts have none)
                 if (sNew[k] >= 0)
                 {
                         seen[k] = clk;
@@ -1757,6 +1809,8 @@ __device__ __forceinline__ bool small_frontend(const DevView &d, const SmallLds 
                                                 sX[n0 + 2 * k + 1] = sZ[1] + zr * sin(sZ[2] + zb);
                                                 seen[nl + k] = clk; // promoted now, never sighted as a landmark
                                                 hits[nl + k] = 0u;
+                                                if (IS_EKF)
+                                                        sgt[nl + k] = 0; // initialised from this very reading: not sighted
                                         }
                                         sm.grow_from = n0;
                                         sm.n = nn;

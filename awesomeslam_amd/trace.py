@@ -382,3 +382,25 @@ def dim_cap(L):
     """Smallest MAX_LANDMARK_COUNT (config.h:45; compared against the state DIMENSION, ekf.cpp:263) that
     admits L landmarks: growth is refused when N >= cap."""
     return full_dim(L) + 1
+
+
+def limit_range(trace, r, t_from=0):
+    """A copy of `trace` (a Trace or one Trajectory of it) whose sensor has range `r` from callback `t_from` on: the observations with
+    range > r are removed there and the rest of each message moves up in order (`obs` compacted, zeros behind, `n_obs` lowered).  Everything
+    else, max_obs included, is as it was.  Pure: `trace` is not touched."""
+    import copy
+
+    out = copy.copy(trace)
+    obs = np.array(trace.obs, np.float32, copy=True)
+    n_obs = np.array(trace.n_obs, np.int32, copy=True)
+    T, slots = obs.shape[-3], obs.shape[-2]
+    live = np.arange(slots) < n_obs[..., None]
+    keep = live & ((obs[..., 0] <= np.float32(r)) | (np.arange(T)[:, None] < int(t_from)))
+    order = np.argsort(~keep, axis=-1, kind="stable")  # kept entries first, in message order
+    obs = np.take_along_axis(obs, order[..., None], axis=-2)
+    n_obs = keep.sum(axis=-1).astype(np.int32)
+    obs[~(np.arange(slots) < n_obs[..., None])] = 0.0
+    out.obs, out.n_obs = np.ascontiguousarray(obs), n_obs
+    if hasattr(trace, "meta"):
+        out.meta = dict(trace.meta, limit_range=(float(r), int(t_from)))
+    return out

@@ -182,6 +182,15 @@ int aslam_ekf_step_batch(aslam_ctx *ctx, const float *vx, const float *az, const
                          const double *a00, const double *a10, double *X_out, int ldx, void *stream);
 int aslam_ukf_step_batch(aslam_ctx *ctx, const float *vx, const float *az, const float *dt, const double *Z, int ldz,
                          double *X_out, int ldx, void *stream);
+/* The two EKF seams with the mask of the callback: sighted[k] != 0 where the host's association gave landmark k an observation in this
+ * callback ([n_landmarks] bytes; the batch form: [batch][ld], row b = filter b, its first (N_b - 3) / 2 entries are used).  Copied down like Z;
+ * aslam_get_sighted returns it.  The mask is applied under aslam_sighted_update_enable only; with the mode off these are aslam_ekf_step[_batch]
+ * that also record the mask.  Under the mode the plain aslam_ekf_step[_batch] treat EVERY landmark as sighted (they record an all-ones mask):
+ * the same update as the _sighted call with all ones, bit for bit. */
+int aslam_ekf_step_sighted(aslam_ctx *ctx, int traj, float vx, float az, float dt, const double *Z, const uint8_t *sighted, double a00,
+                           double a10, double *X_out, void *stream);
+int aslam_ekf_step_batch_sighted(aslam_ctx *ctx, const float *vx, const float *az, const float *dt, const double *Z, int ldz,
+                                 const uint8_t *sighted, int ld, const double *a00, const double *a10, double *X_out, int ldx, void *stream);
 
 /* ---- the replay seam (the whole callback, association and growth included, runs on the device) ----- */
 /* Bind a trace.  Host pointers are copied to HBM; device pointers are used in place and must stay valid. */
@@ -208,6 +217,22 @@ int aslam_innovation_enable(aslam_ctx *ctx, int on);
 /* the record of filter `traj` (synchronises like the getters below); ASLAM_ERR_STATE when the record is off; NaN before the first callback
  * and after a callback in which slam() did not run */
 int aslam_get_innovation(aslam_ctx *ctx, int traj, double *nis, double *logdet);
+
+/* ---- sighted-only update (EKF contexts; off by default) --------------------------------------------------------------------------
+   The reference uses every mapped landmark as a measurement in every update, with the stale range / bearing Z keeps for a landmark that was
+   not re-observed (ekf.cpp:175-181, 300-310).  With the mode on, a callback updates with the pose rows and the rows of the landmarks SIGHTED in
+   it alone: landmark k is sighted iff the association walk of the callback gave it at least one observation (the condition under which
+   aslam_get_sightings' hits[k] goes up; a re-walked stored message counts; a landmark promoted in this callback is not sighted).  With
+   M = {0, 1, 2} + {3 + 2k, 4 + 2k : k sighted}:  S = H_M P H_M^T + R_M,  K = P H_M^T S^-1,  X += K Y_M,  P = (I - K H_M) P.  Predict, updateH,
+   angle wrapping and all bookkeeping are unchanged; a callback with nothing sighted still applies the three pose rows.  aslam_replay[_stats],
+   aslam_ekf_step[_batch][_sighted] honour the mode; NIS and ln det S are then those of S_M and Y_M.  Context-wide; synchronises; kept by
+   aslam_reset; not carried by snapshots.  ASLAM_ERR_UNSUPPORTED on a UKF context.  A context that never switches it on launches exactly the
+   kernels it launched before the mode existed.  (Large-state contexts: ASLAM_GS_TILES=1 is ignored under the mode -- large_build_GS runs.) */
+int aslam_sighted_update_enable(aslam_ctx *ctx, int on);
+/* The mask the last callback of filter `traj` used (replay: written by the front end every callback, mode on or off; steps: what the call
+ * recorded): min(cap, *n_landmarks) entries, the rest of sighted[cap] is zeroed.  aslam_reset, aslam_restore (restored slots) and
+ * aslam_remove_landmarks (filters that lost a landmark) zero it.  Synchronises like the getters. */
+int aslam_get_sighted(aslam_ctx *ctx, int traj, uint8_t *sighted, int cap, int *n_landmarks);
 
 /* ---- removing landmarks from running filters ------------------------------------------------------- */
 /* mask [batch][ld] u8, host or device (is_device; a device mask 16-byte aligned): entry (b, i) != 0 removes landmark i of filter b.
