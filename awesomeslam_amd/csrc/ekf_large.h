@@ -1185,6 +1185,15 @@ __global__ __launch_bounds__(256) void large_syrk(DevView d, LargeView<T> lv, in
 #define ASLAM_XU_ROWS 8
 #endif
 constexpr int XU_ROWS = ASLAM_XU_ROWS; // (rows per wave of large_x_update_rows; 4 and 16 measured in round 4: profiles/r04_experiments.md)
+#ifndef ASLAM_XU_WAVES
+#define ASLAM_XU_WAVES 8
+#endif
+constexpr int XU_WAVES = ASLAM_XU_WAVES;         // waves per workgroup of large_x_update_rows (4, 8 and 16 measured: profiles/xupdate.md)
+constexpr int XU_THREADS = 64 * XU_WAVES;
+constexpr int XU_WG_ROWS = XU_WAVES * XU_ROWS;   // rows of V per workgroup
+typedef double xu_d2 __attribute__((ext_vector_type(2)));
+constexpr int XU_STAGE_THREADS = 256;            // waves 0 .. 3 stage the shared rows of a border and sum its dot products, whatever XU_WAVES is
+static_assert(XU_WAVES >= 4 && XU_WAVES <= 16, "large_x_update_rows: 4 staging waves at least, 1024 threads at most");
 
 /// P -= V V^T with the binary32 products formed on the BF16 matrix pipe ("bf16x3"): every float is the exact sum of three bf16 pieces of
 /// eight mantissa bits (a = a1 + a2 + a3), and  a b ~= a1 b1 + (a1 b2 + a2 b1) + (a1 b3 + a2 b2 + a3 b1):  six v_mfma_f32_16x16x32_bf16
@@ -1530,9 +1539,16 @@ __global__ __launch_bounds__(256) void large_x_update(DevView d, LargeView<T> lv
 /// diagonal is where the error of the fp32 path was largest) and the three POSE columns (the pose block changes by as much as it holds in
 /// every callback, Q against the update, so eps32 |dP| is eps32 |P| there), which are subtracted from P: P(a,a), P(a,0..2) and the mirror
 /// image P(0..2,a).  Costs four more FMAs per element of a row the kernel reads anyway.  The four rows
-/// every row of V is multiplied with -- q and the pose rows of V -- staged ONCE per workgroup in LDS (17 KB) for the XU_ROWS x 4 rows its waves
-/// walk.  With a wave per row and the shared rows read from memory every wave issued 25 loads of 16 bytes per lane for 4 KB of new data: 391 us
-/// per 256 filters against 217 us for round 2's single product (profiles/r03_experiments.md).  grid (ceil(NP / (4 XU_ROWS)), B), 256 threads.
+/// every row of V is multiplied with -- q and the pose rows of V -- staged ONCE per workgroup in LDS, widened to binary64 (XuStaged: 60 KB with the
+/// rows of l), for the XU_ROWS x XU_WAVES rows its waves walk.  With a wave per row and the shared rows read from memory every wave issued 25 loads of 16 bytes per lane for 4 KB of new data: 391 us
+/// per 256 filters against 217 us for round 2's single product (profiles/r03_experiments.md).  grid (ceil(NP / XU_WG_ROWS), B), XU_THREADS threads.
+///
+/// XU_WAVES waves of XU_ROWS rows each share one staging and one border prologue.  Waves 0 .. 3 do the prologue's staging and sums with the strides of a
+/// 256-thread workgroup, whatever XU_WAVES is, and a wave's walk over its rows does not depend on it either: every XU_WAVES gives the same bits.  Every
+/// wave issues the loads of its first row in front of the workgroup's one barrier.  What the prologue leaves behind (L22^-1, V2 of row n and of the pose
+/// rows) is the same in every thread and is moved to scalar registers: the row loop fits 128 vector registers, so that two workgroups of 8 waves (or
+/// one of 16) share a CU, four waves per SIMD.  XU_WAVES = 8: 17 workgroups of 64 rows for the 1027 rows of the benchmark; 4, 8 and 16 are measured
+/// in profiles/xupdate.md.
 ///
 /// THE BORDER (large_border): for a filter with a tail of t <= 3 rows past its last full 64-block the Cholesky and the TRSM in front of this kernel
 /// have covered the n0 = n - t leading columns only, and this kernel -- which runs IN FRONT OF the syrk then -- finishes the factorisation:
@@ -1550,6 +1566,21 @@ __global__ __launch_bounds__(256) void large_x_update(DevView d, LargeView<T> lv
 constexpr int XU_SH_ROWS = 4 + BORDER_MAX;                                      // staged rows: q, pose rows 0 .. 2 of V, l_0 .. l_2
 constexpr int XU_NDOT = 4 * BORDER_MAX + BORDER_MAX * (BORDER_MAX + 1) / 2;     // {q, pose rows} . l_k, then the lower triangle of l l^T
 
+/// One staged row in LDS, widened to binary64 ONCE per workgroup (the conversion is exact) instead of once per row of V and element in every wave: of the
+/// 8 conversions and 8 FMAs per element of V the row loop keeps one conversion.  Columns 4c, 4c + 1 of the row are h[0][c], columns 4c + 2, 4c + 3 are
+/// h[1][c]: a lane owns four consecutive columns and reads them as two 16-byte accesses, each of them dense over the wave (no bank conflict).
+struct XuStaged
+{
+        xu_d2 h[2][LARGE_NP_MAX / 4];
+        __device__ __forceinline__ void put(int j, const f4 &r)
+        {
+                h[0][j >> 2] = (xu_d2){(double)r[0], (double)r[1]};
+                h[1][j >> 2] = (xu_d2){(double)r[2], (double)r[3]};
+        }
+};
+
+__device__ __forceinline__ float readfirstlane_f32(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+
 /// what a workgroup knows of its filter's border; the same values in every thread
 struct XuBorder
 {
@@ -1558,8 +1589,9 @@ struct XuBorder
         bool ok;                           // every pivot of C was positive
 };
 
-/// stages the shared rows (columns < n0 only) and solves the border; contains the workgroup's one barrier
-__device__ __forceinline__ XuBorder x_update_border(float (*sh)[LARGE_NP_MAX], double (*red)[XU_NDOT], const LargeView<float> &lv, int b, int n, const LargeBorder &bd)
+/// stages the shared rows (columns < n0 only) and solves the border; contains the workgroup's one barrier.  Staging and sums are the work of threads
+/// 0 .. XU_STAGE_THREADS - 1, the 3 x 3 behind the barrier of every thread
+__device__ __forceinline__ XuBorder x_update_border(XuStaged *sh, double (*red)[XU_NDOT], const LargeView<float> &lv, int b, int n, const LargeBorder &bd)
 {
         constexpr int BM = BORDER_MAX;
         const int NP = lv.NP, tid = threadIdx.x, t = bd.t, n0 = LB * bd.nbc;
@@ -1580,47 +1612,62 @@ __device__ __forceinline__ XuBorder x_update_border(float (*sh)[LARGE_NP_MAX], d
 #pragma unroll
         for (int i = 0; i < XU_NDOT; ++i)
                 dot[i] = 0.0;
-        for (int j = 4 * tid; j < n0; j += 4 * 256)
+        if (tid < XU_STAGE_THREADS) // (wave-uniform)
         {
-                f4 r[XU_SH_ROWS];
-                r[0] = *reinterpret_cast<const f4 *>(G + (size_t)n * NP + j);
-#pragma unroll
-                for (int m = 0; m < 3; ++m)
-                        r[1 + m] = *reinterpret_cast<const f4 *>(G + (size_t)m * NP + j);
-#pragma unroll
-                for (int k = 0; k < BM; ++k)
-                        r[4 + k] = k < t ? *reinterpret_cast<const f4 *>(G + (size_t)(n + 1 + k) * NP + j) : (f4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int m = 0; m < XU_SH_ROWS; ++m)
-                        *reinterpret_cast<f4 *>(&sh[m][j]) = r[m];
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
+                for (int j = 4 * tid; j < n0; j += 4 * XU_STAGE_THREADS)
                 {
+                        f4 r[XU_SH_ROWS];
+                        r[0] = *reinterpret_cast<const f4 *>(G + (size_t)n * NP + j);
 #pragma unroll
-                        for (int m = 0; m < 4; ++m)
+                        for (int m = 0; m < 3; ++m)
+                                r[1 + m] = *reinterpret_cast<const f4 *>(G + (size_t)m * NP + j);
 #pragma unroll
-                                for (int k = 0; k < BM; ++k)
-                                        dot[BM * m + k] = fma((double)r[m][e], (double)r[4 + k][e], dot[BM * m + k]);
+                        for (int k = 0; k < BM; ++k)
+                                r[4 + k] = k < t ? *reinterpret_cast<const f4 *>(G + (size_t)(n + 1 + k) * NP + j) : (f4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                        for (int i = 0; i < BM; ++i)
+                        for (int m = 0; m < XU_SH_ROWS; ++m)
+                                sh[m].put(j, r[m]);
 #pragma unroll
-                                for (int k = 0; k <= i; ++k)
-                                        dot[4 * BM + i * (i + 1) / 2 + k] = fma((double)r[4 + i][e], (double)r[4 + k][e], dot[4 * BM + i * (i + 1) / 2 + k]);
+                        for (int e = 0; e < 4; ++e)
+                        {
+#pragma unroll
+                                for (int m = 0; m < 4; ++m)
+#pragma unroll
+                                        for (int k = 0; k < BM; ++k)
+                                                dot[BM * m + k] = fma((double)r[m][e], (double)r[4 + k][e], dot[BM * m + k]);
+#pragma unroll
+                                for (int i = 0; i < BM; ++i)
+#pragma unroll
+                                        for (int k = 0; k <= i; ++k)
+                                                dot[4 * BM + i * (i + 1) / 2 + k] = fma((double)r[4 + i][e], (double)r[4 + k][e], dot[4 * BM + i * (i + 1) / 2 + k]);
+                        }
                 }
-        }
-#pragma unroll
-        for (int i = 0; i < XU_NDOT; ++i)
-                dot[i] = wave_sum_dpp(dot[i]);
-        if ((tid & 63) == 63)
-        {
 #pragma unroll
                 for (int i = 0; i < XU_NDOT; ++i)
-                        red[tid >> 6][i] = dot[i];
+                        dot[i] = wave_sum_dpp(dot[i]);
+                if ((tid & 63) == 63)
+                {
+#pragma unroll
+                        for (int i = 0; i < XU_NDOT; ++i)
+                                red[tid >> 6][i] = dot[i];
+                }
         }
         __syncthreads();
+        // (S22 and G2 were loaded from addresses every thread shares: kept as the 18 floats they are while the loads were in flight, scalars from here on)
+#pragma unroll
+        for (int i = 0; i < BM; ++i)
+#pragma unroll
+                for (int j = 0; j <= i; ++j)
+                        s22[i][j] = readfirstlane_f32(s22[i][j]);
+#pragma unroll
+        for (int k = 0; k < BM; ++k)
+#pragma unroll
+                for (int m = 0; m < 4; ++m)
+                        g2[m][k] = readfirstlane_f32(g2[m][k]);
+        static_assert(XU_STAGE_THREADS == 4 * 64, "the sum below is written out for four staging waves");
 #pragma unroll
         for (int i = 0; i < XU_NDOT; ++i)
-                dot[i] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
+                dot[i] = readfirstlane_f64((red[0][i] + red[1][i]) + (red[2][i] + red[3][i]));
         // C = S22 - l l^T, its Cholesky factor and the inverse of that (rows >= t: the identity)
         XuBorder bx;
         double L[BM][BM];
@@ -1665,44 +1712,58 @@ __device__ __forceinline__ XuBorder x_update_border(float (*sh)[LARGE_NP_MAX], d
         return bx;
 }
 
-/// the XU_ROWS rows of one wave.  BORDER: the pass stops at n0; the row's G2 (columns n0 .. n0 + 3: 16 aligned bytes, zero from column n on) rides along
-/// with the loads of the row
+/// passes of 64 lanes x 4 columns over a row: 5 x 256 = 1280 >= LARGE_NP_MAX; with a border the pass stops at n0 <= LARGE_NP_MAX - LB = 4 x 256
+template <bool BORDER> constexpr int XU_NPASS = BORDER ? 4 : 5;
+static_assert(5 * 256 >= LARGE_NP_MAX && 4 * 256 >= LARGE_NP_MAX - LB, "large_x_update_rows: passes per row");
+
+/// the first row of wave `wave` of workgroup `xb`
+__device__ __forceinline__ int x_update_first_row(int xb, int wave) { return (xb * XU_WAVES + wave) * XU_ROWS; }
+
+/// row a of V (of filter matrix G) into registers: 16 bytes per lane and pass.  BORDER: the pass stops at n0 (= jlim); the row's G2 (columns n0 .. n0 + 3:
+/// 16 aligned bytes, zero from column n on) rides along with the loads of the row
+template <bool BORDER>
+__device__ __forceinline__ void x_update_load_row(f4 (&v)[XU_NPASS<BORDER>], f4 &g2, const float *G, int NP, int n, int jlim, int n0, int a)
+{
+        const int lane = threadIdx.x & 63;
+        const float *vr = G + (size_t)min(a, n - 1) * NP;
+#pragma unroll
+        for (int i = 0; i < XU_NPASS<BORDER>; ++i)
+        {
+                const int j = 4 * lane + 256 * i;
+                v[i] = j < jlim ? *reinterpret_cast<const f4 *>(vr + j) : (f4){0.f, 0.f, 0.f, 0.f}; // (columns n .. of every row of V are zero)
+        }
+        if constexpr (BORDER)
+                g2 = *reinterpret_cast<const f4 *>(vr + n0);
+}
+
+/// the XU_ROWS rows of one wave; vn, g2n: the wave's first row, loaded by the caller (x_update_load_row) in front of the workgroup's barrier
 template <int MODE, bool BORDER>
-__device__ __forceinline__ void x_update_rows_loop(const float (*sh)[LARGE_NP_MAX], const XuBorder &bx, const DevView &d, const LargeView<float> &lv, int b, int xb, int n,
-                                                   int n0, int s, int nsteps, double *poses_out, int32_t *dims_out)
+__device__ __forceinline__ void x_update_rows_loop(const XuStaged *sh, const XuBorder &bx, const DevView &d, const LargeView<float> &lv, int b, int xb, int n,
+                                                   int n0, int s, int nsteps, double *poses_out, int32_t *dims_out, f4 (&vn)[XU_NPASS<BORDER>], f4 &g2n)
 {
         const int NP = lv.NP;
         const int tid = threadIdx.x, lane = tid & 63;
         float *G = lv.G + (size_t)b * NP * NP;
         double *P = lv.P + (size_t)b * NP * NP;
-        const int a0 = (xb * 4 + (tid >> 6)) * XU_ROWS;
-        constexpr int NPASS = 5; // 5 x 64 lanes x 4 columns = 1280 >= LARGE_NP_MAX
+        const int a0 = x_update_first_row(xb, __builtin_amdgcn_readfirstlane(tid >> 6));
+        constexpr int NPASS = XU_NPASS<BORDER>;
         const int jlim = BORDER ? n0 : n;
-        auto load_row = [&](f4 (&v)[NPASS], f4 &g2, int a) {
-                const float *vr = G + (size_t)min(a, n - 1) * NP;
+        auto load_row = [&](f4 (&v)[NPASS], f4 &g2, int a) { x_update_load_row<BORDER>(v, g2, G, NP, n, jlim, n0, a); };
+        // What the prologue left, the same in every thread, as scalars: L22^-1, V2 of row n (q2) and of the pose rows
+        double Li[BORDER_MAX][BORDER_MAX];
+        float q2[BORDER_MAX], pv[3][BORDER_MAX];
 #pragma unroll
-                for (int i = 0; i < NPASS; ++i)
-                {
-                        const int j = 4 * lane + 256 * i;
-                        v[i] = j < jlim ? *reinterpret_cast<const f4 *>(vr + j) : (f4){0.f, 0.f, 0.f, 0.f}; // (columns n .. of every row of V are zero)
-                }
-                if constexpr (BORDER)
-                        g2 = *reinterpret_cast<const f4 *>(vr + n0);
-        };
-        // V2 of the pose rows, pinned in registers: selected by the row index below, and a select between members of a struct sends the whole struct
-        // to scratch memory
-        float pv[3][BORDER_MAX];
+        for (int k = 0; k < BORDER_MAX; ++k)
+        {
 #pragma unroll
-        for (int m = 0; m < 3; ++m)
+                for (int j = 0; j < BORDER_MAX; ++j)
+                        Li[k][j] = j <= k ? readfirstlane_f64(bx.Li[k][j]) : 0.0;
+                q2[k] = readfirstlane_f32(bx.v2[0][k]);
 #pragma unroll
-                for (int k = 0; k < BORDER_MAX; ++k)
-                {
-                        pv[m][k] = bx.v2[1 + m][k];
-                        asm volatile("" : "+v"(pv[m][k]));
-                }
+                for (int m = 0; m < 3; ++m)
+                        pv[m][k] = readfirstlane_f32(bx.v2[1 + m][k]);
+        }
         // the loads of row a + 1 are issued before row a is multiplied: the kernel lives on bytes in flight
-        f4 vn[NPASS], g2n = {0.f, 0.f, 0.f, 0.f};
-        load_row(vn, g2n, a0);
 #pragma unroll 1
         for (int r = 0; r < XU_ROWS; ++r)
         {
@@ -1716,6 +1777,20 @@ __device__ __forceinline__ void x_update_rows_loop(const float (*sh)[LARGE_NP_MA
                         v[i] = vn[i];
                 if (r + 1 < XU_ROWS)
                         load_row(vn, g2n, a + 1);
+                // The entries of P and X this row updates (nobody else touches them: P(a, 0 .. 2) with the mirror image, P(a, a), X(a)) are fetched NOW and
+                // needed behind the sums.  Fetched there, every row of every wave ended in a round trip to memory with nothing else of the wave in
+                // flight: 400 -> 343 us per 256 filters (profiles/xupdate.md)
+                double *prow = P + (size_t)a * NP;
+                double pold[3] = {0.0, 0.0, 0.0}, pdiag = 0.0, xold = 0.0;
+                if (lane == 63)
+                {
+#pragma unroll
+                        for (int j = 0; j < 3; ++j)
+                                if (j < a)
+                                        pold[j] = prow[j];
+                        pdiag = prow[a];
+                        xold = d.X[(size_t)b * NP + a];
+                }
                 double acc = 0.0, dd = 0.0, d0 = 0.0, d1 = 0.0, d2 = 0.0, e0 = 0.0, e1 = 0.0, e2 = 0.0;
 #pragma unroll
                 for (int i = 0; i < NPASS; ++i)
@@ -1723,31 +1798,48 @@ __device__ __forceinline__ void x_update_rows_loop(const float (*sh)[LARGE_NP_MA
                         const int j = 4 * lane + 256 * i;
                         if (j >= jlim)
                                 continue; // (beyond NP nothing was staged)
-                        const f4 wi = *reinterpret_cast<const f4 *>(&sh[0][j]), p0 = *reinterpret_cast<const f4 *>(&sh[1][j]),
-                                 p1 = *reinterpret_cast<const f4 *>(&sh[2][j]), p2 = *reinterpret_cast<const f4 *>(&sh[3][j]);
-                        f4 l0 = {0.f, 0.f, 0.f, 0.f}, l1 = l0, l2 = l0;
-                        if constexpr (BORDER)
-                                l0 = *reinterpret_cast<const f4 *>(&sh[4][j]), l1 = *reinterpret_cast<const f4 *>(&sh[5][j]), l2 = *reinterpret_cast<const f4 *>(&sh[6][j]);
 #pragma unroll
-                        for (int e = 0; e < 4; ++e)
+                        for (int h = 0; h < 2; ++h) // columns j, j + 1, then j + 2, j + 3: the order of the sums is that of the columns
                         {
-                                const double ve = (double)v[i][e];
-                                acc = fma(ve, (double)wi[e], acc);
-                                dd = fma(ve, ve, dd);
-                                d0 = fma(ve, (double)p0[e], d0);
-                                d1 = fma(ve, (double)p1[e], d1);
-                                d2 = fma(ve, (double)p2[e], d2);
+                                const xu_d2 wi = sh[0].h[h][j >> 2], p0 = sh[1].h[h][j >> 2], p1 = sh[2].h[h][j >> 2], p2 = sh[3].h[h][j >> 2];
+                                xu_d2 l0 = {0.0, 0.0}, l1 = l0, l2 = l0;
                                 if constexpr (BORDER)
+                                        l0 = sh[4].h[h][j >> 2], l1 = sh[5].h[h][j >> 2], l2 = sh[6].h[h][j >> 2];
+#pragma unroll
+                                for (int e = 0; e < 2; ++e)
                                 {
-                                        e0 = fma(ve, (double)l0[e], e0);
-                                        e1 = fma(ve, (double)l1[e], e1);
-                                        e2 = fma(ve, (double)l2[e], e2);
+                                        const double ve = (double)v[i][2 * h + e];
+                                        acc = fma(ve, wi[e], acc);
+                                        dd = fma(ve, ve, dd);
+                                        d0 = fma(ve, p0[e], d0);
+                                        d1 = fma(ve, p1[e], d1);
+                                        d2 = fma(ve, p2[e], d2);
+                                        if constexpr (BORDER)
+                                        {
+                                                e0 = fma(ve, l0[e], e0);
+                                                e1 = fma(ve, l1[e], e1);
+                                                e2 = fma(ve, l2[e], e2);
+                                        }
                                 }
                         }
                 }
                 acc = wave_sum_dpp(acc), dd = wave_sum_dpp(dd), d0 = wave_sum_dpp(d0), d1 = wave_sum_dpp(d1), d2 = wave_sum_dpp(d2);
                 if constexpr (BORDER)
                         e0 = wave_sum_dpp(e0), e1 = wave_sum_dpp(e1), e2 = wave_sum_dpp(e2);
+                if constexpr (BORDER)
+                {
+                        // q2 and the V2 of the pose rows, pinned in their scalar registers in every pass: they are selected by the row index below (a select
+                        // between members of a struct sends the whole struct to scratch memory), and widened to binary64 outside the loop they would
+                        // occupy 24 vector registers for all of it
+#pragma unroll
+                        for (int k = 0; k < BORDER_MAX; ++k)
+                        {
+                                asm volatile("" : "+s"(q2[k]));
+#pragma unroll
+                                for (int m = 0; m < 3; ++m)
+                                        asm volatile("" : "+s"(pv[m][k]));
+                        }
+                }
                 if (lane == 63)
                 {
                         if constexpr (BORDER)
@@ -1755,8 +1847,8 @@ __device__ __forceinline__ void x_update_rows_loop(const float (*sh)[LARGE_NP_MA
                                 // V2(a) = (G2(a) - V1(a) l^T) L22^-T, rounded to binary32 as it is stored; the pose rows take the values every
                                 // workgroup holds (the same expression over another order of summation)
                                 const double w0 = (double)g2[0] - e0, w1 = (double)g2[1] - e1, w2 = (double)g2[2] - e2;
-                                float x0 = (float)(w0 * bx.Li[0][0]), x1 = (float)(w0 * bx.Li[1][0] + w1 * bx.Li[1][1]),
-                                      x2 = (float)(w0 * bx.Li[2][0] + w1 * bx.Li[2][1] + w2 * bx.Li[2][2]);
+                                float x0 = (float)(w0 * Li[0][0]), x1 = (float)(w0 * Li[1][0] + w1 * Li[1][1]),
+                                      x2 = (float)(w0 * Li[2][0] + w1 * Li[2][1] + w2 * Li[2][2]);
                                 if (a < 3)
                                 {
                                         x0 = a == 0 ? pv[0][0] : a == 1 ? pv[1][0] : pv[2][0];
@@ -1769,24 +1861,25 @@ __device__ __forceinline__ void x_update_rows_loop(const float (*sh)[LARGE_NP_MA
                                 for (int k = 0; k < BORDER_MAX; ++k)
                                 {
                                         const double ve = (double)xs[k];
-                                        acc = fma(ve, (double)bx.v2[0][k], acc);
+                                        acc = fma(ve, (double)q2[k], acc);
                                         dd = fma(ve, ve, dd);
-                                        d0 = fma(ve, (double)bx.v2[1][k], d0);
-                                        d1 = fma(ve, (double)bx.v2[2][k], d1);
-                                        d2 = fma(ve, (double)bx.v2[3][k], d2);
+                                        d0 = fma(ve, (double)pv[0][k], d0);
+                                        d1 = fma(ve, (double)pv[1][k], d1);
+                                        d2 = fma(ve, (double)pv[2][k], d2);
                                 }
                         }
-                        double *prow = P + (size_t)a * NP;
                         const double dp[3] = {d0, d1, d2};
                         // pose columns j < min(a, 3) with their mirror image; the diagonal entry itself
-                        for (int j = 0; j < 3 && j < a; ++j)
-                        {
-                                const double pn = prow[j] - dp[j];
-                                prow[j] = pn;
-                                P[(size_t)j * NP + a] = pn;
-                        }
-                        prow[a] -= dd;
-                        const double xa = d.X[(size_t)b * NP + a] + acc;
+#pragma unroll
+                        for (int j = 0; j < 3; ++j)
+                                if (j < a)
+                                {
+                                        const double pn = pold[j] - dp[j];
+                                        prow[j] = pn;
+                                        P[(size_t)j * NP + a] = pn;
+                                }
+                        prow[a] = pdiag - dd;
+                        const double xa = xold + acc;
                         d.X[(size_t)b * NP + a] = xa;
                         if (MODE == MODE_REPLAY)
                         {
@@ -1799,27 +1892,30 @@ __device__ __forceinline__ void x_update_rows_loop(const float (*sh)[LARGE_NP_MA
         }
 }
 
-/// the body: workgroup `xb` of filter `b` (32 rows); sh = XU_SH_ROWS x LARGE_NP_MAX floats of LDS, red = 4 x XU_NDOT doubles
+/// the body: workgroup `xb` of filter `b` (XU_WG_ROWS rows); sh = XU_SH_ROWS staged rows in LDS, red = 4 x XU_NDOT doubles
 template <int MODE>
-__device__ __forceinline__ void x_update_rows_body(float (*sh)[LARGE_NP_MAX], double (*red)[XU_NDOT], const DevView &d, const LargeView<float> &lv, int b, int xb, int n,
+__device__ __forceinline__ void x_update_rows_body(XuStaged *sh, double (*red)[XU_NDOT], const DevView &d, const LargeView<float> &lv, int b, int xb, int n,
                                                    int s, int nsteps, double *poses_out, int32_t *dims_out)
 {
         const int NP = lv.NP;
         const int tid = threadIdx.x;
-        if (xb * 4 * XU_ROWS >= n)
+        if (xb * XU_WG_ROWS >= n)
                 return;
         float *G = lv.G + (size_t)b * NP * NP;
         const LargeBorder bd = large_border(n, lv.border);
         const int n0 = LB * bd.nbc;
-        XuBorder bx = {};
+        const int a0 = x_update_first_row(xb, __builtin_amdgcn_readfirstlane(tid >> 6));
+        f4 g20 = {0.f, 0.f, 0.f, 0.f};
         if (bd.t)
         {
-                bx = x_update_border(sh, red, lv, b, n, bd);
+                f4 v0[XU_NPASS<true>];
+                x_update_load_row<true>(v0, g20, G, NP, n, n0, n0, a0);
+                const XuBorder bx = x_update_border(sh, red, lv, b, n, bd);
                 if (xb == 0)
                 {
                         // row n of V, the border's block of Linv, the status
                         float *Lb = lv.Linv + ((size_t)b * LARGE_NB_MAX + bd.nbc) * LB * LB;
-                        for (int e = tid; e < LB * LB; e += 256)
+                        for (int e = tid; e < LB * LB; e += XU_THREADS)
                         {
                                 const int r = e >> 6, c = e & (LB - 1);
                                 double v = r == c ? 1.0 : 0.0;
@@ -1834,29 +1930,29 @@ __device__ __forceinline__ void x_update_rows_body(float (*sh)[LARGE_NP_MAX], do
                                         atomicOr(&d.status[b], 4u); // ASLAM_ST_NOT_PD
                         }
                 }
+                x_update_rows_loop<MODE, true>(sh, bx, d, lv, b, xb, n, n0, s, nsteps, poses_out, dims_out, v0, g20);
         }
         else
         {
-                for (int j = 4 * tid; j < NP; j += 4 * 256)
+                f4 v0[XU_NPASS<false>];
+                x_update_load_row<false>(v0, g20, G, NP, n, n, n0, a0);
+                for (int j = 4 * tid; j < NP; j += 4 * XU_THREADS)
                 {
-                        *reinterpret_cast<f4 *>(&sh[0][j]) = *reinterpret_cast<const f4 *>(G + (size_t)n * NP + j);
-                        *reinterpret_cast<f4 *>(&sh[1][j]) = *reinterpret_cast<const f4 *>(G + j);
-                        *reinterpret_cast<f4 *>(&sh[2][j]) = *reinterpret_cast<const f4 *>(G + NP + j);
-                        *reinterpret_cast<f4 *>(&sh[3][j]) = *reinterpret_cast<const f4 *>(G + 2 * (size_t)NP + j);
+                        sh[0].put(j, *reinterpret_cast<const f4 *>(G + (size_t)n * NP + j));
+                        sh[1].put(j, *reinterpret_cast<const f4 *>(G + j));
+                        sh[2].put(j, *reinterpret_cast<const f4 *>(G + NP + j));
+                        sh[3].put(j, *reinterpret_cast<const f4 *>(G + 2 * (size_t)NP + j));
                 }
                 __syncthreads();
+                x_update_rows_loop<MODE, false>(sh, XuBorder{}, d, lv, b, xb, n, n0, s, nsteps, poses_out, dims_out, v0, g20);
         }
-        if (bd.t)
-                x_update_rows_loop<MODE, true>(sh, bx, d, lv, b, xb, n, n0, s, nsteps, poses_out, dims_out);
-        else
-                x_update_rows_loop<MODE, false>(sh, bx, d, lv, b, xb, n, n0, s, nsteps, poses_out, dims_out);
 }
 
-/// grid (ceil(NP / (4 XU_ROWS)), B), 256 threads
+/// grid (ceil(NP / XU_WG_ROWS), B), XU_THREADS threads
 template <int MODE>
-__global__ __launch_bounds__(256) void large_x_update_rows(DevView d, LargeView<float> lv, int s, int nsteps, double *poses_out, int32_t *dims_out, const int *skipped)
+__global__ __launch_bounds__(XU_THREADS, 4) void large_x_update_rows(DevView d, LargeView<float> lv, int s, int nsteps, double *poses_out, int32_t *dims_out, const int *skipped)
 {
-        __shared__ __attribute__((aligned(16))) float sh[XU_SH_ROWS][LARGE_NP_MAX]; // q, pose rows 0 .. 2 of V, the rows of l (border)
+        __shared__ __attribute__((aligned(16))) XuStaged sh[XU_SH_ROWS]; // q, pose rows 0 .. 2 of V, the rows of l (border)
         __shared__ double red[4][XU_NDOT];
         const int b = blockIdx.y;
         if (skipped[b])

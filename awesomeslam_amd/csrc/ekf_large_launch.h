@@ -283,7 +283,7 @@ void launch_large_chain(const LargePlan &plan, const LargeGroup<T> &g, size_t ld
                 // the syrk launch, and on a side stream of its own -- and both were slower: 2436 us against 1997 + 324 per 256 filters, and 31.7 k
                 // against 36.4 k filter-steps/s (profiles/r04_experiments.md section 1)
                 auto x_update = [&]() {
-                        hipLaunchKernelGGL((large_x_update_rows<MODE>), dim3((NP + 4 * XU_ROWS - 1) / (4 * XU_ROWS), gb), dim3(256), 0, g.st, g.dv, vv, s, nsteps,
+                        hipLaunchKernelGGL((large_x_update_rows<MODE>), dim3((NP + XU_WG_ROWS - 1) / XU_WG_ROWS, gb), dim3(XU_THREADS), 0, g.st, g.dv, vv, s, nsteps,
                                            g.poses, g.dims, g.skip);
                 };
                 if (plan.border)
