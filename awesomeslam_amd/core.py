@@ -25,7 +25,7 @@ CORE_SYMBOLS = (
     "aslam_create", "aslam_destroy", "aslam_reset", "aslam_last_error", "aslam_abi_version", "aslam_set_state",
     "aslam_grow", "aslam_ekf_step", "aslam_ukf_step", "aslam_ekf_step_batch", "aslam_ukf_step_batch", "aslam_set_trace", "aslam_replay", "aslam_get_dim",
     "aslam_get_state", "aslam_get_A", "aslam_get_landmarks", "aslam_get_wait", "aslam_get_status",
-    "aslam_get_layout", "aslam_kernel_info", "aslam_get_launch_info",
+    "aslam_get_layout", "aslam_kernel_info", "aslam_get_launch_info", "aslam_get_syrk_tail",
     "aslam_replay_stats", "aslam_innovation_enable", "aslam_get_innovation",
     "aslam_params_default", "aslam_set_params", "aslam_get_params",
     "aslam_remove_landmarks", "aslam_select_beyond",
@@ -185,6 +185,7 @@ def core_lib():
         L.aslam_get_layout.argtypes = [vp, pi, ctypes.POINTER(ctypes.c_int64)]
         L.aslam_kernel_info.argtypes = [vp, ctypes.c_char_p, ci, pi, pi, pi]
         L.aslam_get_launch_info.argtypes = [vp, pi, pi, pi]
+        L.aslam_get_syrk_tail.argtypes = [vp, pi]
         L.aslam_remove_landmarks.argtypes = [vp, vp, ci, ci, vp]
         L.aslam_select_beyond.argtypes = [vp, pd, vp, ci, vp]
         L.aslam_get_sightings.argtypes = [vp, ci, pu, pu, ci, pi, pu]
@@ -743,6 +744,12 @@ class Core:
         g, r, l = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         _chk(core_lib().aslam_get_launch_info(self._h, ctypes.byref(g), ctypes.byref(r), ctypes.byref(l)))
         return {"stream_groups": g.value, "chol_resident": bool(r.value), "launches_per_callback": l.value}
+
+    def syrk_tail(self):
+        """Whether the last replay / step handed the syrk its tail rule (aslam_get_syrk_tail)."""
+        on = ctypes.c_int()
+        _chk(core_lib().aslam_get_syrk_tail(self._h, ctypes.byref(on)))
+        return bool(on.value)
 
 
 class Node:

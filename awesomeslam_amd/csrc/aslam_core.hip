@@ -1746,6 +1746,14 @@ int aslam_get_launch_info(aslam_ctx *c, int *stream_groups, int *chol_resident, 
         return ASLAM_OK;
 }
 
+int aslam_get_syrk_tail(aslam_ctx *c, int *on)
+{
+        if (!c || !on)
+                return fail(ASLAM_ERR_ARG, "null argument");
+        *on = c->large && c->lh.last_syrk_tail;
+        return ASLAM_OK;
+}
+
 int aslam_kernel_info(aslam_ctx *c, char *name, int name_cap, int *grid, int *block, int *lds_bytes)
 {
         if (!c)

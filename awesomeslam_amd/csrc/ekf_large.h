@@ -54,6 +54,7 @@ template <typename T> struct LargeView // (its arrays, their sizes per filter an
         unsigned short *Lpl; // binary32 mode with the bf16-pipe TRSM: LPlanes::base (bf16 planes of L and of the inverses, written by large_chol_resident), else nullptr
         int xrows;  // vector rows that ride in G behind the n state rows through the factorisation: 1 (EKF: Y^T), 2 (large-state UKF: z^T and the innovation, ukf_large.h)
         int border; // 1: this launch solves a short tail past the last full 64-block as a binary64 border (large_border below; set per launch from LargePlan::border), else 0
+        int syrk_tail; // 1: large_syrk_bf16x3<false> forms a last tile row of <= 16 state rows on the idle waves of its diagonal tiles (large_syrk_tail below; LargePlan::syrk_tail), else 0
 };
 
 // ---- MFMA traits -------------------------------------------------------------------------------------------------
@@ -175,6 +176,23 @@ __host__ __device__ __forceinline__ LargeBorder large_border(int n, int enabled)
         return {on ? t : 0, on ? n0 / LB : large_blocks(n)};
 }
 constexpr int BORDER_MAX = 3;  // widest border
+
+/// The tail rule of large_syrk_bf16x3 (LargeView::syrk_tail).  rl = (n - 1) / 128 is the last row of 128x128 tiles that holds state rows.  When it holds no
+/// more than 16 of them -- ONE 16-row MFMA tile; the benchmark's n = 1027 = 8 x 128 + 3 -- the tiles (rl, jt), jt < rl, would stage 33 slabs of 2 x 128 rows
+/// each for two waves' worth of one row tile.  Instead the idle wave of every diagonal tile (jt, jt), jt < rl, whose Bs already holds the planes of column
+/// tile jt, forms rows 128 rl .. n-1 x columns 128 jt .. + 127 with its A operand read straight into registers, and the tiles (rl, jt), jt < rl, return at
+/// once.  Same operands, same products in the same order, same epilogue arithmetic: bit-identical.  The corner tile (rl, rl) stays as it is.
+/// `rows` = 0: no tail for this n (every tile of row rl runs as without the rule).
+struct SyrkTail
+{
+        int rl;   // last tile row with state rows
+        int rows; // state rows in it when the rule holds (1 .. 16), else 0
+};
+__host__ __device__ __forceinline__ SyrkTail large_syrk_tail(int n, int enabled)
+{
+        const int rl = (n - 1) / 128, t = n - 128 * rl;
+        return {rl, enabled && rl >= 1 && t <= 16 ? t : 0};
+}
 // Rows n+1 .. n+t of G are spare (n + 1 + t <= n0 + 7 < n0 + 64 <= NP; nothing downstream reads them as V: the syrk stores no row >= n, large_stats and
 // the X update read row n and rows < n).  Row n+1+k carries row k of S21 in columns < n0 and, in columns n0 + BORDER_SAVE + m, a copy of column n0 + k
 // of the rows of G2 every workgroup of the X update needs while their owners overwrite them with V2: m = 0 .. 2 the pose rows, m = 3 row n (Y^T).
@@ -1221,6 +1239,12 @@ static_assert(XU_WAVES >= 4 && XU_WAVES <= 16, "large_x_update_rows: 4 staging w
 /// chain, in front of this one; launch 6, behind it, without the border.
 /// RUNNING = false is the default chain's kernel.  RUNNING = true (ASLAM_SYRK_RUNNING=1) is round 2's accumulation order, kept for comparison: every tile
 /// takes the general path and the six products of a slab are added straight into the running sum (profiles/r03_experiments.md).
+///
+/// THE TILE MAP has one exception (large_syrk_tail above; RUNNING = false with LargeView::syrk_tail): a last tile row rl that holds no more than 16 state
+/// rows -- the benchmark's rows 1024 .. 1026 -- has no tiles of its own left of the corner.  Tiles (rl, jt), jt < rl, return at once; in diagonal tile
+/// (jt, jt) the wave of the upper quadrant, which otherwise only helps to stage, forms those rows x the 128 columns of tile jt from the Bs of its
+/// workgroup (`tailw` below) and stores them with the epilogue's arithmetic.  Bit-identical to the tile row (tests/test_gpu_large_syrk_tail.py;
+/// profiles/syrk_tail.md).
 template <bool RUNNING>
 __global__ __launch_bounds__(256, 3) void large_syrk_bf16x3(DevView d, LargeView<float> lv, int nfilters, const int *skipped)
 {
@@ -1248,6 +1272,9 @@ __global__ __launch_bounds__(256, 3) void large_syrk_bf16x3(DevView d, LargeView
         const int jt = tl - rt * (rt + 1) / 2;
         if (rt * TB >= n)
                 return;
+        const SyrkTail tail = large_syrk_tail(n, !RUNNING && lv.syrk_tail);
+        if (tail.rows && rt == tail.rl && jt < rt)
+                return; // (formed by the idle waves of the diagonal tiles (jt, jt): tailw below)
         const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lg = lane >> 4;
         const int wr = (wave >> 1) * 64, wc = (wave & 1) * 64;
         const float *G = lv.G + (size_t)b * NP * NP;
@@ -1310,7 +1337,23 @@ __global__ __launch_bounds__(256, 3) void large_syrk_bf16x3(DevView d, LargeView
         const int kend = min(na, (n + KC - 1) / KC * KC); // columns n .. na-1 of V are zero (G = P H^T is zero there and L is the identity)
         const int a_off = (wr + li) * LDB + 8 * (lg ^ (li >> 2)), b_off = (wc + li) * LDB + 8 * (lg ^ (li >> 2)); // swizzled k-group
         const int s_off = lrow * LDB + 8 * ((lc0 >> 3) ^ ((lrow & 15) >> 2)) + (lc0 & 4); // this thread's 8 bytes of a staged row (rows lrow + 32 q: same row & 15)
+        // The tail (large_syrk_tail): the idle wave of diagonal tile (jt, jt), jt < rl, forms rows 128 rl .. n-1 x the 128 columns of tile jt.  Bs holds the B
+        // operands (what tile (rl, jt) would stage again: column rows 16 v + li, v = 0 .. 7); the A operand, V(128 rl + li, kc + 8 lg .. + 7) for lane (li, lg),
+        // comes straight from memory, two 16-byte loads a slab ahead, and is split as stash() splits: no LDS, no barrier.  The eight accumulators are
+        // acc[0][0..3], acc[1][0..3].  The wave's other accumulators are dead, and what the path carries from slab to slab lives in them -- acc[3][0..1] the
+        // prefetched floats, acc[3][2][0] the bits of the row's byte offset in G -- so that the kernel needs no register more than without the path.
+        const bool tailw = idle && tail.rows && rt < tail.rl; // (wave-uniform, like idle; left to the compiler as a divergent condition: made scalar, hipcc spills accumulators inside the K loop)
+        f4 &tp0 = acc[3][0], &tp1 = acc[3][1];
+        if (tailw) // (rows past the tail: clamped like the staging; MFMA rows do not mix)
+                acc[3][2][0] = __builtin_bit_cast(float, 4u * (unsigned)(min(tail.rl * TB + li, na - 1) * NP + 8 * lg));
+        auto tail_fetch = [&](int kc) {
+                const char *row = reinterpret_cast<const char *>(G + kc) + __builtin_bit_cast(unsigned, acc[3][2][0]);
+                tp0 = *reinterpret_cast<const f4 *>(row);
+                tp1 = *reinterpret_cast<const f4 *>(row + 16);
+        };
         fetch(0);
+        if (tailw)
+                tail_fetch(0);
         for (int kc = 0; kc < kend; kc += KC)
         {
 #pragma unroll
@@ -1375,6 +1418,34 @@ __global__ __launch_bounds__(256, 3) void large_syrk_bf16x3(DevView d, LargeView
                                 acc[3][vh + 1] += pb;
                         }
                 }
+                else if (tailw)
+                {
+                        // the products of tile (rl, jt), wave by wave: tail rows as the second operand, column rows as the first, the six MFMAs in the
+                        // order of the general path below, a zero-initialised temporary per column tile and slab
+                        u2x h0, m0, l0, h1, m1, l1;
+                        split_bf16x3(tp0, h0, m0, l0);
+                        split_bf16x3(tp1, h1, m1, l1);
+                        const u4 ap[3] = {(u4){h0[0], h0[1], h1[0], h1[1]}, (u4){m0[0], m0[1], m1[0], m1[1]}, (u4){l0[0], l0[1], l1[0], l1[1]}};
+                        if (kc + KC < kend)
+                                tail_fetch(kc + KC);
+#pragma unroll
+                        for (int v = 0; v < 8; ++v)
+                        {
+                                u4 bq[3];
+#pragma unroll
+                                for (int p = 0; p < 3; ++p)
+                                        bq[p] = *reinterpret_cast<const u4 *>(&Bs[p][b_off + (16 * v - wc) * LDB]);
+                                f4 tmp;
+                                ASLAM_MM(tmp, bq[0], ap[2], ((f4){0.f, 0.f, 0.f, 0.f}));
+                                ASLAM_MM(tmp, bq[1], ap[1], tmp);
+                                ASLAM_MM(tmp, bq[2], ap[0], tmp);
+                                ASLAM_MM(tmp, bq[0], ap[1], tmp);
+                                ASLAM_MM(tmp, bq[1], ap[0], tmp);
+                                ASLAM_MM(tmp, bq[0], ap[0], tmp);
+                                acc[v >> 2][v & 3] += tmp;
+                                __builtin_amdgcn_sched_barrier(0); // (as in the interior path: keep the operand reads of a column tile next to its MFMAs)
+                        }
+                }
                 else
                 {
 #pragma unroll
@@ -1424,74 +1495,85 @@ __global__ __launch_bounds__(256, 3) void large_syrk_bf16x3(DevView d, LargeView
 #undef ASLAM_MM
                 __syncthreads();
         }
-        if (idle)
+        if (idle && !tailw)
                 return;
         const bool mirror = (jt < rt || wc < wr);
         // The DIAGONAL of V V^T and its three POSE columns (and their mirror image, the pose rows) are formed with binary64 accumulation by the X-update
         // kernel (large_x_update_rows) and are NOT TOUCHED here -- not even read and stored back (a store-back of an old value would tie the order of the two
         // kernels).  Pose columns 0..2 = registers 0..2 of lane group 0 in the first
         // column tile of tile column 0 (posecols below: only its column 3 is updated, by 8-byte accesses); the diagonal is skipped element-wise.
-        const bool posecols_lane = (jt == 0 && wc == 0 && lg == 0);
+        // The K loop multiplies B x A^T (operands swapped), so a lane's four registers are four consecutive COLUMNS of one row of the
+        // lower tile: 32 contiguous bytes, two 16-byte loads and stores per 16x16 tile; the mirror image is the strided side (four
+        // 8-byte stores).  With A x B^T (four consecutive rows per lane: four 8-byte loads + stores, 16-byte mirror stores) the
+        // epilogue cost 0.66 ms per 256 filters against 0.33 ms (trsm_bench).
+        typedef double d2 __attribute__((ext_vector_type(2)));
+        // a lane's register quad: P(row, col0 .. col0 + 3) -= a, the new values also to the mirror positions
+        auto update4 = [&](int row, int col0, const f4 &a, bool diag16, bool posecols, bool mir) {
+                if (diag16 || posecols)
+                {
+                        // 16x16 tile on the diagonal: the elements J < I, each with its mirror image (J == I: the X update);
+                        // columns 0 .. 3: column 3 only
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                                if (col0 + r < row && !(posecols && r < 3) && col0 + r < n)
+                                {
+                                        double *pe = P + (size_t)row * NP + col0 + r;
+                                        const double pn = *pe - (double)a[r];
+                                        *pe = pn;
+                                        P[(size_t)(col0 + r) * NP + row] = pn;
+                                }
+                        return;
+                }
+                double *pp = P + (size_t)row * NP + col0;
+                double nv4[4];
+                if (col0 + 3 < n)
+                {
+                        const d2 o0 = *reinterpret_cast<const d2 *>(pp), o1 = *reinterpret_cast<const d2 *>(pp + 2);
+                        nv4[0] = o0[0] - (double)a[0], nv4[1] = o0[1] - (double)a[1];
+                        nv4[2] = o1[0] - (double)a[2], nv4[3] = o1[1] - (double)a[3];
+                        *reinterpret_cast<d2 *>(pp) = (d2){nv4[0], nv4[1]};
+                        *reinterpret_cast<d2 *>(pp + 2) = (d2){nv4[2], nv4[3]};
+                }
+                else
+                {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                                if (col0 + r < n)
+                                {
+                                        nv4[r] = pp[r] - (double)a[r];
+                                        pp[r] = nv4[r];
+                                }
+                }
+                if (mir)
+                {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                                if (col0 + r < n)
+                                        P[(size_t)(col0 + r) * NP + row] = nv4[r];
+                }
+        };
+        if (tailw)
         {
-                // The K loop multiplies B x A^T (operands swapped), so a lane's four registers are four consecutive COLUMNS of one row of the
-                // lower tile: 32 contiguous bytes, two 16-byte loads and stores per 16x16 tile; the mirror image is the strided side (four
-                // 8-byte stores).  With A x B^T (four consecutive rows per lane: four 8-byte loads + stores, 16-byte mirror stores) the
-                // epilogue cost 0.66 ms per 256 filters against 0.33 ms (trsm_bench).
-                typedef double d2 __attribute__((ext_vector_type(2)));
+                // rows 128 rl + li of the tail x column tile jt: what tile (rl, jt) stored (columns < 128 rl < n; pose columns where jt == 0)
+                const int row = tail.rl * TB + li;
+                if (row < n)
 #pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                        for (int v = 0; v < 4; ++v)
-                        {
-                                const int row = rt * TB + wr + 16 * u + li;
-                                const int col0 = jt * TB + wc + 16 * v + 4 * lg;
-                                if (row >= n || col0 >= n || (diagq && v > u))
-                                        continue;
-                                const bool posecols = posecols_lane && v == 0; // this lane's four columns are 0 .. 3
-                                if ((diagq && v == u) || posecols)
-                                {
-                                        // 16x16 tile on the diagonal: the elements J < I, each with its mirror image (J == I: the X update);
-                                        // columns 0 .. 3: column 3 only
-#pragma unroll
-                                        for (int r = 0; r < 4; ++r)
-                                                if (col0 + r < row && !(posecols && r < 3) && col0 + r < n)
-                                                {
-                                                        double *pe = P + (size_t)row * NP + col0 + r;
-                                                        const double pn = *pe - (double)acc[u][v][r];
-                                                        *pe = pn;
-                                                        P[(size_t)(col0 + r) * NP + row] = pn;
-                                                }
-                                        continue;
-                                }
-                                double *pp = P + (size_t)row * NP + col0;
-                                double nv4[4];
-                                if (col0 + 3 < n)
-                                {
-                                        const d2 o0 = *reinterpret_cast<const d2 *>(pp), o1 = *reinterpret_cast<const d2 *>(pp + 2);
-                                        nv4[0] = o0[0] - (double)acc[u][v][0], nv4[1] = o0[1] - (double)acc[u][v][1];
-                                        nv4[2] = o1[0] - (double)acc[u][v][2], nv4[3] = o1[1] - (double)acc[u][v][3];
-                                        *reinterpret_cast<d2 *>(pp) = (d2){nv4[0], nv4[1]};
-                                        *reinterpret_cast<d2 *>(pp + 2) = (d2){nv4[2], nv4[3]};
-                                }
-                                else
-                                {
-#pragma unroll
-                                        for (int r = 0; r < 4; ++r)
-                                                if (col0 + r < n)
-                                                {
-                                                        nv4[r] = pp[r] - (double)acc[u][v][r];
-                                                        pp[r] = nv4[r];
-                                                }
-                                }
-                                if (mirror || diagq)
-                                {
-#pragma unroll
-                                        for (int r = 0; r < 4; ++r)
-                                                if (col0 + r < n)
-                                                        P[(size_t)(col0 + r) * NP + row] = nv4[r];
-                                }
-                        }
+                        for (int v = 0; v < 8; ++v)
+                                update4(row, jt * TB + 16 * v + 4 * lg, acc[v >> 2][v & 3], false, jt == 0 && lg == 0 && v == 0, true);
+                return;
         }
+        const bool posecols_lane = (jt == 0 && wc == 0 && lg == 0);
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int v = 0; v < 4; ++v)
+                {
+                        const int row = rt * TB + wr + 16 * u + li;
+                        const int col0 = jt * TB + wc + 16 * v + 4 * lg;
+                        if (row >= n || col0 >= n || (diagq && v > u))
+                                continue;
+                        update4(row, col0, acc[u][v], diagq && v == u, posecols_lane && v == 0 /* this lane's four columns are 0 .. 3 */, mirror || diagq);
+                }
 }
 
 /// X <- X + V q with q = row n of G = (L^-1 Y)^T; one wave per state row.  grid (ceil(NP/4), B), 256 threads.  In replay

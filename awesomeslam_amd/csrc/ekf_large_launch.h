@@ -38,6 +38,7 @@ struct LargeKnobs
         int keep_l32 = 0;     // ASLAM_KEEP_L32=1 (tests/manual/large_residuals.py reads L back): large_chol_bf16 also stores the off-diagonal blocks of L in binary32
         int gs_tiles = 0;     // G, S by the row-pair kernel that reads all of P (large_build_GS); ASLAM_GS_TILES=1: from the lower block triangle of P (large_build_GS_tiles) -- bit-identical results, slower, kept for its test
         int border = 1;       // default chain (bf16-pipe Cholesky and TRSM): a tail of <= 3 rows past the last full 64-block is solved as a binary64 border by the X update (large_border, ekf_large.h); ASLAM_BORDER=0: every block row and column through the sweeps, the X update behind the syrk -- kept for its agreement test
+        int syrk_tail = 1;    // large_syrk_bf16x3<false>: a last tile row of <= 16 state rows is formed by the idle waves of the diagonal tiles (large_syrk_tail, ekf_large.h); ASLAM_SYRK_TAIL=0: that row as 128x128 tiles of its own -- bit-identical results, kept for its agreement test
         int syrk_running = 0; // diagnostic (ASLAM_SYRK_RUNNING=1): round 2's accumulation order in large_syrk_bf16x3 (profiles/r03_experiments.md)
 };
 
@@ -55,6 +56,7 @@ inline LargeKnobs large_knobs_from_env()
         flag("ASLAM_GS_TILES", k.gs_tiles);
         flag("ASLAM_SYRK_RUNNING", k.syrk_running);
         flag("ASLAM_BORDER", k.border);
+        flag("ASLAM_SYRK_TAIL", k.syrk_tail);
         return k;
 }
 
@@ -75,6 +77,7 @@ struct LargePlan
         bool border;                 // F32_RESIDENT with chol16 && trsm16: large_border() applies (the kernels decide per filter from its n), the X update runs in front of the syrk
         bool chol_f32out;            // large_chol_bf16 also stores the off-diagonal blocks of L in binary32 (the bf16 TRSM reads L through its planes only)
         bool gs_tiles, syrk_running; // large_build_GS_tiles for large_build_GS; large_syrk_bf16x3<true> for <false>
+        bool syrk_tail;              // binary32 chains, large_syrk_bf16x3<false>: large_syrk_tail() applies (the kernel decides per filter from its n)
         int launches;                // kernel launches per callback and stream group
         bool need_Lpl, need_Vw;      // buffers a context of `batch` filters owns besides P, G, S, Hc, Y, Linv
 };
@@ -87,6 +90,7 @@ inline LargePlan large_plan(bool f32, int NP, int batch, int filters, const Larg
         LargePlan p = {};
         p.gs_tiles = k.gs_tiles != 0;
         p.syrk_running = k.syrk_running != 0;
+        p.syrk_tail = f32 && !p.syrk_running && k.syrk_tail != 0;
         p.need_Lpl = f32 && k.bf16_pipe != 0;
         p.need_Vw = f32 && k.right_step && !resident(batch); // (a one-trajectory step on a context that is resident as a whole finds no Vw: F32_LEFT)
         if (!f32)
@@ -116,6 +120,7 @@ struct LargeHost
         int last_groups = 0;        // stream groups that received work (1 = the caller's stream alone; 0 = nothing launched yet)
         int last_launches = 0;      // kernel launches per callback and stream group of that launch (large_stats included)
         bool last_resident = false; // that launch ran LargeChain::F32_RESIDENT
+        bool last_syrk_tail = false; // the views of that launch carried the syrk's tail rule (LargeView::syrk_tail; aslam_get_syrk_tail)
         bool sighted = false;       // aslam_sighted_update_enable: the SIGHTED instantiations of the front end and of large_build_GS (which then also stands in for large_build_GS_tiles)
 };
 
@@ -319,6 +324,7 @@ hipError_t launch_large(LargeHost &h, const DevView &dv, const LargeView<T> &lv,
         LargeGroup<T> g[LARGE_GROUPS_MAX];
         h.last_launches = plan.launches + (sv.any() ? 1 : 0); // large_stats
         h.last_resident = plan.chain == LargeChain::F32_RESIDENT;
+        h.last_syrk_tail = plan.syrk_tail;
         h.last_groups = 0;
         for (int q = 0; q < NG; ++q)
         {
@@ -326,6 +332,7 @@ hipError_t launch_large(LargeHost &h, const DevView &dv, const LargeView<T> &lv,
                 const size_t b0 = (size_t)(first + o);
                 g[q] = {shifted_dev(dv, b0, MODE == MODE_REPLAY), shifted(lv, b0), skipped + b0, poses, dims, std::min(per, Bz - o), q == 0 ? st : h.aux[q - 1], shifted_stats(sv, b0, nsteps)};
                 g[q].v.border = plan.border; // (per launch: a one-trajectory step of a resident context runs another chain)
+                g[q].v.syrk_tail = plan.syrk_tail;
                 if (MODE == MODE_REPLAY && poses)
                         g[q].poses += b0 * (size_t)nsteps * 3;
                 if (MODE == MODE_REPLAY && dims)

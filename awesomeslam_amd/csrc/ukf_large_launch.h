@@ -59,6 +59,7 @@ hipError_t launch_ukf_large(LargeHost &h, const DevView &dv0, const LargeView<do
         const int fgroups = (gb + 7) / 8; // ukf_large_wabt and large_syrk deal filters to the 8 XCDs
         h.last_launches = plan.launches + (sv.any() ? 1 : 0);
         h.last_resident = false;
+        h.last_syrk_tail = false;
         h.last_groups = 1;
         for (int s = 0; s < nsteps; ++s)
         {

@@ -295,6 +295,10 @@ int aslam_kernel_info(aslam_ctx *ctx, char *name, int name_cap, int *grid, int *
  * 0, 0, 1): stream groups the batch was split into (1 = the caller's stream alone), whether the Cholesky of S ran as the one-launch
  * resident kernel, kernel launches per callback and group.  Lets a test assert that it exercised the launch shape it means to. */
 int aslam_get_launch_info(aslam_ctx *ctx, int *stream_groups, int *chol_resident, int *launches_per_callback);
+/* whether the LAST launch of this context handed large_syrk_bf16x3 the tail rule (a last tile row of <= 16 state rows formed on the idle waves
+ * of the diagonal tiles; the kernel applies it per filter from its dimension).  0 with ASLAM_SYRK_TAIL=0, ASLAM_SYRK_RUNNING=1, in binary64 and
+ * on the single-CU kernels. */
+int aslam_get_syrk_tail(aslam_ctx *ctx, int *on);
 
 #ifdef __cplusplus
 }

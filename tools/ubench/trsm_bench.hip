@@ -139,6 +139,7 @@ int main(int argc, char **argv)
         LargeView<float> lv = {};
         lv.NP = NP;
         lv.xrows = 1;
+        lv.syrk_tail = 1; // (as the library launches large_syrk_bf16x3<false>)
         lv.P = dP;
         lv.G = dG;
         lv.S = dS;
