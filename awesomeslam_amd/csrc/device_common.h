@@ -117,4 +117,19 @@ __device__ __forceinline__ d4 mfma_f64(double a, double b, d4 c)
 {
         return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
 }
+
+/// entry (i, j), j <= i, number q = i (i + 1) / 2 + j of the lower triangle: row-major, diagonal included
+struct TriIndex
+{
+        int i, j;
+};
+__device__ __forceinline__ TriIndex tri_index(int q)
+{
+        int i = (int)((sqrtf(8.0f * (float)q + 1.0f) - 1.0f) * 0.5f);
+        while ((i + 1) * (i + 2) / 2 <= q)
+                ++i;
+        while (i * (i + 1) / 2 > q)
+                --i;
+        return {i, q - i * (i + 1) / 2};
+}
 } // namespace aslam

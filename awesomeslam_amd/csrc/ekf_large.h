@@ -94,6 +94,95 @@ template <> struct Mfma<float>
         }
 };
 
+/// acc = A(rows of tile rt, 0 .. kend-1) B(rows of tile jt, 0 .. kend-1)^T: one 128x128 tile of a binary64 product on the 16x16x4 MFMA, the loop of
+/// large_syrk (A = B = V) and of ukf_large_wabt (A = D or DZ scaled by the sigma-point weights, ukf_large.h).  256 threads, 4 waves, wave w the
+/// 64x64 quadrant (w >> 1, w & 1) as 4x4 MFMA tiles in acc[u][v].  A and B are row-major with row stride ld; slabs of T128_KC columns go through
+/// LDS, the next one fetched into registers while the current one is multiplied.  Staging: 8 lanes cover one 128-byte row segment with 16-byte
+/// loads, so every wave-level load fetches 8 whole cache lines; 4 passes of 32 rows.  A tile may hang over the na active rows: such rows read row
+/// na - 1 instead (the caller never stores their products).  store_a(dst, t, k) puts a thread's pair t = A(row, k .. k+1) at dst in As: the one
+/// place where the callers' loops differ.  nu / nv: 16-row / 16-column subtiles of this wave's quadrant to multiply (wave-uniform; 0: the wave only
+/// stages).  kend is a multiple of T128_KC.
+constexpr int T128 = 128, T128_KC = 16, T128_LD = T128_KC + 2;
+template <typename StoreA>
+__device__ __forceinline__ void tile128_f64_product(double (&As)[T128][T128_LD], double (&Bs)[T128][T128_LD], const double *A, const double *B, int ld,
+                                                    int na, int rt, int jt, int kend, int nu, int nv, StoreA &&store_a, d4 (&acc)[4][4])
+{
+        typedef Mfma<double> MM;
+        typedef double d2 __attribute__((ext_vector_type(2)));
+        constexpr int KC = T128_KC;
+        const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lg = lane >> 4;
+        const int wr = (wave >> 1) * 64, wc = (wave & 1) * 64;
+        const int lrow = tid >> 3, lc0 = (tid & 7) * 2;
+        const double *Ap[4], *Bp[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+        {
+                Ap[q] = A + (size_t)min(rt * T128 + lrow + 32 * q, na - 1) * ld + lc0;
+                Bp[q] = B + (size_t)min(jt * T128 + lrow + 32 * q, na - 1) * ld + lc0;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int v = 0; v < 4; ++v)
+                        acc[u][v] = MM::zero();
+        d2 ta[4], tb[4];
+        auto fetch = [&](int kc) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                {
+                        ta[q] = *reinterpret_cast<const d2 *>(Ap[q] + kc);
+                        tb[q] = *reinterpret_cast<const d2 *>(Bp[q] + kc);
+                }
+        };
+        const bool full = (nu == 4 && nv == 4);
+        fetch(0);
+        for (int kc = 0; kc < kend; kc += KC)
+        {
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                {
+                        store_a(&As[lrow + 32 * q][lc0], ta[q], kc + lc0);
+                        *reinterpret_cast<d2 *>(&Bs[lrow + 32 * q][lc0]) = tb[q];
+                }
+                __syncthreads();
+                if (kc + KC < kend)
+                        fetch(kc + KC);
+                if (full)
+                {
+#pragma unroll
+                        for (int s = 0; s < KC / 4; ++s)
+                        {
+                                double av[4], bv[4];
+#pragma unroll
+                                for (int u = 0; u < 4; ++u)
+                                {
+                                        av[u] = As[wr + 16 * u + li][lg + 4 * s];
+                                        bv[u] = Bs[wc + 16 * u + li][lg + 4 * s];
+                                }
+#pragma unroll
+                                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                                        for (int v = 0; v < 4; ++v)
+                                                acc[u][v] = MM::mma(av[u], bv[v], acc[u][v]);
+                        }
+                }
+                else
+                {
+#pragma unroll
+                        for (int u = 0; u < 4; ++u)
+                                if (u < nu)
+#pragma unroll
+                                        for (int v = 0; v < 4; ++v)
+                                                if (v < nv)
+#pragma unroll
+                                                        for (int s = 0; s < KC / 4; ++s)
+                                                                acc[u][v] = MM::mma(As[wr + 16 * u + li][lg + 4 * s], Bs[wc + 16 * v + li][lg + 4 * s],
+                                                                                    acc[u][v]);
+                }
+                __syncthreads();
+        }
+}
+
 /// four floats -> their three bf16 planes, packed two to a register: x = h + m + l up to 2^-25 |x|.  Round to nearest at every level
 /// (v_cvt_pk_bf16_f32): with truncated pieces, which all carry the sign of x, the dropped terms of a split product have the sign of the product
 /// (large_syrk_bf16x3).
@@ -666,12 +755,8 @@ template <typename T> __global__ __launch_bounds__(256) void large_build_GS_tile
         const int n = d.n[b], NP = lv.NP;
         const int nb = large_blocks(n);
         const int tl = blockIdx.x;
-        int I = (int)((sqrtf(8.0f * (float)tl + 1.0f) - 1.0f) * 0.5f);
-        while ((I + 1) * (I + 2) / 2 <= tl)
-                ++I;
-        while (I * (I + 1) / 2 > tl)
-                --I;
-        const int J = tl - I * (I + 1) / 2;
+        const TriIndex blk = tri_index(tl);
+        const int I = blk.i, J = blk.j;
         if (I >= nb)
                 return;
         const double *P = lv.P + (size_t)b * NP * NP;
@@ -1049,19 +1134,17 @@ __global__ __launch_bounds__(256) void large_update_panel(DevView d, LargeView<T
 
 /// P -= V V^T (ekf.cpp:311 in the A-form, V = G after the panel solves) on 128x128 tiles: the kernel is bound by the
 /// operand traffic out of L2 (every row tile of V is read once per tile column), so the tile is as large as the
-/// accumulators allow: 4 waves, each a 64x64 quadrant = 4x4 MFMA 16x16 tiles (64 accumulator registers in fp32).  Lower
-/// tiles only, mirrored on store.  The next K slab is fetched into registers while the current one is multiplied.
-/// grid (8 * lower tiles * ceil(B/8)), 256 threads.
+/// accumulators allow: 4 waves, each a 64x64 quadrant = 4x4 MFMA 16x16 tiles (tile128_f64_product above, K = na).  Lower
+/// tiles only, mirrored on store.
+/// grid (8 * lower tiles * ceil(B/8)), 256 threads.  (A template only because this header is part of two translation units: T is double.)
 template <typename T>
 __global__ __launch_bounds__(256) void large_syrk(DevView d, LargeView<T> lv, int nfilters, const int *skipped)
 {
         static_assert(sizeof(T) == 8, "binary32 products go through large_syrk_bf16x3");
-        typedef Mfma<T> MM;
-        constexpr int TB = 128;
-        constexpr int KC = (sizeof(T) == 4) ? 32 : 16;
-        constexpr int LDS_LD = (sizeof(T) == 4) ? KC + 4 : KC + 2; // fp32: stride = 4 mod 64 banks -> conflict-free operand reads
-        __shared__ T As[TB][LDS_LD];
-        __shared__ T Bs[TB][LDS_LD];
+        typedef Mfma<double> MM;
+        constexpr int TB = T128;
+        __shared__ double As[TB][T128_LD];
+        __shared__ double Bs[TB][T128_LD];
         // XCD-aware mapping: consecutive workgroup ids go round-robin to the 8 XCDs, each with its own L2.  All lower tiles of
         // one filter are given ids that are equal mod 8, so the ~45 workgroups that share a filter's V run on one XCD and its
         // row tiles are fetched into that L2 once instead of into all eight.
@@ -1073,100 +1156,23 @@ __global__ __launch_bounds__(256) void large_syrk(DevView d, LargeView<T> lv, in
         const int n = d.n[b], NP = lv.NP;
         const int na = large_blocks(n, lv.xrows) * LB;
         const int tl = slot % nlow;
-        int rt = (int)((sqrtf(8.0f * (float)tl + 1.0f) - 1.0f) * 0.5f);
-        while ((rt + 1) * (rt + 2) / 2 <= tl)
-                ++rt;
-        while (rt * (rt + 1) / 2 > tl)
-                --rt;
-        const int jt = tl - rt * (rt + 1) / 2;
+        const TriIndex tile = tri_index(tl);
+        const int rt = tile.i, jt = tile.j;
         if (rt * TB >= na)
                 return;
-        const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lg = lane >> 4;
+        const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15;
         const int wr = (wave >> 1) * 64, wc = (wave & 1) * 64;
-        const T *G = lv.G + (size_t)b * NP * NP;
-        T *P = lv.P + (size_t)b * NP * NP;
-        // staging: 8 lanes cover one 128-byte row segment (KC elements) with 16-byte loads, so every wave-level load
-        // instruction fetches 8 whole cache lines; 4 passes of 32 rows
-        typedef T vec_t __attribute__((ext_vector_type(16 / sizeof(T))));
-        constexpr int VW = 16 / sizeof(T);
-        static_assert(KC / VW == 8, "8 lanes per staged row");
-        const int lrow = tid >> 3, lc0 = (tid & 7) * VW;
-        // the last tile row may hang over the allocation: such rows read row na-1 instead (their products are never stored)
-        const T *Ap[4], *Bp[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-        {
-                Ap[q] = G + (size_t)min(rt * TB + lrow + 32 * q, na - 1) * NP + lc0;
-                Bp[q] = G + (size_t)min(jt * TB + lrow + 32 * q, na - 1) * NP + lc0;
-        }
-        typename MM::acc_t acc[4][4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int v = 0; v < 4; ++v)
-                        acc[u][v] = MM::zero();
-        vec_t ta[4], tb[4];
-        auto fetch = [&](int kc) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                {
-                        ta[q] = *reinterpret_cast<const vec_t *>(Ap[q] + kc);
-                        tb[q] = *reinterpret_cast<const vec_t *>(Bp[q] + kc);
-                }
-        };
+        const double *G = lv.G + (size_t)b * NP * NP;
+        double *P = lv.P + (size_t)b * NP * NP;
         // 16-row / 16-column subtiles of this wave's quadrant that hold at least one of the n valid rows / columns (n = 3 mod 128
         // at full size: the last tile row is almost empty), and the upper quadrant of a diagonal tile is the mirror image of
         // its lower one: neither is multiplied
         const bool idle = (rt == jt && wc > wr);
         const int nu = idle ? 0 : __builtin_amdgcn_readfirstlane(max(0, min(4, (n - (rt * TB + wr) + 15) >> 4)));
         const int nv = idle ? 0 : __builtin_amdgcn_readfirstlane(max(0, min(4, (n - (jt * TB + wc) + 15) >> 4)));
-        const bool full = (nu == 4 && nv == 4);
-        fetch(0);
-        for (int kc = 0; kc < na; kc += KC)
-        {
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                {
-                        *reinterpret_cast<vec_t *>(&As[lrow + 32 * q][lc0]) = ta[q];
-                        *reinterpret_cast<vec_t *>(&Bs[lrow + 32 * q][lc0]) = tb[q];
-                }
-                __syncthreads();
-                if (kc + KC < na)
-                        fetch(kc + KC);
-                if (full)
-                {
-#pragma unroll
-                        for (int s = 0; s < KC / 4; ++s)
-                        {
-                                T av[4], bv[4];
-#pragma unroll
-                                for (int u = 0; u < 4; ++u)
-                                {
-                                        av[u] = As[wr + 16 * u + li][lg + 4 * s];
-                                        bv[u] = Bs[wc + 16 * u + li][lg + 4 * s];
-                                }
-#pragma unroll
-                                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                                        for (int v = 0; v < 4; ++v)
-                                                acc[u][v] = MM::mma(av[u], bv[v], acc[u][v]);
-                        }
-                }
-                else
-                {
-#pragma unroll
-                        for (int u = 0; u < 4; ++u)
-                                if (u < nu)
-#pragma unroll
-                                        for (int v = 0; v < 4; ++v)
-                                                if (v < nv)
-#pragma unroll
-                                                        for (int s = 0; s < KC / 4; ++s)
-                                                                acc[u][v] = MM::mma(As[wr + 16 * u + li][lg + 4 * s], Bs[wc + 16 * v + li][lg + 4 * s],
-                                                                                    acc[u][v]);
-                }
-                __syncthreads();
-        }
+        typedef double d2 __attribute__((ext_vector_type(2)));
+        MM::acc_t acc[4][4];
+        tile128_f64_product(As, Bs, G, G, NP, na, rt, jt, na, nu, nv, [](double *dst, const d2 &t, int) { *reinterpret_cast<d2 *>(dst) = t; }, acc);
         if (idle)
                 return;
 #pragma unroll
@@ -1184,10 +1190,7 @@ __global__ __launch_bounds__(256) void large_syrk(DevView d, LargeView<T> lv, in
                         }
                         if ((jt < rt || wc < wr) && col < n)
                         {
-                                // mirror into the upper triangle.  fp32: a lane's four registers are four consecutive rows of
-                                // the tile = 16 contiguous bytes of the mirrored row: one 16-byte read-modify-write
-                                const int row0 = rt * TB + wr + 16 * u + MM::row(lane, 0);
-                                (void)row0;
+                                // mirror into the upper triangle
 #pragma unroll
                                 for (int r = 0; r < 4; ++r)
                                 {
@@ -1264,7 +1267,7 @@ __global__ __launch_bounds__(256, 3) void large_syrk_bf16x3(DevView d, LargeView
         const int n = d.n[b], NP = lv.NP;
         const int na = large_blocks(n) * LB;
         const int tl = slot % nlow;
-        int rt = (int)((sqrtf(8.0f * (float)tl + 1.0f) - 1.0f) * 0.5f);
+        int rt = (int)((sqrtf(8.0f * (float)tl + 1.0f) - 1.0f) * 0.5f); // (tri_index() written out: this kernel's register allocation changes with the call)
         while ((rt + 1) * (rt + 2) / 2 <= tl)
                 ++rt;
         while (rt * (rt + 1) / 2 > tl)
@@ -1307,24 +1310,12 @@ __global__ __launch_bounds__(256, 3) void large_syrk_bf16x3(DevView d, LargeView
         // four floats -> their three bf16 planes: x = h + m + l up to 2^-25 |x|.  Round to nearest at every level (v_cvt_pk_bf16_f32): with
         // truncated pieces, which all carry the sign of x, the dropped terms a2 b3 + a3 b2 have the sign of the product, V V^T comes out
         // systematically small and the covariance error grew 1.5x faster than with binary32 MFMAs; rounded, it is 4x smaller than theirs.
-        typedef float f2 __attribute__((ext_vector_type(2)));
-        typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
         auto stash = [&](unsigned short (&S)[3][TB * LDB], int off, const f4 &x) {
-                unsigned pk[3][2];
-#pragma unroll
-                for (int e = 0; e < 2; ++e)
-                {
-                        const f2 v = {x[2 * e], x[2 * e + 1]};
-                        const bf2 h = __builtin_convertvector(v, bf2);
-                        const f2 r1 = v - __builtin_convertvector(h, f2);
-                        const bf2 m = __builtin_convertvector(r1, bf2);
-                        const f2 r2 = r1 - __builtin_convertvector(m, f2);
-                        const bf2 l = __builtin_convertvector(r2, bf2);
-                        pk[0][e] = __builtin_bit_cast(unsigned, h), pk[1][e] = __builtin_bit_cast(unsigned, m), pk[2][e] = __builtin_bit_cast(unsigned, l);
-                }
+                u2 pk[3];
+                split_bf16x3(x, pk[0], pk[1], pk[2]);
 #pragma unroll
                 for (int p = 0; p < 3; ++p)
-                        *reinterpret_cast<u2 *>(&S[p][off]) = (u2){pk[p][0], pk[p][1]};
+                        *reinterpret_cast<u2 *>(&S[p][off]) = pk[p];
         };
         const bool idle = (rt == jt && wc > wr); // upper quadrant of a diagonal tile: the mirror image of its lower one
         // A diagonal quadrant holds (I, J) and (J, I).  With binary32 MFMA products the two sums are bit-identical; here the six partial

@@ -306,12 +306,8 @@ __global__ __launch_bounds__(256) void large_right_step(DevView d, LargeView<flo
         int type, ri, cj = k;
         if (idx < nS)
         {
-                int ii = (int)((sqrtf(8.0f * (float)idx + 1.0f) - 1.0f) * 0.5f);
-                while ((ii + 1) * (ii + 2) / 2 <= idx)
-                        ++ii;
-                while (ii * (ii + 1) / 2 > idx)
-                        --ii;
-                type = 0, ri = k + 1 + ii, cj = k + 1 + (idx - ii * (ii + 1) / 2);
+                const TriIndex blk = tri_index(idx);
+                type = 0, ri = k + 1 + blk.i, cj = k + 1 + blk.j;
         }
         else if (idx < nS + nG)
                 type = 1, ri = (idx - nS) / m, cj = k + 1 + (idx - nS) % m;

@@ -169,12 +169,8 @@ __global__ __launch_bounds__(SMALL_WG) void ekf_small_kernel(DevView d, int64_t 
         for (int idx = tid; idx < LY::NTILES * 256; idx += SMALL_WG)
         {
                 const int tl = idx >> 8, e = idx & 255;
-                int ib = (int)((sqrtf(8.0f * (float)tl + 1.0f) - 1.0f) * 0.5f);
-                while ((ib + 1) * (ib + 2) / 2 <= tl)
-                        ++ib;
-                while (ib * (ib + 1) / 2 > tl)
-                        --ib;
-                const int jb = tl - ib * (ib + 1) / 2;
+                const TriIndex tile = tri_index(tl);
+                const int ib = tile.i, jb = tile.j;
                 Lt[tl * TSZ + (e >> 4) * TLD + (e & 15)] = Pg[(size_t)(16 * ib + (e >> 4)) * NP + 16 * jb + (e & 15)];
         }
         __syncthreads();

@@ -455,13 +455,8 @@ __device__ __forceinline__ void chol_panel_share(double *Lt, const double *Dinv,
 __device__ __forceinline__ void chol_trailing_tile(double *Lt, int kb, int q, int li, int lg)
 {
         {
-                int i = (int)((sqrtf(8.0f * (float)q + 1.0f) - 1.0f) * 0.5f);
-                while ((i + 1) * (i + 2) / 2 <= q)
-                        ++i;
-                while (i * (i + 1) / 2 > q)
-                        --i;
-                const int j = q - i * (i + 1) / 2;
-                const int ib = kb + 1 + i, jb = kb + 1 + j;
+                const TriIndex tile = tri_index(q);
+                const int ib = kb + 1 + tile.i, jb = kb + 1 + tile.j;
                 double *S = Lt + tile_index(ib, jb) * TSZ;
                 const double *Li = Lt + tile_index(ib, kb) * TSZ;
                 const double *Lj = Lt + tile_index(jb, kb) * TSZ;
@@ -998,12 +993,8 @@ __device__ __forceinline__ void cholesky_inverse_tiles(double *Lt, double *Dinv,
                         d4 o0 = {0.0, 0.0, 0.0, 0.0}, o1 = {0.0, 0.0, 0.0, 0.0};
                         if (tl < ntl)
                         {
-                                rb = (int)((sqrtf(8.0f * (float)tl + 1.0f) - 1.0f) * 0.5f);
-                                while ((rb + 1) * (rb + 2) / 2 <= tl)
-                                        ++rb;
-                                while (rb * (rb + 1) / 2 > tl)
-                                        --rb;
-                                jb = tl - rb * (rb + 1) / 2;
+                                const TriIndex tile = tri_index(tl);
+                                rb = tile.i, jb = tile.j;
                                 for (int k = rb; k < nt; k += 2)
                                 {
                                         const bool two = (k + 1 < nt);

@@ -352,9 +352,8 @@ __global__ __launch_bounds__(256) void ukf_large_points(DevView d, LargeView<dou
 ///   WABT_P   A = B = D:   P <- D W D^T + Q                                   lower 128x128 tiles, mirrored on store; P's padding is not touched
 ///   WABT_S   A = B = DZ:  S <- DZ W DZ^T + R WITHOUT the i = 0 term (= S+)   lower tiles; identity on rows / columns n .. na - 1
 ///   WABT_TC  A = D, B = DZ: G <- D W DZ^T (= Tc)                             all tiles; zero on the padding, rows n, n + 1 (z^T, the innovation) kept
-/// Tiling as large_syrk: 4 waves, each a 64x64 quadrant = 4x4 MFMA 16x16 tiles; operand slabs of 16 sigma points staged through LDS (A is scaled
-/// by the weights on the way in: weights(i) * diff first, as the reference does), the next slab fetched into registers while the current one is
-/// multiplied; a filter's tiles on one XCD.  grid (8 * tiles * ceil(B / 8)), 256 threads.
+/// The tile product is large_syrk's, tile128_f64_product (ekf_large.h), over slabs of 16 sigma points, with A scaled by the weights on the way into
+/// LDS; a filter's tiles on one XCD.  grid (8 * tiles * ceil(B / 8)), 256 threads.
 enum
 {
         WABT_P = 0,
@@ -369,9 +368,9 @@ __host__ __device__ __forceinline__ int ukf_wabt_tiles(int NP, int mode)
 __global__ __launch_bounds__(256) void ukf_large_wabt(DevView d, LargeView<double> lv, UkfLargeView uv, int mode, int nfilters, const int *skipped)
 {
         typedef Mfma<double> MM;
-        constexpr int TB = 128, KC = 16, LDS_LD = KC + 2;
-        __shared__ double As[TB][LDS_LD];
-        __shared__ double Bs[TB][LDS_LD];
+        constexpr int TB = T128, KC = T128_KC;
+        __shared__ double As[TB][T128_LD];
+        __shared__ double Bs[TB][T128_LD];
         const int ntile = (lv.NP + TB - 1) / TB, ntl = ukf_wabt_tiles(lv.NP, mode);
         const int slot = blockIdx.x >> 3;
         const int b = (slot / ntl) * 8 + (blockIdx.x & 7);
@@ -385,107 +384,35 @@ __global__ __launch_bounds__(256) void ukf_large_wabt(DevView d, LargeView<doubl
                 rt = tl / ntile, jt = tl - rt * ntile;
         else
         {
-                rt = (int)((sqrtf(8.0f * (float)tl + 1.0f) - 1.0f) * 0.5f);
-                while ((rt + 1) * (rt + 2) / 2 <= tl)
-                        ++rt;
-                while (rt * (rt + 1) / 2 > tl)
-                        --rt;
-                jt = tl - rt * (rt + 1) / 2;
+                const TriIndex tile = tri_index(tl);
+                rt = tile.i, jt = tile.j;
         }
         if (rt * TB >= na || jt * TB >= na)
                 return;
-        const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lg = lane >> 4;
+        const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15;
         const int wr = (wave >> 1) * 64, wc = (wave & 1) * 64;
         const double *A = (mode == WABT_S ? uv.DZ : uv.D) + (size_t)b * NP * MP;
         const double *Bm = (mode == WABT_P ? uv.D : uv.DZ) + (size_t)b * NP * MP;
         const UkfWeights W = ukf_weights(n);
         const double w_first = (mode == WABT_S) ? 0.0 : W.w_0; // S+ leaves the centre point out
         const int kend = (W.m + KC - 1) / KC * KC;            // <= MP
-        // staging: 8 lanes cover one 128-byte row segment (KC doubles) with 16-byte loads; 4 passes of 32 rows.  Tile rows beyond na read row
-        // na - 1 instead (their products are never stored)
-        typedef double d2 __attribute__((ext_vector_type(2)));
-        const int lrow = tid >> 3, lc0 = (tid & 7) * 2;
-        const double *Ap[4], *Bp[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-        {
-                Ap[q] = A + (size_t)min(rt * TB + lrow + 32 * q, na - 1) * MP + lc0;
-                Bp[q] = Bm + (size_t)min(jt * TB + lrow + 32 * q, na - 1) * MP + lc0;
-        }
-        MM::acc_t acc[4][4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int v = 0; v < 4; ++v)
-                        acc[u][v] = MM::zero();
-        d2 ta[4], tb[4];
-        auto fetch = [&](int kc) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                {
-                        ta[q] = *reinterpret_cast<const d2 *>(Ap[q] + kc);
-                        tb[q] = *reinterpret_cast<const d2 *>(Bp[q] + kc);
-                }
-        };
         // 16-row / 16-column subtiles of this wave's quadrant that hold at least one of the n valid rows / columns; the upper quadrant of a diagonal
         // tile of a symmetric product is the mirror image of its lower one: neither is multiplied
         const bool sym = mode != WABT_TC;
         const bool idle = sym && rt == jt && wc > wr;
         const int nu = idle ? 0 : __builtin_amdgcn_readfirstlane(max(0, min(4, (n - (rt * TB + wr) + 15) >> 4)));
         const int nv = idle ? 0 : __builtin_amdgcn_readfirstlane(max(0, min(4, (n - (jt * TB + wc) + 15) >> 4)));
-        const bool full = (nu == 4 && nv == 4);
-        fetch(0);
-        for (int kc = 0; kc < kend; kc += KC)
-        {
-                {
-                        const int k0 = kc + lc0;
-                        const double w0 = (k0 == 0) ? w_first : (k0 < W.m) ? W.w_i : 0.0;
-                        const double w1 = (k0 + 1 < W.m) ? W.w_i : 0.0;
-#pragma unroll
-                        for (int q = 0; q < 4; ++q)
-                        {
-                                As[lrow + 32 * q][lc0] = w0 * ta[q][0];
-                                As[lrow + 32 * q][lc0 + 1] = w1 * ta[q][1];
-                                *reinterpret_cast<d2 *>(&Bs[lrow + 32 * q][lc0]) = tb[q];
-                        }
-                }
-                __syncthreads();
-                if (kc + KC < kend)
-                        fetch(kc + KC);
-                if (full)
-                {
-#pragma unroll
-                        for (int s = 0; s < KC / 4; ++s)
-                        {
-                                double av[4], bv[4];
-#pragma unroll
-                                for (int u = 0; u < 4; ++u)
-                                {
-                                        av[u] = As[wr + 16 * u + li][lg + 4 * s];
-                                        bv[u] = Bs[wc + 16 * u + li][lg + 4 * s];
-                                }
-#pragma unroll
-                                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                                        for (int v = 0; v < 4; ++v)
-                                                acc[u][v] = MM::mma(av[u], bv[v], acc[u][v]);
-                        }
-                }
-                else
-                {
-#pragma unroll
-                        for (int u = 0; u < 4; ++u)
-                                if (u < nu)
-#pragma unroll
-                                        for (int v = 0; v < 4; ++v)
-                                                if (v < nv)
-#pragma unroll
-                                                        for (int s = 0; s < KC / 4; ++s)
-                                                                acc[u][v] = MM::mma(As[wr + 16 * u + li][lg + 4 * s], Bs[wc + 16 * v + li][lg + 4 * s],
-                                                                                    acc[u][v]);
-                }
-                __syncthreads();
-        }
+        typedef double d2 __attribute__((ext_vector_type(2)));
+        MM::acc_t acc[4][4];
+        // A goes into LDS scaled by the weights of its two sigma points k0, k0 + 1: weights(i) * diff first, as the reference does
+        tile128_f64_product(As, Bs, A, Bm, MP, na, rt, jt, kend, nu, nv,
+                            [&](double *dst, const d2 &t, int k0) {
+                                    const double w0 = (k0 == 0) ? w_first : (k0 < W.m) ? W.w_i : 0.0;
+                                    const double w1 = (k0 + 1 < W.m) ? W.w_i : 0.0;
+                                    dst[0] = w0 * t[0];
+                                    dst[1] = w1 * t[1];
+                            },
+                            acc);
         if (idle)
                 return;
         double *C = (mode == WABT_P ? lv.P : mode == WABT_S ? lv.S : lv.G) + (size_t)b * NP * NP;

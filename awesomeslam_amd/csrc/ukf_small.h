@@ -106,12 +106,8 @@ __device__ __forceinline__ void gemm_wabt(const double *A, const double *B, int 
                 {
                         if (LOWER)
                         {
-                                ib = (int)((sqrtf(8.0f * (float)tl + 1.0f) - 1.0f) * 0.5f);
-                                while ((ib + 1) * (ib + 2) / 2 <= tl)
-                                        ++ib;
-                                while (ib * (ib + 1) / 2 > tl)
-                                        --ib;
-                                jb = tl - ib * (ib + 1) / 2;
+                                const TriIndex tile = tri_index(tl);
+                                ib = tile.i, jb = tile.j;
                         }
                         else
                         {
@@ -441,12 +437,8 @@ __global__ __launch_bounds__(SMALL_WG) void ukf_small_kernel(DevView d, UkfView 
                         const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
                         for (int tl = wave; tl < ntl; tl += SMALL_WG / 64)
                         {
-                                int ib = (int)((sqrtf(8.0f * (float)tl + 1.0f) - 1.0f) * 0.5f);
-                                while ((ib + 1) * (ib + 2) / 2 <= tl)
-                                        ++ib;
-                                while (ib * (ib + 1) / 2 > tl)
-                                        --ib;
-                                const int jb = tl - ib * (ib + 1) / 2;
+                                const TriIndex tile = tri_index(tl);
+                                const int ib = tile.i, jb = tile.j;
 #pragma unroll
                                 for (int q = 0; q < 4; ++q)
                                 {
