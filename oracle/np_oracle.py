@@ -144,6 +144,7 @@ class NpFilter:
         self.init_z = True
         self.sensor = []  # list of [range f32, bearing f32]
         self.wait = []  # list of [range f32, bearing f32, count]
+        self.sm_den = float("nan")  # (UKF) recorded by every slam(): see _slam_ukf
         N = self.N
         self.X = np.zeros(N)
         self.Z = np.zeros(N)
@@ -331,7 +332,11 @@ class NpFilter:
             self._wrap_even(col)
         S = (DZ * W) @ DZ.T + self.R
         Tc = (D * W) @ DZ.T
-        K = Tc @ np.linalg.inv(S)
+        Sinv = np.linalg.inv(S)
+        K = Tc @ Sinv
+        # conditioning of this step, for the tests (no part of the filter): S = S+ - z z^T with z = sqrt(-w0) dz_0 and S+ the sum over i >= 1,
+        # and 1 / (1 + z^T S^-1 z) = 1 - z^T S+^-1 z is the denominator of a Sherman-Morrison form of S^-1; near 0, S is almost singular
+        self.sm_den = float(1.0 / (1.0 - W[0] * (DZ[:, 0] @ Sinv @ DZ[:, 0])))
         Zdiff = self.Z - Zpred
         self._wrap_even(Zdiff)
         self.X = self.X + K @ Zdiff
