@@ -31,6 +31,7 @@ CORE_SYMBOLS = (
     "aslam_remove_landmarks", "aslam_select_beyond",
     "aslam_get_sightings", "aslam_select_stale",
     "aslam_sighted_update_enable", "aslam_get_sighted", "aslam_ekf_step_sighted", "aslam_ekf_step_batch_sighted",
+    "aslam_merge_landmarks", "aslam_select_duplicates",
 )
 NODE_SYMBOLS = (
     "aslam_node_create", "aslam_node_create_at", "aslam_node_destroy", "aslam_node_error", "aslam_node_sensor", "aslam_node_odom",
@@ -38,6 +39,7 @@ NODE_SYMBOLS = (
     "aslam_host_narrow_odom", "aslam_node_enable_innovation", "aslam_node_innovation",
     "aslam_node_set_params", "aslam_node_get_params", "aslam_node_remove_landmarks",
     "aslam_node_get_sightings", "aslam_node_remove_stale", "aslam_node_set_sighted_only",
+    "aslam_node_merge_landmarks", "aslam_node_merge_duplicates",
 )
 TRACE_FILE_SYMBOLS = (
     "aslam_trace_file_open", "aslam_trace_file_close", "aslam_trace_file_error", "aslam_trace_file_dims",
@@ -190,6 +192,8 @@ def core_lib():
         L.aslam_select_beyond.argtypes = [vp, pd, vp, ci, vp]
         L.aslam_get_sightings.argtypes = [vp, ci, pu, pu, ci, pi, pu]
         L.aslam_select_stale.argtypes = [vp, pu, vp, ci, vp]
+        L.aslam_merge_landmarks.argtypes = [vp, vp, ci, ci, cd, vp, vp]
+        L.aslam_select_duplicates.argtypes = [vp, pd, pd, vp, ci, vp]
         pb = ctypes.POINTER(ctypes.c_uint8)
         L.aslam_sighted_update_enable.argtypes = [vp, ci]
         L.aslam_get_sighted.argtypes = [vp, ci, pb, ci, pi]
@@ -238,6 +242,8 @@ def node_lib():
         L.aslam_node_get_sightings.argtypes = [vp, pu, pu, ci, pu]
         L.aslam_node_remove_stale.argtypes = [vp, ctypes.c_uint32]
         L.aslam_node_set_sighted_only.argtypes = [vp, ci]
+        L.aslam_node_merge_landmarks.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ci, ctypes.c_double]
+        L.aslam_node_merge_duplicates.argtypes = [vp, ctypes.c_double, ctypes.c_double, ctypes.c_double]
         # include/aslam_trace_file.h
         L.aslam_trace_file_error.restype = ctypes.c_char_p
         L.aslam_trace_file_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
@@ -728,6 +734,61 @@ class Core:
             done += k
         return np.array(dims, np.int64).reshape(len(dims), self.batch)
 
+    # ---- merging duplicate landmarks (aslam_merge_landmarks / aslam_select_duplicates)
+    def merge_landmarks(self, into_or_pairs, traj=None, noise_var=0.0, stream=None):
+        """Fuse duplicate landmarks: entry (b, j) = i of a [batch, L] int32 array (or int32 device tensor) merges landmark j of filter b into
+        landmark i < j, -1 keeps j; with `traj`, a list of (i, j) pairs of that one filter.  The constraint "both are the same point" (with
+        `noise_var` on its diagonal) is applied to X and P, then j is removed as remove_landmarks removes it.  Returns the pairs fused and
+        removed per filter [batch].  A refused call (AslamError: i >= j, a chain, an index out of range) leaves the context unchanged."""
+        if traj is not None:
+            L = max(self.landmark_capacity(), 1)
+            if not 0 <= int(traj) < self.batch:
+                raise ValueError("traj out of range")
+            into = np.full((self.batch, L), -1, np.int32)
+            for i, j in np.asarray(into_or_pairs, np.int64).reshape(-1, 2):
+                if not 0 <= j < L:
+                    raise ValueError(f"landmark index out of range (capacity {L})")
+                into[int(traj), j] = i
+            into_or_pairs = into
+        if hasattr(into_or_pairs, "data_ptr"):
+            m = into_or_pairs
+            if m.dim() != 2 or m.shape[0] != self.batch or m.element_size() != 4 or m.is_floating_point() or not m.is_contiguous():
+                raise ValueError("a device array is a contiguous [batch, L] int32 tensor")
+            return self.merge_landmarks_ptr(m.data_ptr(), m.shape[1], True, noise_var, stream)
+        m = np.ascontiguousarray(into_or_pairs, np.int32)
+        if m.ndim != 2 or m.shape[0] != self.batch:
+            raise ValueError("`into` is [batch, L]")
+        return self.merge_landmarks_ptr(m.ctypes.data, m.shape[1], False, noise_var, stream)
+
+    def merge_landmarks_ptr(self, into_ptr, ld, is_device, noise_var=0.0, stream=None):
+        """aslam_merge_landmarks as it is: a raw pointer (int) to a [batch][ld] i32 array.  Returns merged_out [batch]."""
+        out = np.zeros(self.batch, np.int32)
+        _chk(core_lib().aslam_merge_landmarks(self._h, into_ptr, int(ld), 1 if is_device else 0, float(noise_var), out.ctypes.data, stream))
+        return out
+
+    def select_duplicates(self, gate, max_dist, into_ptr, ld, stream=None):
+        """Device array [batch][ld] i32 at `into_ptr` <- for every landmark j the i < j to merge it into (the candidate of smallest Mahalanobis
+        distance below `gate` within `max_dist`; scalars, or one value per filter), -1 elsewhere (aslam_select_duplicates).  Asynchronous."""
+        g = np.ascontiguousarray(np.broadcast_to(np.asarray(gate, np.float64), (self.batch,)))
+        d = np.ascontiguousarray(np.broadcast_to(np.asarray(max_dist, np.float64), (self.batch,)))
+        _chk(core_lib().aslam_select_duplicates(self._h, _ptr(g, ctypes.c_double), _ptr(d, ctypes.c_double), into_ptr, int(ld), stream))
+
+    def merge_duplicates(self, gate, max_dist, noise_var=0.0, max_passes=4, stream=None):
+        """select_duplicates + merge_landmarks with a device array that never leaves the GPU, until a pass merges nothing or `max_passes` ran
+        (the selector leaves a landmark whose partner is itself merged for the next pass).  Returns the landmarks merged per filter [batch]."""
+        import torch
+
+        ld = (max(self.landmark_capacity(), 1) + 15) // 16 * 16
+        into = torch.empty((self.batch, ld), dtype=torch.int32, device="cuda")
+        total = np.zeros(self.batch, np.int64)
+        for _ in range(int(max_passes)):
+            self.select_duplicates(gate, max_dist, into.data_ptr(), ld, stream)
+            k = self.merge_landmarks(into, noise_var=noise_var, stream=stream)  # (synchronises)
+            total += k
+            if not k.any():
+                break
+        return total
+
     def layout(self):
         npad, nbytes = ctypes.c_int(), ctypes.c_int64()
         _chk(core_lib().aslam_get_layout(self._h, ctypes.byref(npad), ctypes.byref(nbytes)))
@@ -852,6 +913,21 @@ class Node:
     def remove_stale(self, max_age):
         """FilterNode::removeStale: forget the landmarks last sighted more than max_age callbacks ago.  Returns how many went."""
         k = node_lib().aslam_node_remove_stale(self._h, int(max_age))
+        if k < 0:
+            raise AslamError(node_lib().aslam_node_error().decode())
+        return k
+
+    def merge_landmarks(self, pairs, noise_var=0.0):
+        """FilterNode::mergeLandmarks: fuse each (i, j), i < j, and drop j; the mirror's own records fuse by the core's rule.  Returns how many."""
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        k = node_lib().aslam_node_merge_landmarks(self._h, _ptr(pr, ctypes.c_int32), len(pr), float(noise_var))
+        if k < 0:
+            raise AslamError(node_lib().aslam_node_error().decode())
+        return k
+
+    def merge_duplicates(self, gate, max_dist, noise_var=0.0):
+        """FilterNode::mergeDuplicates: aslam_select_duplicates + mergeLandmarks, passes until one merges nothing (4 at the most)."""
+        k = node_lib().aslam_node_merge_duplicates(self._h, float(gate), float(max_dist), float(noise_var))
         if k < 0:
             raise AslamError(node_lib().aslam_node_error().decode())
         return k

@@ -25,6 +25,7 @@
 #include "scan_front.h"
 #include "snapshot.h"
 #include "prune.h"
+#include "merge.h"
 #if ASLAM_HAVE_UKF
 #include "ukf_small.h"
 #include "ukf_large.h"
@@ -1413,24 +1414,25 @@ int aslam_select_stale(aslam_ctx *c, const uint32_t *max_age, uint8_t *mask_dev,
         return ASLAM_OK;
 }
 
-int aslam_remove_landmarks(aslam_ctx *c, const uint8_t *mask, int ld, int is_device, void *stream)
+namespace
 {
-        if (const char *e = bad_mask(c, mask, ld, is_device))
-                return fail(ASLAM_ERR_ARG, std::string("aslam_remove_landmarks: ") + e);
-        int rc = sync_ctx(c);
-        if (rc != ASLAM_OK)
-                return rc;
+/// aslam_remove_landmarks behind its argument checks and the synchronisation of the context.  The staging begins `base` bytes into the
+/// context's block: what a caller keeps in front of it (aslam_merge_landmarks: its plan, with the mask at mask_off when `mask` is null)
+/// survives.  meta_out (may be null) receives what prune_map reported: n and n_new of every filter.
+int remove_landmarks_at(aslam_ctx *c, const uint8_t *mask, size_t mask_off, int ld, int is_device, hipStream_t st, size_t base,
+                        std::vector<PruneMeta> *meta_out)
+{
+        int rc;
         const int B = c->cfg.batch;
         const size_t NP = (size_t)c->NP;
-        hipStream_t st = static_cast<hipStream_t>(stream);
         // staging: descriptors | what prune_map reports | the survivor lists | a host mask's copy | the records
-        const size_t o_meta = (size_t)snap_pad64((int64_t)sizeof(SnapDesc) * B);
+        const size_t o_meta = base + (size_t)snap_pad64((int64_t)sizeof(SnapDesc) * B);
         const size_t o_src = o_meta + (size_t)snap_pad64((int64_t)sizeof(PruneMeta) * B);
         const size_t o_mask = o_src + (size_t)snap_pad64((int64_t)(sizeof(int) * NP) * B);
         const size_t o_blob = o_mask + (is_device ? 0 : (size_t)snap_pad64((int64_t)B * ld));
-        if ((rc = snap_reserve(c, o_blob)) != ASLAM_OK)
+        if ((rc = base ? snap_reserve_keep(c, o_blob, base) : snap_reserve(c, o_blob)) != ASLAM_OK)
                 return rc;
-        const uint8_t *mdev = mask;
+        const uint8_t *mdev = mask ? mask : reinterpret_cast<const uint8_t *>(c->snap_dev + mask_off);
         if (!is_device)
         {
                 HIP_TRY(hipMemcpy(c->snap_dev + o_mask, mask, (size_t)B * ld, hipMemcpyHostToDevice));
@@ -1445,6 +1447,8 @@ int aslam_remove_landmarks(aslam_ctx *c, const uint8_t *mask, int ld, int is_dev
         std::vector<PruneMeta> meta((size_t)B);
         HIP_TRY(hipMemcpyAsync(meta.data(), c->snap_dev + o_meta, sizeof(PruneMeta) * B, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
+        if (meta_out)
+                *meta_out = meta;
         std::vector<SnapDesc> desc;
         int n_max = 3;
         for (int b = 0; b < B; ++b)
@@ -1471,10 +1475,9 @@ int aslam_remove_landmarks(aslam_ctx *c, const uint8_t *mask, int ld, int is_dev
         const int64_t total = off;
         if ((rc = snap_reserve_keep(c, o_blob + (size_t)total, o_blob)) != ASLAM_OK)
                 return rc;
-        HIP_TRY(hipMemcpy(c->snap_dev, desc.data(), sizeof(SnapDesc) * count, hipMemcpyHostToDevice));
-        if (!is_device)
-                mdev = nullptr; // (the block may have moved; the mask is not read again)
-        const SnapDesc *ddev = reinterpret_cast<const SnapDesc *>(c->snap_dev);
+        HIP_TRY(hipMemcpy(c->snap_dev + base, desc.data(), sizeof(SnapDesc) * count, hipMemcpyHostToDevice));
+        mdev = nullptr; // (the block may have moved; the mask is not read again)
+        const SnapDesc *ddev = reinterpret_cast<const SnapDesc *>(c->snap_dev + base);
         char *blob = c->snap_dev + o_blob;
         const SnapCtx sc = snap_ctx(c);
         hipLaunchKernelGGL(prune_pack, snap_grid((int64_t)n_max * (n_max + 1) / 2, count), dim3(SNAP_WG), 0, st, sc, ddev, count, (uint32_t)c->cfg.filter,
@@ -1489,6 +1492,187 @@ int aslam_remove_landmarks(aslam_ctx *c, const uint8_t *mask, int ld, int is_dev
         // the mask of the last callback indexes landmarks that have moved: zero in every filter that lost one
         for (const SnapDesc &q : desc)
                 HIP_TRY(hipMemsetAsync(c->dv.sighted + (size_t)q.slot * (c->NP / 2), 0, (size_t)c->NP / 2, st));
+        return ASLAM_OK;
+}
+} // namespace
+
+int aslam_remove_landmarks(aslam_ctx *c, const uint8_t *mask, int ld, int is_device, void *stream)
+{
+        if (const char *e = bad_mask(c, mask, ld, is_device))
+                return fail(ASLAM_ERR_ARG, std::string("aslam_remove_landmarks: ") + e);
+        int rc = sync_ctx(c);
+        if (rc != ASLAM_OK)
+                return rc;
+        return remove_landmarks_at(c, mask, 0, ld, is_device, static_cast<hipStream_t>(stream), 0, nullptr);
+}
+
+/* ---- merging duplicate landmarks (merge.h) ----------------------------------------------------------------------------- */
+namespace
+{
+/// aslam_merge_landmarks.  With `ms` (aslam_debug_merge_rate): plan and the first round's merge_gain as in the call, then that round's
+/// merge_downdate 3 + reps times, each between two device events, and nothing else -- the filters are left mid-merge, for timing alone.
+int merge_landmarks_run(aslam_ctx *c, const int32_t *into, int ld, int is_device, double noise_var, int32_t *merged_out, void *stream, int reps, float *ms)
+{
+        if (const char *e = bad_mask(c, into, ld, is_device))
+        {
+                std::string m(e);
+                for (size_t at; (at = m.find("mask")) != std::string::npos;)
+                        m.replace(at, 4, "into");
+                return fail(ASLAM_ERR_ARG, "aslam_merge_landmarks: " + m);
+        }
+        if (!std::isfinite(noise_var) || noise_var < 0.0)
+                return fail(ASLAM_ERR_ARG, "aslam_merge_landmarks: noise_var must be finite and not negative");
+        int rc = sync_ctx(c);
+        if (rc != ASLAM_OK)
+                return rc;
+        const int B = c->cfg.batch, NP = c->NP;
+        const int ldm = (ld + 15) & ~15;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        // staging in front of the remove path's: the plan's report | pairs (i) | pairs (j) | removal mask | stop flags | V | a host array's copy
+        const size_t o_pi = (size_t)snap_pad64((int64_t)sizeof(MergeMeta) * B);
+        const size_t o_pj = o_pi + (size_t)snap_pad64(4 * (int64_t)B * ldm);
+        const size_t o_mask = o_pj + (size_t)snap_pad64(4 * (int64_t)B * ldm);
+        const size_t o_stop = o_mask + (size_t)snap_pad64((int64_t)B * ldm);
+        const size_t o_V = o_stop + (size_t)snap_pad64(4 * (int64_t)B);
+        const size_t o_into = o_V + (size_t)snap_pad64(8 * (int64_t)B * MERGE_K * NP);
+        const size_t base = o_into + (is_device ? 0 : (size_t)snap_pad64(4 * (int64_t)B * ld));
+        // (with the remove path's descriptors, report and survivor lists behind it: the block does not move while the rounds are in flight)
+        const size_t behind = (size_t)(snap_pad64((int64_t)sizeof(SnapDesc) * B) + snap_pad64((int64_t)sizeof(PruneMeta) * B) + snap_pad64(4 * (int64_t)NP * B));
+        if ((rc = snap_reserve(c, base + behind)) != ASLAM_OK)
+                return rc;
+        const int32_t *idev = into;
+        if (!is_device)
+        {
+                HIP_TRY(hipMemcpy(c->snap_dev + o_into, into, sizeof(int32_t) * B * ld, hipMemcpyHostToDevice));
+                idev = reinterpret_cast<const int32_t *>(c->snap_dev + o_into);
+        }
+        char *sd = c->snap_dev;
+        MergeMeta *meta_dev = reinterpret_cast<MergeMeta *>(sd);
+        int32_t *pi = reinterpret_cast<int32_t *>(sd + o_pi), *pj = reinterpret_cast<int32_t *>(sd + o_pj), *stop = reinterpret_cast<int32_t *>(sd + o_stop);
+        uint8_t *mask = reinterpret_cast<uint8_t *>(sd + o_mask);
+        double *V = reinterpret_cast<double *>(sd + o_V);
+        c->last_stream = st;
+        hipLaunchKernelGGL(merge_plan, dim3((unsigned)B), dim3(PRUNE_WAVE), 0, st, idev, ld, (const int *)c->dv.n, NP, ldm, pi, pj, mask, stop, meta_dev);
+        HIP_TRY(hipGetLastError());
+        // the plan's report, checked before any filter is written: a refused call leaves the context as it was
+        std::vector<MergeMeta> meta((size_t)B);
+        HIP_TRY(hipMemcpyAsync(meta.data(), meta_dev, sizeof(MergeMeta) * B, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        int max_count = 0, max_L = 0;
+        for (int b = 0; b < B; ++b)
+        {
+                const MergeMeta &m = meta[b];
+                if (m.bad_j >= 0)
+                        return fail(ASLAM_ERR_ARG, "aslam_merge_landmarks: filter " + std::to_string(b) + ", landmark " + std::to_string(m.bad_j) + ": into = " +
+                                                       std::to_string(m.bad_i) + " (needs 0 <= into < landmark, and a root that is not merged away itself)");
+                max_count = std::max(max_count, m.count);
+                if (m.count > 0)
+                        max_L = std::max(max_L, m.L);
+        }
+        if (merged_out)
+                std::fill(merged_out, merged_out + B, 0);
+        if (max_count == 0)
+                return ASLAM_OK;
+        double *P = c->large ? c->largeP : c->dv.P;
+        const int T = (3 + 2 * max_L + MERGE_TILE - 1) / MERGE_TILE;
+        for (int r = 0; r * MERGE_ROUND < max_count; ++r)
+        {
+                hipLaunchKernelGGL(merge_gain, dim3((unsigned)B), dim3(MERGE_WG), 0, st, c->dv.X, (const double *)P, (const int *)c->dv.n, NP, ldm,
+                                   (const int32_t *)pi, (const int32_t *)pj, (const MergeMeta *)meta_dev, r, noise_var, V, mask, stop);
+                HIP_TRY(hipGetLastError());
+                if (ms)
+                {
+                        hipEvent_t e0, e1;
+                        HIP_TRY(hipEventCreate(&e0));
+                        HIP_TRY(hipEventCreate(&e1));
+                        for (int k = -3; k < reps; ++k)
+                        {
+                                HIP_TRY(hipEventRecord(e0, st));
+                                hipLaunchKernelGGL(merge_downdate, dim3((unsigned)(T * (T + 1) / 2), (unsigned)B), dim3(MERGE_WG), 0, st, P, (const int *)c->dv.n,
+                                                   NP, (const MergeMeta *)meta_dev, r, (const double *)V, (const int32_t *)stop);
+                                HIP_TRY(hipEventRecord(e1, st));
+                                HIP_TRY(hipEventSynchronize(e1));
+                                float t = 0.f;
+                                HIP_TRY(hipEventElapsedTime(&t, e0, e1));
+                                if (k >= 0)
+                                        ms[k] = t;
+                        }
+                        (void)hipEventDestroy(e0);
+                        (void)hipEventDestroy(e1);
+                        return ASLAM_OK;
+                }
+                hipLaunchKernelGGL(merge_downdate, dim3((unsigned)(T * (T + 1) / 2), (unsigned)B), dim3(MERGE_WG), 0, st, P, (const int *)c->dv.n, NP,
+                                   (const MergeMeta *)meta_dev, r, (const double *)V, (const int32_t *)stop);
+                HIP_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(merge_sightings, dim3((unsigned)B), dim3(PRUNE_WAVE), 0, st, (const uint32_t *)c->dv.clock, c->dv.lm_seen, c->dv.lm_hits, NP, ldm,
+                           (const int32_t *)pi, (const int32_t *)pj, (const MergeMeta *)meta_dev, (const uint8_t *)mask);
+        HIP_TRY(hipGetLastError());
+        // the merged-away landmarks leave through the remove path itself, with the mask the plan wrote (less what a failed pivot took out)
+        std::vector<PruneMeta> pm;
+        if ((rc = remove_landmarks_at(c, nullptr, o_mask, ldm, 1, st, base, &pm)) != ASLAM_OK)
+                return rc;
+        if (merged_out)
+                for (int b = 0; b < B; ++b)
+                        merged_out[b] = (pm[b].n - pm[b].n_new) / 2;
+        return ASLAM_OK;
+}
+} // namespace
+
+int aslam_merge_landmarks(aslam_ctx *c, const int32_t *into, int ld, int is_device, double noise_var, int32_t *merged_out, void *stream)
+{
+        return merge_landmarks_run(c, into, ld, is_device, noise_var, merged_out, stream, 0, nullptr);
+}
+
+/* diagnostic (tools/merge_rate.py): merge_downdate alone.  The plan and the first round's gain of aslam_merge_landmarks(into_dev), then that
+   round's downdate launch `reps` times after three untimed ones, each between two device events on the default stream; ms [reps].  Every
+   repetition subtracts again: the filters are left in no state to run on -- restore them. */
+int aslam_debug_merge_rate(aslam_ctx *c, const int32_t *into_dev, int ld, double noise_var, int reps, float *ms)
+{
+        if (!ms || reps < 1)
+                return fail(ASLAM_ERR_ARG, "null argument");
+        return merge_landmarks_run(c, into_dev, ld, 1, noise_var, nullptr, nullptr, reps, ms);
+}
+
+int aslam_select_duplicates(aslam_ctx *c, const double *gate, const double *max_dist, int32_t *into_dev, int ld, void *stream)
+{
+        if (const char *e = bad_mask(c, into_dev, ld, 1))
+        {
+                std::string m(e);
+                for (size_t at; (at = m.find("mask")) != std::string::npos;)
+                        m.replace(at, 4, "into");
+                return fail(ASLAM_ERR_ARG, "aslam_select_duplicates: " + m);
+        }
+        if (!gate || !max_dist)
+                return fail(ASLAM_ERR_ARG, "aslam_select_duplicates: null gate or max_dist");
+        const int B = c->cfg.batch;
+        std::vector<double> par(2 * (size_t)B);
+        for (int b = 0; b < B; ++b)
+        {
+                if (!(gate[b] > 0.0))
+                        return fail(ASLAM_ERR_ARG, "aslam_select_duplicates: gate[" + std::to_string(b) + "] must be positive");
+                if (!std::isfinite(max_dist[b]) || max_dist[b] <= 0.0)
+                        return fail(ASLAM_ERR_ARG, "aslam_select_duplicates: max_dist[" + std::to_string(b) + "] must be finite and positive");
+                par[b] = max_dist[b] * max_dist[b];
+                par[(size_t)B + b] = gate[b];
+        }
+        int rc = sync_ctx(c);
+        const size_t o_partner = (size_t)snap_pad64(16 * (int64_t)B);
+        if (rc == ASLAM_OK)
+                rc = snap_reserve(c, o_partner + (size_t)snap_pad64(4 * (int64_t)B * ld));
+        if (rc != ASLAM_OK)
+                return rc;
+        HIP_TRY(hipMemcpy(c->snap_dev, par.data(), sizeof(double) * 2 * B, hipMemcpyHostToDevice));
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        c->last_stream = st;
+        const double *pd = reinterpret_cast<const double *>(c->snap_dev);
+        int32_t *partner = reinterpret_cast<int32_t *>(c->snap_dev + o_partner);
+        const int wpb = MERGE_WG / PRUNE_WAVE;
+        hipLaunchKernelGGL(merge_select, dim3((unsigned)((ld + wpb - 1) / wpb), (unsigned)B), dim3(MERGE_WG), 0, st, (const double *)c->dv.X,
+                           (const double *)(c->large ? c->largeP : c->dv.P), (const int *)c->dv.n, c->NP, pd, pd + B, partner, ld);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(merge_resolve, dim3((unsigned)B), dim3(PRUNE_WAVE), 0, st, (const int32_t *)partner, into_dev, ld);
+        HIP_TRY(hipGetLastError());
         return ASLAM_OK;
 }
 

@@ -203,7 +203,13 @@ void FilterNode::removeLandmarks(const std::vector<int> &indices)
         if (indices.empty())
                 return;
         check(aslam_remove_landmarks(ctx, mask.data(), (int)mask.size(), 0, nullptr), "aslam_remove_landmarks");
-        // the host copies of X and Z and the sighting record, compacted the same way (the wait-list and the stored message stay)
+        compactHost(mask);
+}
+
+/// the host copies of X and Z and the sighting record, compacted the way the core compacts its own (the wait-list and the stored message stay)
+void FilterNode::compactHost(const std::vector<uint8_t> &mask)
+{
+        const int mapped = (int)(N - 3) / 2;
         uint32_t kept = 3;
         for (int i = 0; i < mapped; ++i)
         {
@@ -223,6 +229,100 @@ void FilterNode::removeLandmarks(const std::vector<int> &indices)
         lm_seen.resize((N - 3) / 2);
         lm_hits.resize((N - 3) / 2);
         lm_sighted.assign((N - 3) / 2, 0); // (the mask of the last callback indexed the old landmarks)
+}
+
+// aslam_merge_landmarks is bound weakly like aslam_remove_landmarks: a core without it refuses the call, at run time.
+extern "C" {
+int aslam_merge_landmarks(aslam_ctx *, const int32_t *, int, int, double, int32_t *, void *) __attribute__((weak));
+}
+
+int FilterNode::mergeLandmarks(const std::vector<std::pair<int, int>> &pairs, double noise_var)
+{
+        if (!aslam_merge_landmarks)
+                throw std::runtime_error("this core cannot merge landmarks");
+        const int mapped = (int)(N - 3) / 2;
+        std::vector<int32_t> into((size_t)std::max(mapped, (MAX_LANDMARK_COUNT - 2) / 2), -1);
+        for (const auto &p : pairs)
+        {
+                if (p.second < 0 || p.second >= mapped || into[p.second] != -1)
+                        throw std::runtime_error("mergeLandmarks: landmark index " + std::to_string(p.second) + " out of range or named twice");
+                into[p.second] = p.first; // (the core checks 0 <= i < j and the chains, and changes nothing when it refuses)
+        }
+        if (pairs.empty())
+                return 0;
+        int32_t merged = 0;
+        check(aslam_merge_landmarks(ctx, into.data(), (int)into.size(), 0, noise_var, &merged, nullptr), "aslam_merge_landmarks");
+        // the core takes the pairs in ascending j and stops, if at all, at a round: the first `merged` of them are fused and gone
+        std::vector<uint8_t> mask(into.size(), 0);
+        int done = 0;
+        for (int j = 0; j < mapped && done < merged; ++j)
+        {
+                const int i = into[j];
+                if (i < 0)
+                        continue;
+                lm_hits[i] += lm_hits[j];
+                if (sight_clock - lm_seen[j] < sight_clock - lm_seen[i])
+                        lm_seen[i] = lm_seen[j];
+                mask[j] = 1;
+                ++done;
+        }
+        if (done)
+        {
+                compactHost(mask);
+                check(aslam_get_state(ctx, 0, param_X.data(), nullptr, nullptr), "aslam_get_state"); // (the constraint moved every entry of X)
+        }
+        return done;
+}
+
+int FilterNode::mergeDuplicates(double gate, double max_dist, double noise_var)
+{
+        if (!(gate > 0.0) || !std::isfinite(max_dist) || max_dist <= 0.0)
+                throw std::runtime_error("mergeDuplicates: gate must be positive, max_dist finite and positive");
+        const double maxd2 = max_dist * max_dist;
+        int total = 0;
+        for (int pass = 0; pass < 4; ++pass)
+        {
+                const int n = (int)N, L = (n - 3) / 2;
+                if (L < 2)
+                        break;
+                std::vector<double> X((size_t)n), P((size_t)n * n);
+                check(aslam_get_state(ctx, 0, X.data(), nullptr, P.data()), "aslam_get_state");
+                // aslam_select_duplicates' arithmetic (aslam_core.h), operation by operation; this file is compiled without FMA contraction
+                std::vector<int> partner((size_t)L, -1);
+                auto p = [&](int r, int c) { return P[(size_t)r * n + c]; };
+                for (int j = 1; j < L; ++j)
+                {
+                        double best = 0.0;
+                        for (int i = 0; i < j; ++i)
+                        {
+                                const int a0 = 3 + 2 * i, a1 = a0 + 1, c0 = 3 + 2 * j, c1 = c0 + 1;
+                                const double dx = X[a0] - X[c0], dy = X[a1] - X[c1];
+                                const double r2 = dx * dx + dy * dy;
+                                if (!(r2 <= maxd2))
+                                        continue;
+                                const double s00 = ((p(a0, a0) + p(c0, c0)) - p(c0, a0)) - p(c0, a0);
+                                const double s11 = ((p(a1, a1) + p(c1, c1)) - p(c1, a1)) - p(c1, a1);
+                                const double s10 = ((p(a1, a0) + p(c1, c0)) - p(c1, a0)) - p(c0, a1);
+                                const double det = s00 * s11 - s10 * s10;
+                                if (!(s00 > 0.0) || !(det > 0.0))
+                                        continue;
+                                const double t1 = (s10 * dx) * dy;
+                                const double num = (((s11 * dx) * dx) - (t1 + t1)) + ((s00 * dy) * dy);
+                                const double m = num / det;
+                                if (m < gate && (partner[j] < 0 || m < best))
+                                        best = m, partner[j] = i;
+                        }
+                }
+                std::vector<std::pair<int, int>> pairs;
+                for (int j = 1; j < L; ++j)
+                        if (partner[j] >= 0 && partner[partner[j]] == -1)
+                                pairs.emplace_back(partner[j], j);
+                const int k = pairs.empty() ? 0 : mergeLandmarks(pairs, noise_var);
+                total += k;
+                if (k == 0)
+                        break;
+        }
+        return total;
 }
 
 int FilterNode::removeStale(uint32_t max_age)
@@ -571,6 +671,39 @@ int aslam_node_remove_landmarks(aslam_node *n, const int32_t *indices, int count
                         throw std::runtime_error("null argument");
                 n->impl->removeLandmarks(std::vector<int>(indices, indices + count));
                 return 0;
+        }
+        catch (const std::exception &e)
+        {
+                g_node_err = e.what();
+                return -1;
+        }
+}
+
+int aslam_node_merge_landmarks(aslam_node *n, const int32_t *pairs, int count, double noise_var)
+{
+        try
+        {
+                if (!n || count < 0 || (count && !pairs))
+                        throw std::runtime_error("null argument");
+                std::vector<std::pair<int, int>> pr;
+                for (int k = 0; k < count; ++k)
+                        pr.emplace_back(pairs[2 * k], pairs[2 * k + 1]);
+                return n->impl->mergeLandmarks(pr, noise_var);
+        }
+        catch (const std::exception &e)
+        {
+                g_node_err = e.what();
+                return -1;
+        }
+}
+
+int aslam_node_merge_duplicates(aslam_node *n, double gate, double max_dist, double noise_var)
+{
+        try
+        {
+                if (!n)
+                        throw std::runtime_error("null argument");
+                return n->impl->mergeDuplicates(gate, max_dist, noise_var);
         }
         catch (const std::exception &e)
         {

@@ -143,8 +143,18 @@ class FilterNode
         }
         /// removeLandmarks of every landmark whose age, clock() - lastSeen()[i] in unsigned 32-bit arithmetic, exceeds max_age; returns how many went
         int removeStale(uint32_t max_age);
+        /// Fuse duplicate landmarks (aslam_merge_landmarks of aslam_core.h): each pair (i, j), i < j, applies "i and j are the same point" (with
+        /// noise_var on the constraint's diagonal) to X and P on the core and drops j; the mirror's lastSeen / hits fuse by the core's rule (hits
+        /// add up, the younger last_seen stays), its X is read back and its Z compacted.  Returns the pairs fused; throws where the core refuses
+        /// (nothing has changed then).  Between two callbacks.
+        int mergeLandmarks(const std::vector<std::pair<int, int>> &pairs, double noise_var = 0.0);
+        /// aslam_select_duplicates' rule, evaluated here on the state read back from the core (one filter; the arithmetic of aslam_core.h operation
+        /// by operation, so the selection is the device selector's), then mergeLandmarks; passes until one merges nothing, 4 at the most.
+        /// Returns the landmarks merged.
+        int mergeDuplicates(double gate, double max_dist, double noise_var = 0.0);
 
       private:
+        void compactHost(const std::vector<uint8_t> &mask);
         int filter;
         int MAX_LANDMARK_COUNT;
         aslam_ctx *ctx;
@@ -223,6 +233,10 @@ int aslam_node_remove_landmarks(aslam_node *n, const int32_t *indices, int count
 int aslam_node_get_sightings(const aslam_node *n, uint32_t *last_seen, uint32_t *hits, int cap, uint32_t *clock);
 /* FilterNode::removeStale: the number of landmarks removed, or -1 with aslam_node_error(). */
 int aslam_node_remove_stale(aslam_node *n, uint32_t max_age);
+/* FilterNode::mergeLandmarks: pairs [count][2] = (i, j); the number of pairs fused, or -1 with aslam_node_error(). */
+int aslam_node_merge_landmarks(aslam_node *n, const int32_t *pairs, int count, double noise_var);
+/* FilterNode::mergeDuplicates: the number of landmarks merged, or -1 with aslam_node_error(). */
+int aslam_node_merge_duplicates(aslam_node *n, double gate, double max_dist, double noise_var);
 /* Narrow `count` recorded odometry messages ([count][8]: px,py,qw,qx,qy,qz,vx,wz) the way cbOdom/updateZandA do
  * (ekf.cpp:139-142): pose[count][2], yaw[count] = quat2euler(...) as binary32, twist[count][2]. */
 void aslam_host_narrow_odom(int64_t count, const double *odom, double *pose, float *yaw, double *twist);

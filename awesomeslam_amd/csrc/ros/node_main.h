@@ -28,6 +28,11 @@ template <class Filter> struct Node
         // forgetting policy (~forget_after, ~forget_period; in callbacks): every forget_period counted callbacks the landmarks last sighted more than
         // forget_after callbacks ago are removed (FilterNode::removeStale).  forget_after = 0, the default: never
         uint32_t forget_after = 0, forget_period = 1;
+        // duplicate merging (~merge_gate, ~merge_dist, ~merge_period): every merge_period counted callbacks the landmark pairs within merge_dist
+        // of each other whose Mahalanobis distance is below merge_gate are fused and one of each removed (FilterNode::mergeDuplicates;
+        // 5.99 is the 95 % point of chi-square with 2 degrees of freedom).  merge_gate = 0, the default: never
+        double merge_gate = 0.0, merge_dist = 1.0;
+        uint32_t merge_period = 1;
 
         /// the reference's constructor (ekf.cpp:39-46): subscribe, advertise, initialize() -- whose `last_time = ros::Time::now().toSec()`
         /// (ekf.cpp:54) is the `now_init` of the mirror
@@ -48,6 +53,8 @@ template <class Filter> struct Node
                         return; // no sensor message yet (ekf.cpp:76-77)
                 if (forget_after && filter.clock() % forget_period == 0)
                         filter.removeStale(forget_after);
+                if (merge_gate > 0.0 && filter.clock() % merge_period == 0)
+                        filter.mergeDuplicates(merge_gate, merge_dist);
                 const aslam::Landmarks l = filter.landmarks(); // convertToLandmarkMsg, common.h:93-108
                 awesome_slam_msgs::Landmarks out;
                 out.x = l.x;
@@ -91,7 +98,15 @@ template <class Filter> int node_main(int argc, char **argv, const char *node_na
         int forget_after = 0, forget_period = 1;
         ros::param::param("~forget_after", forget_after, 0);
         ros::param::param("~forget_period", forget_period, 1);
+        double merge_gate = 0.0, merge_dist = 1.0;
+        int merge_period = 1;
+        ros::param::param("~merge_gate", merge_gate, 0.0);
+        ros::param::param("~merge_dist", merge_dist, 1.0);
+        ros::param::param("~merge_period", merge_period, 1);
         Node<Filter> a(max_landmark_count, queue_size);
+        a.merge_gate = merge_gate > 0.0 ? merge_gate : 0.0;
+        a.merge_dist = merge_dist > 0.0 ? merge_dist : 1.0;
+        a.merge_period = merge_period < 1 ? 1u : (uint32_t)merge_period;
         a.forget_after = forget_after < 0 ? 0u : (uint32_t)forget_after;
         a.forget_period = forget_period < 1 ? 1u : (uint32_t)forget_period;
         a.filter.setParams(prm); // before the first callback: p0_pose applies

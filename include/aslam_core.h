@@ -276,6 +276,45 @@ int aslam_get_sightings(aslam_ctx *ctx, int traj, uint32_t *last_seen, uint32_t 
 int aslam_select_stale(aslam_ctx *ctx, const uint32_t *max_age, uint8_t *mask_dev, int ld, void *stream);
 /* (the mask is aslam_remove_landmarks' and aslam_select_beyond's: the same shape, synchronisation and ASLAM_ERR_ARG refusals) */
 
+/* ---- merging duplicate landmarks: select, fuse, remove ---------------------------------------------- */
+/* The reference associates by a fixed Euclidean threshold (assoc_dist); pose drift can push a landmark's re-observation past it, and the
+   observation is then promoted as a SECOND landmark at the end of the state.  A merge applies the constraint "these two are the same point"
+   and drops one of the pair.  One merge of landmark j into landmark i < j, with a = {3 + 2i, 4 + 2i}, c = {3 + 2j, 4 + 2j}:
+       H (2 x n): +I2 at columns a, -I2 at columns c       d = X[a] - X[c]       W = P H^T = P[:, a] - P[:, c]
+       S = H P H^T + noise_var I2                          X <- X - W S^-1 d     P <- P - W S^-1 W^T
+   then landmark j is removed; i keeps its index and its Z entries.  The pairs of a filter are taken in ascending j, 8 per round, the k pairs
+   of a round jointly: S is 2k x 2k, Lc = chol(S), V = Lc^-1 W^T, y = Lc^-1 d, X -= V^T y, P -= V^T V.  Rounds run one after another, a later
+   one on the P the earlier one left; several leaves of one root may share a round.  All of it in binary64, in ASLAM_F32 contexts too (P is
+   binary64 there), and P stays exactly symmetric.
+   into [batch][ld] i32, host or device (is_device; a device array 16-byte aligned): into[b][j] = i merges landmark j of filter b into i, -1
+   keeps j.  ld and "entries at or beyond a filter's landmark count are ignored" as for aslam_remove_landmarks.  ASLAM_ERR_ARG, with a message
+   that names the filter and the landmark, unless every entry is -1 or has 0 <= i < j and into[b][i] == -1 (no chains: a root is not itself
+   merged away), and unless noise_var is finite and >= 0.  A refused call leaves the context unchanged bit for bit: the device's report on
+   `into` is checked on the host before any filter is written.
+   Synchronises like aslam_remove_landmarks; one more small device-to-host copy (that report) and the synchronisation it needs come in front
+   of that call's own.  After the rounds the merged-away landmarks leave through aslam_remove_landmarks' own path (a fresh, compacted slot;
+   the sighted mask and the innovation record as after a prune); before it the sighting records fuse: hits[i] += hits[j], last_seen[i] =
+   whichever of the two is the younger (age = clock - last_seen, unsigned 32-bit).  A filter that merges nothing is not touched.
+   merged_out (host [batch] or NULL): pairs fused and removed per filter.  A filter whose S fails to factor in some round (a pivot <= 0 or
+   not finite) keeps the merges of its earlier rounds; that round's and all later pairs are left alone, neither fused nor removed, and no
+   status bit is set: the filter is valid. */
+int aslam_merge_landmarks(aslam_ctx *ctx, const int32_t *into, int ld, int is_device, double noise_var, int32_t *merged_out, void *stream);
+/* device array into_dev [batch][ld] i32 (16-byte aligned, ld as above) <- for every landmark j the i < j to merge it into, or -1; entries from
+   the landmark count up to ld are -1.  gate, max_dist: host arrays [batch]; gate > 0 (infinity allowed), max_dist finite and > 0, else
+   ASLAM_ERR_ARG.  For a pair i < j, binary64, every operation rounded on its own (no FMA), lower-triangle entries of P only, with
+   a0 = 3 + 2i, a1 = a0 + 1, c0 = 3 + 2j, c1 = c0 + 1:
+       dx = X[a0] - X[c0]    dy = X[a1] - X[c1]    r2 = dx*dx + dy*dy
+       s00 = ((P[a0][a0] + P[c0][c0]) - P[c0][a0]) - P[c0][a0]
+       s11 = ((P[a1][a1] + P[c1][c1]) - P[c1][a1]) - P[c1][a1]
+       s10 = ((P[a1][a0] + P[c1][c0]) - P[c1][a0]) - P[c0][a1]
+       det = s00*s11 - s10*s10
+       t1 = (s10*dx)*dy      num = (((s11*dx)*dx) - (t1 + t1)) + ((s00*dy)*dy)      m = num / det
+   (i, j) is a candidate iff r2 <= max_dist^2 (squared on the host), s00 > 0, det > 0 and m < gate.  partner[j] = the candidate i of smallest
+   m, ties to the smaller i, or -1.  Then into[j] = partner[j] if partner[partner[j]] == -1, else -1 -- the conservative rule: a landmark whose
+   partner is itself about to be merged waits for the next call, so every selected pair is directly gated and the array always passes
+   aslam_merge_landmarks' validation.  Synchronises the context first, then runs on `stream`. */
+int aslam_select_duplicates(aslam_ctx *ctx, const double *gate, const double *max_dist, int32_t *into_dev, int ld, void *stream);
+
 /* ---- read-back (synchronises the context's last stream) ------------------------------------------- */
 int aslam_get_dim(aslam_ctx *ctx, int traj, int *n);
 /* X[n], Z[n], P[n*n] row-major; any may be NULL */
