@@ -32,6 +32,7 @@ CORE_SYMBOLS = (
     "aslam_get_sightings", "aslam_select_stale",
     "aslam_sighted_update_enable", "aslam_get_sighted", "aslam_ekf_step_sighted", "aslam_ekf_step_batch_sighted",
     "aslam_merge_landmarks", "aslam_select_duplicates",
+    "aslam_gate_observations",
 )
 NODE_SYMBOLS = (
     "aslam_node_create", "aslam_node_create_at", "aslam_node_destroy", "aslam_node_error", "aslam_node_sensor", "aslam_node_odom",
@@ -40,6 +41,7 @@ NODE_SYMBOLS = (
     "aslam_node_set_params", "aslam_node_get_params", "aslam_node_remove_landmarks",
     "aslam_node_get_sightings", "aslam_node_remove_stale", "aslam_node_set_sighted_only",
     "aslam_node_merge_landmarks", "aslam_node_merge_duplicates",
+    "aslam_node_set_assoc_gate", "aslam_node_assoc_rejected",
 )
 TRACE_FILE_SYMBOLS = (
     "aslam_trace_file_open", "aslam_trace_file_close", "aslam_trace_file_error", "aslam_trace_file_dims",
@@ -194,6 +196,7 @@ def core_lib():
         L.aslam_select_stale.argtypes = [vp, pu, vp, ci, vp]
         L.aslam_merge_landmarks.argtypes = [vp, vp, ci, ci, cd, vp, vp]
         L.aslam_select_duplicates.argtypes = [vp, pd, pd, vp, ci, vp]
+        L.aslam_gate_observations.argtypes = [vp, vp, ci, ci, ctypes.POINTER(ctypes.c_int32), pd, vp, vp, vp]
         pb = ctypes.POINTER(ctypes.c_uint8)
         L.aslam_sighted_update_enable.argtypes = [vp, ci]
         L.aslam_get_sighted.argtypes = [vp, ci, pb, ci, pi]
@@ -244,6 +247,9 @@ def node_lib():
         L.aslam_node_set_sighted_only.argtypes = [vp, ci]
         L.aslam_node_merge_landmarks.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ci, ctypes.c_double]
         L.aslam_node_merge_duplicates.argtypes = [vp, ctypes.c_double, ctypes.c_double, ctypes.c_double]
+        L.aslam_node_set_assoc_gate.argtypes = [vp, ctypes.c_double]
+        L.aslam_node_assoc_rejected.argtypes = [vp]
+        L.aslam_node_assoc_rejected.restype = ctypes.c_uint64
         # include/aslam_trace_file.h
         L.aslam_trace_file_error.restype = ctypes.c_char_p
         L.aslam_trace_file_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
@@ -789,6 +795,38 @@ class Core:
                 break
         return total
 
+    # ---- Mahalanobis-gated data association (aslam_gate_observations)
+    def gate_observations(self, obs, n_obs, gate, stream=None):
+        """For every observation the landmark of smallest Mahalanobis distance m = v^T (H_k P H_k^T + R)^-1 v if m < gate, else -1
+        (aslam_gate_observations; binary64 on the device, P never leaves it).  `obs`: [batch, ldo, 2] float32 (range, bearing), a NumPy array
+        or a contiguous float32 device tensor; `n_obs`: [batch] observations per filter; `gate`: a scalar or one value per filter (9.21: the
+        99 % point of chi-square with 2 degrees of freedom).  Returns (assoc [batch, ldo] int32, mdist [batch, ldo] float64) as NumPy arrays:
+        -1 and +inf from n_obs[b] on.  Reads the filters, changes nothing."""
+        import torch
+
+        if hasattr(obs, "data_ptr"):
+            if obs.dim() != 3 or obs.shape[0] != self.batch or obs.shape[2] != 2 or obs.dtype != torch.float32 or not obs.is_contiguous():
+                raise ValueError("a device obs is a contiguous [batch, ldo, 2] float32 tensor")
+            ptr, ldo, dev = obs.data_ptr(), obs.shape[1], True
+        else:
+            obs = np.ascontiguousarray(obs, np.float32)
+            if obs.ndim != 3 or obs.shape[0] != self.batch or obs.shape[2] != 2:
+                raise ValueError("`obs` is [batch, ldo, 2]")
+            ptr, ldo, dev = obs.ctypes.data, obs.shape[1], False
+        assoc = torch.empty((self.batch, max(ldo, 1)), dtype=torch.int32, device="cuda")
+        mdist = torch.empty((self.batch, max(ldo, 1)), dtype=torch.float64, device="cuda")
+        self.gate_observations_ptr(ptr, ldo, dev, n_obs, gate, assoc.data_ptr(), mdist.data_ptr(), stream)
+        self.sync(stream)
+        return assoc.cpu().numpy(), mdist.cpu().numpy()
+
+    def gate_observations_ptr(self, obs_ptr, ldo, is_device, n_obs, gate, assoc_ptr, mdist_ptr=None, stream=None):
+        """aslam_gate_observations as it is: raw pointers (ints) to obs [batch][ldo][2] f32 and to the device outputs assoc [batch][ldo] i32 and
+        mdist [batch][ldo] f64 (or None); n_obs [batch] and gate (a scalar, or [batch]) are host values.  Asynchronous on `stream`."""
+        k = None if n_obs is None else np.ascontiguousarray(np.broadcast_to(np.asarray(n_obs, np.int32), (self.batch,)))
+        g = None if gate is None else np.ascontiguousarray(np.broadcast_to(np.asarray(gate, np.float64), (self.batch,)))
+        _chk(core_lib().aslam_gate_observations(self._h, obs_ptr, int(ldo), 1 if is_device else 0, _ptr(k, ctypes.c_int32), _ptr(g, ctypes.c_double),
+                                                assoc_ptr, mdist_ptr, stream))
+
     def layout(self):
         npad, nbytes = ctypes.c_int(), ctypes.c_int64()
         _chk(core_lib().aslam_get_layout(self._h, ctypes.byref(npad), ctypes.byref(nbytes)))
@@ -931,6 +969,16 @@ class Node:
         if k < 0:
             raise AslamError(node_lib().aslam_node_error().decode())
         return k
+
+    def set_assoc_gate(self, gate):
+        """FilterNode::setAssocGate: associate by the Mahalanobis gate of aslam_gate_observations (9.21: 99 % of chi-square with 2 degrees of
+        freedom); 0, the default, keeps the reference's Euclidean rule.  A negative or NaN value is refused."""
+        if node_lib().aslam_node_set_assoc_gate(self._h, float(gate)) != 0:
+            raise AslamError(node_lib().aslam_node_error().decode())
+
+    def assoc_rejected(self):
+        """FilterNode::assocRejected: observations dropped because the gate refused them while the Euclidean rule would have associated them."""
+        return int(node_lib().aslam_node_assoc_rejected(self._h))
 
     def wait_list(self, cap=4096):
         r, b, c = np.empty(cap, np.float32), np.empty(cap, np.float32), np.empty(cap, np.uint32)

@@ -26,6 +26,7 @@
 #include "snapshot.h"
 #include "prune.h"
 #include "merge.h"
+#include "assoc.h"
 #if ASLAM_HAVE_UKF
 #include "ukf_small.h"
 #include "ukf_large.h"
@@ -1672,6 +1673,64 @@ int aslam_select_duplicates(aslam_ctx *c, const double *gate, const double *max_
                            (const double *)(c->large ? c->largeP : c->dv.P), (const int *)c->dv.n, c->NP, pd, pd + B, partner, ld);
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(merge_resolve, dim3((unsigned)B), dim3(PRUNE_WAVE), 0, st, (const int32_t *)partner, into_dev, ld);
+        HIP_TRY(hipGetLastError());
+        return ASLAM_OK;
+}
+
+/* ---- Mahalanobis-gated data association (assoc.h) ------------------------------------------------------------------------ */
+int aslam_gate_observations(aslam_ctx *c, const float *obs, int ldo, int is_device, const int32_t *n_obs, const double *gate, int32_t *assoc_dev,
+                            double *mdist_dev, void *stream)
+{
+        const std::string who = "aslam_gate_observations: ";
+        if (!c)
+                return fail(ASLAM_ERR_ARG, who + "null context");
+        if (!obs)
+                return fail(ASLAM_ERR_ARG, who + "null obs");
+        if (!n_obs)
+                return fail(ASLAM_ERR_ARG, who + "null n_obs");
+        if (!gate)
+                return fail(ASLAM_ERR_ARG, who + "null gate");
+        if (!assoc_dev)
+                return fail(ASLAM_ERR_ARG, who + "null assoc_dev");
+        if (ldo < 1)
+                return fail(ASLAM_ERR_ARG, who + "ldo must be at least 1");
+        const int B = c->cfg.batch;
+        for (int b = 0; b < B; ++b)
+        {
+                if (n_obs[b] < 0 || n_obs[b] > ldo)
+                        return fail(ASLAM_ERR_ARG, who + "n_obs[" + std::to_string(b) + "] = " + std::to_string(n_obs[b]) + " is outside 0 .. ldo (filter " +
+                                                       std::to_string(b) + ")");
+                if (!(gate[b] > 0.0))
+                        return fail(ASLAM_ERR_ARG, who + "gate[" + std::to_string(b) + "] must be positive (filter " + std::to_string(b) + ")");
+        }
+        if (is_device && ((uintptr_t)obs & 15))
+                return fail(ASLAM_ERR_ARG, who + "a device obs must be 16-byte aligned");
+        if ((uintptr_t)assoc_dev & 15)
+                return fail(ASLAM_ERR_ARG, who + "assoc_dev must be 16-byte aligned");
+        if ((uintptr_t)mdist_dev & 15)
+                return fail(ASLAM_ERR_ARG, who + "mdist_dev must be 16-byte aligned");
+        int rc = sync_ctx(c);
+        // staging: gate | n_obs | a host array's copy
+        const size_t o_n = (size_t)snap_pad64(8 * (int64_t)B);
+        const size_t o_obs = o_n + (size_t)snap_pad64(4 * (int64_t)B);
+        const size_t obs_bytes = sizeof(float) * 2 * (size_t)B * ldo;
+        if (rc == ASLAM_OK)
+                rc = snap_reserve(c, o_obs + (is_device ? 0 : (size_t)snap_pad64((int64_t)obs_bytes)));
+        if (rc != ASLAM_OK)
+                return rc;
+        HIP_TRY(hipMemcpy(c->snap_dev, gate, sizeof(double) * B, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->snap_dev + o_n, n_obs, sizeof(int32_t) * B, hipMemcpyHostToDevice));
+        const float *odev = obs;
+        if (!is_device)
+        {
+                HIP_TRY(hipMemcpy(c->snap_dev + o_obs, obs, obs_bytes, hipMemcpyHostToDevice));
+                odev = reinterpret_cast<const float *>(c->snap_dev + o_obs);
+        }
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        c->last_stream = st;
+        hipLaunchKernelGGL(assoc_gate, dim3((unsigned)B), dim3(ASSOC_WG), 0, st, (const double *)c->dv.X, (const double *)(c->large ? c->largeP : c->dv.P),
+                           (const int *)c->dv.n, c->NP, (const aslam_params *)c->params_dev, odev, ldo, reinterpret_cast<const int32_t *>(c->snap_dev + o_n),
+                           reinterpret_cast<const double *>(c->snap_dev), assoc_dev, mdist_dev);
         HIP_TRY(hipGetLastError());
         return ASLAM_OK;
 }

@@ -77,8 +77,12 @@ FilterNode::FilterNode(int filter_, int max_landmark_count, int device, double n
         check(aslam_create(&cfg, &ctx), "aslam_create");
 }
 
+extern "C" int hipFree(void *) __attribute__((weak)); // (associateGated's array: see there)
+
 FilterNode::~FilterNode()
 {
+        if (gate_dev && hipFree)
+                (void)hipFree(gate_dev);
         aslam_destroy(ctx);
 }
 
@@ -325,6 +329,82 @@ int FilterNode::mergeDuplicates(double gate, double max_dist, double noise_var)
         return total;
 }
 
+// aslam_gate_observations is bound weakly like the entry points above.  Its output is a device array, and this file is plain C++: the three
+// calls of the HIP runtime it needs for that array (the copy libaslam_core.so itself is linked against) are declared here with their C ABI
+// -- hipError_t and hipMemcpyKind are int-sized enums -- and bound weakly too, so that the mirror still links where no HIP runtime is.
+extern "C" {
+int aslam_gate_observations(aslam_ctx *, const float *, int, int, const int32_t *, const double *, int32_t *, double *, void *) __attribute__((weak));
+int hipMalloc(void **, size_t) __attribute__((weak));
+int hipFree(void *) __attribute__((weak));
+int hipMemcpy(void *, const void *, size_t, int) __attribute__((weak));
+}
+
+void FilterNode::setAssocGate(double gate)
+{
+        if (!(gate >= 0.0))
+                throw std::runtime_error("setAssocGate: the gate must be positive, or 0 for off");
+        assoc_gate = gate;
+}
+
+/// updateZ's association with the gate on and `mapped` > 0 landmarks: one aslam_gate_observations call for the stored message, then the
+/// observations in message order (see setAssocGate in aslam_node.h)
+void FilterNode::associateGated(uint32_t mapped, std::vector<uint8_t> &sighted)
+{
+        if (!aslam_gate_observations || !hipMalloc || !hipFree || !hipMemcpy)
+                throw std::runtime_error("this core cannot gate observations");
+        const size_t count = sensor_landmark.size();
+        std::vector<float> ob(2 * count);
+        for (size_t j = 0; j < count; ++j)
+        {
+                LaserData &obs = sensor_landmark[j];
+                obs.bearing = normalizeAngle(obs.bearing);
+                ob[2 * j] = obs.range;
+                ob[2 * j + 1] = obs.bearing;
+        }
+        if (count > gate_cap)
+        {
+                if (gate_dev)
+                        (void)hipFree(gate_dev);
+                gate_dev = nullptr;
+                gate_cap = 0;
+                const size_t cap = std::max<size_t>(64, 2 * count);
+                if (hipMalloc(&gate_dev, sizeof(int32_t) * cap) != 0)
+                        throw std::runtime_error("associateGated: hipMalloc failed");
+                gate_cap = cap;
+        }
+        const int32_t n_obs = (int32_t)count;
+        std::vector<int32_t> assoc(count, -1);
+        check(aslam_gate_observations(ctx, ob.data(), (int)count, 0, &n_obs, &assoc_gate, static_cast<int32_t *>(gate_dev), nullptr, nullptr),
+              "aslam_gate_observations");
+        if (hipMemcpy(assoc.data(), gate_dev, sizeof(int32_t) * count, 2 /* hipMemcpyDeviceToHost: waits for the launch on the default stream */) != 0)
+                throw std::runtime_error("associateGated: hipMemcpy failed");
+        for (size_t j = 0; j < count; ++j)
+        {
+                const LaserData &obs = sensor_landmark[j];
+                if (assoc[j] >= 0 && (uint32_t)assoc[j] < mapped)
+                {
+                        param_Z[3 + 2 * assoc[j]] = obs.range;
+                        param_Z[4 + 2 * assoc[j]] = obs.bearing;
+                        sighted[assoc[j]] = 1;
+                        continue;
+                }
+                // the reference's own test (updateZ below), for the verdict alone
+                const WorldPoint seen = project(obs, param_Z);
+                float best_d = 0.0f;
+                for (uint32_t k = 0; k < mapped; ++k)
+                {
+                        const WorldPoint known = {(float)param_X[3 + 2 * k], (float)param_X[4 + 2 * k]};
+                        const float dk = separation(seen, known);
+                        if (k == 0 || dk < best_d)
+                                best_d = dk;
+                }
+                if (best_d < prm.assoc_dist)
+                        assoc_rejected += 1; // dropped: the Euclidean rule would have made it a match, the gate says it is none
+                else
+                        updateNewLandmarkWait(obs);
+        }
+}
+
 int FilterNode::removeStale(uint32_t max_age)
 {
         std::vector<int> stale;
@@ -357,6 +437,10 @@ void FilterNode::updateZ(const Odometry &msg, float delta_time)
         sight_clock += 1;
         std::vector<uint8_t> &sighted = lm_sighted; // several observations on one landmark are one hit; the mask of this callback
         sighted.assign(mapped, 0);
+        const bool gated = assoc_gate > 0.0 && mapped > 0 && !sensor_landmark.empty();
+        if (gated)
+                associateGated(mapped, sighted);
+        else // the reference's rule, line for line what it was
         for (LaserData &obs : sensor_landmark)
         {
                 obs.bearing = normalizeAngle(obs.bearing);
@@ -710,6 +794,27 @@ int aslam_node_merge_duplicates(aslam_node *n, double gate, double max_dist, dou
                 g_node_err = e.what();
                 return -1;
         }
+}
+
+int aslam_node_set_assoc_gate(aslam_node *n, double gate)
+{
+        try
+        {
+                if (!n)
+                        throw std::runtime_error("null argument");
+                n->impl->setAssocGate(gate);
+                return 0;
+        }
+        catch (const std::exception &e)
+        {
+                g_node_err = e.what();
+                return -1;
+        }
+}
+
+uint64_t aslam_node_assoc_rejected(const aslam_node *n)
+{
+        return n->impl->assocRejected();
 }
 
 int aslam_node_get_sightings(const aslam_node *n, uint32_t *last_seen, uint32_t *hits, int cap, uint32_t *clock)

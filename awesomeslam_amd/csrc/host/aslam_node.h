@@ -152,9 +152,32 @@ class FilterNode
         /// by operation, so the selection is the device selector's), then mergeLandmarks; passes until one merges nothing, 4 at the most.
         /// Returns the landmarks merged.
         int mergeDuplicates(double gate, double max_dist, double noise_var = 0.0);
+        /// Mahalanobis-gated association (aslam_gate_observations of aslam_core.h).  gate = 0, the default: off, updateZ associates by the
+        /// reference's Euclidean rule alone.  gate > 0 (9.21: the 99 % point of chi-square with 2 degrees of freedom), once a landmark is mapped:
+        /// updateZ asks the core for the gated landmark of every observation of the stored message in ONE call and copies the indices back (4
+        /// bytes per observation; P stays on the device).  An observation the gate accepts goes to that landmark; one it refuses although the
+        /// Euclidean rule (best_d < assoc_dist) would have associated it is DROPPED -- neither a match nor evidence for a new landmark, which
+        /// is what keeps drift from promoting duplicates -- and counted in assocRejected(); every other one goes to the wait-list as before
+        /// (the wait-list stays Euclidean: its entries have no covariance).  The gate is evaluated at the state the last callback left on
+        /// the device: the motion of one odometry period is not added.  Throws on a negative or NaN gate, and at the first gated callback with
+        /// a core that lacks the entry point or without the HIP runtime in the process (both bound weakly, like the innovation record).
+        void setAssocGate(double gate);
+        double assocGate() const
+        {
+                return assoc_gate;
+        }
+        uint64_t assocRejected() const
+        {
+                return assoc_rejected;
+        }
 
       private:
         void compactHost(const std::vector<uint8_t> &mask);
+        void associateGated(uint32_t mapped, std::vector<uint8_t> &sighted);
+        double assoc_gate = 0.0;
+        uint64_t assoc_rejected = 0;
+        void *gate_dev = nullptr; // device [gate_cap] i32: the indices of one gated message
+        size_t gate_cap = 0;
         int filter;
         int MAX_LANDMARK_COUNT;
         aslam_ctx *ctx;
@@ -237,6 +260,10 @@ int aslam_node_remove_stale(aslam_node *n, uint32_t max_age);
 int aslam_node_merge_landmarks(aslam_node *n, const int32_t *pairs, int count, double noise_var);
 /* FilterNode::mergeDuplicates: the number of landmarks merged, or -1 with aslam_node_error(). */
 int aslam_node_merge_duplicates(aslam_node *n, double gate, double max_dist, double noise_var);
+/* FilterNode::setAssocGate (0 = off, the default): 0, or -1 with aslam_node_error() (a negative or NaN gate). */
+int aslam_node_set_assoc_gate(aslam_node *n, double gate);
+/* FilterNode::assocRejected: observations the gate dropped although the Euclidean rule would have associated them. */
+uint64_t aslam_node_assoc_rejected(const aslam_node *n);
 /* Narrow `count` recorded odometry messages ([count][8]: px,py,qw,qx,qy,qz,vx,wz) the way cbOdom/updateZandA do
  * (ekf.cpp:139-142): pose[count][2], yaw[count] = quat2euler(...) as binary32, twist[count][2]. */
 void aslam_host_narrow_odom(int64_t count, const double *odom, double *pose, float *yaw, double *twist);

@@ -103,7 +103,12 @@ template <class Filter> int node_main(int argc, char **argv, const char *node_na
         ros::param::param("~merge_gate", merge_gate, 0.0);
         ros::param::param("~merge_dist", merge_dist, 1.0);
         ros::param::param("~merge_period", merge_period, 1);
+        // ~assoc_gate: associate by the Mahalanobis gate (FilterNode::setAssocGate; 9.21 is the 99 % point of chi-square with 2 degrees of
+        // freedom) and drop the observations it refuses although they lie within assoc_dist.  0, the default: the reference's Euclidean rule
+        double assoc_gate = 0.0;
+        ros::param::param("~assoc_gate", assoc_gate, 0.0);
         Node<Filter> a(max_landmark_count, queue_size);
+        a.filter.setAssocGate(assoc_gate > 0.0 ? assoc_gate : 0.0);
         a.merge_gate = merge_gate > 0.0 ? merge_gate : 0.0;
         a.merge_dist = merge_dist > 0.0 ? merge_dist : 1.0;
         a.merge_period = merge_period < 1 ? 1u : (uint32_t)merge_period;

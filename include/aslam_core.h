@@ -315,6 +315,31 @@ int aslam_merge_landmarks(aslam_ctx *ctx, const int32_t *into, int ld, int is_de
    aslam_merge_landmarks' validation.  Synchronises the context first, then runs on `stream`. */
 int aslam_select_duplicates(aslam_ctx *ctx, const double *gate, const double *max_dist, int32_t *into_dev, int ld, void *stream);
 
+/* ---- Mahalanobis-gated data association -------------------------------------------------------------- */
+/* The reference associates an observation with the landmark nearest to it if that is closer than assoc_dist, a fixed Euclidean threshold that
+   ignores the covariance.  This call evaluates the individual-compatibility gate where P lives: for every observation of every filter the
+   innovation against each landmark, weighed by S_k = H_k P H_k^T + R, against a chi-square point (9.21 is the 99 % point of chi-square with
+   2 degrees of freedom).  All arithmetic is binary64, in ASLAM_F32 contexts too; only lower-triangle entries of P are read.
+   For filter b with L = (n_b - 3) / 2 landmarks and landmark k, a0 = 3 + 2k, a1 = a0 + 1:
+       dx = X[a0] - X[0]    dy = X[a1] - X[1]    q = dx^2 + dy^2    rh = sqrt(q)    bh = atan2(dy, dx) - X[2]
+       H_k (2 x 5 over the columns 0, 1, 2, a0, a1):   range row (-dx/rh, -dy/rh, 0, dx/rh, dy/rh),   bearing row (dy/q, -dx/q, -1, -dy/q, dx/q)
+       S = H_k P5 H_k^T (P5: the symmetric 5 x 5 of those rows and columns)
+       s00 = S00 + r_range    s11 = S11 + r_bearing    s10 = S10    det = s00 s11 - s10^2        (the filter's own aslam_params)
+   The landmark is valid iff q > 0, s00 > 0 and det > 0 (a NaN fails every comparison).  For observation j = (r, beta), binary32 widened:
+       v0 = r - rh    v1 = remainder(beta - bh, 2 pi) (the IEEE remainder; 2 pi rounded to binary64)
+       m = (s11 v0^2 - 2 s10 v0 v1 + s00 v1^2) / det                                              (a NaN m is skipped)
+   mdist[b][j] = the smallest m over the valid landmarks, +inf when there is none; assoc[b][j] = the k that attains it if m < gate[b], else
+   -1; ties go to the smaller k.  Entries j >= n_obs[b] get -1 and +inf.
+   obs [batch][ldo][2] f32 (range, bearing), host or device (is_device; a device array 16-byte aligned); n_obs, gate: host arrays [batch];
+   assoc_dev: device [batch][ldo] i32; mdist_dev: device [batch][ldo] f64, or NULL (both 16-byte aligned).  ASLAM_ERR_ARG, with a message that
+   names the argument (and the filter, where there is one): a null obs, n_obs, gate or assoc_dev, ldo < 1, an n_obs[b] outside 0 .. ldo, a
+   gate[b] that is not > 0 (infinity is allowed), a misaligned device pointer.  A refused call launches nothing.
+   Synchronises the context first, then runs on `stream` (one launch, one workgroup per filter); the outputs are complete when the stream
+   is.  The call reads X, P, the dimensions and the parameters and writes nothing a filter owns.  It works on every kind of context; for the
+   UKF it is this same linearised gate, not the S of the sigma points.  The replay seam (aslam_replay) keeps the Euclidean rule. */
+int aslam_gate_observations(aslam_ctx *ctx, const float *obs, int ldo, int is_device, const int32_t *n_obs, const double *gate, int32_t *assoc_dev,
+                            double *mdist_dev, void *stream);
+
 /* ---- read-back (synchronises the context's last stream) ------------------------------------------- */
 int aslam_get_dim(aslam_ctx *ctx, int traj, int *n);
 /* X[n], Z[n], P[n*n] row-major; any may be NULL */
