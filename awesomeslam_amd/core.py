@@ -42,6 +42,7 @@ NODE_SYMBOLS = (
     "aslam_node_get_sightings", "aslam_node_remove_stale", "aslam_node_set_sighted_only",
     "aslam_node_merge_landmarks", "aslam_node_merge_duplicates",
     "aslam_node_set_assoc_gate", "aslam_node_assoc_rejected",
+    "aslam_node_join_map",
 )
 TRACE_FILE_SYMBOLS = (
     "aslam_trace_file_open", "aslam_trace_file_close", "aslam_trace_file_error", "aslam_trace_file_dims",
@@ -86,6 +87,20 @@ class Params(ctypes.Structure):
                 raise KeyError(f"aslam_params has no field {k!r}")
             setattr(p, k, v)
         return p
+
+
+class Frame(ctypes.Structure):
+    """aslam_frame (include/aslam_snapshot.h): p' = t + R(phi) p with the covariance of (tx, ty, phi), row-major.  96 bytes."""
+    _fields_ = [("tx", ctypes.c_double), ("ty", ctypes.c_double), ("phi", ctypes.c_double), ("cov", ctypes.c_double * 9)]
+
+    @classmethod
+    def make(cls, frame=None):
+        """A Frame from a Frame, a (tx, ty, phi, cov3x3 or None) tuple, or None (the identity with zero covariance)."""
+        if isinstance(frame, cls):
+            return cls.from_buffer_copy(frame)
+        tx, ty, phi, cov = (0.0, 0.0, 0.0, None) if frame is None else frame
+        cov = np.zeros(9) if cov is None else np.asarray(cov, np.float64).reshape(9)
+        return cls(float(tx), float(ty), float(phi), (ctypes.c_double * 9)(*cov))
 
 
 def default_params():
@@ -209,6 +224,7 @@ def core_lib():
         L.aslam_snapshot_check.argtypes = [vp, ctypes.c_int64, p32, p32]
         L.aslam_snapshot.argtypes = [vp, p32, ci, vp, ctypes.c_int64, ci, p64, vp]
         L.aslam_restore.argtypes = [vp, p32, p32, ci, vp, ctypes.c_int64, ci, vp]
+        L.aslam_join_maps.argtypes = [vp, p32, p32, ci, vp, ctypes.c_int64, ci, ctypes.POINTER(Frame), vp, ci, p32, vp]
         _core = L
     return _core
 
@@ -247,6 +263,7 @@ def node_lib():
         L.aslam_node_set_sighted_only.argtypes = [vp, ci]
         L.aslam_node_merge_landmarks.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ci, ctypes.c_double]
         L.aslam_node_merge_duplicates.argtypes = [vp, ctypes.c_double, ctypes.c_double, ctypes.c_double]
+        L.aslam_node_join_map.argtypes = [vp, vp, ctypes.c_int64, ci, pd, ctypes.POINTER(ctypes.c_uint8), ci]
         L.aslam_node_set_assoc_gate.argtypes = [vp, ctypes.c_double]
         L.aslam_node_assoc_rejected.argtypes = [vp]
         L.aslam_node_assoc_rejected.restype = ctypes.c_uint64
@@ -276,7 +293,7 @@ def _chk(rc):
 
 SCAN_SYMBOLS = ("aslam_scan_landmarks",)
 # every symbol include/aslam_snapshot.h declares
-SNAPSHOT_SYMBOLS = ("aslam_snapshot_record_bytes", "aslam_snapshot_check", "aslam_snapshot", "aslam_restore")
+SNAPSHOT_SYMBOLS = ("aslam_snapshot_record_bytes", "aslam_snapshot_check", "aslam_snapshot", "aslam_restore", "aslam_join_maps")
 SCAN_BEAMS = 360
 SCAN_REF_ABORT, SCAN_OVERFLOW = 1, 2
 
@@ -626,6 +643,51 @@ class Core:
             cnt = snapfmt.blob_info(blob)[1]
         _chk(core_lib().aslam_restore(self._h, _ptr(r, ctypes.c_int32), _ptr(t, ctypes.c_int32), cnt, ptr, size, 1 if dev else 0, stream))
 
+    # ---- joining maps (aslam_join_maps)
+    def join_maps(self, blob, records=None, trajs=None, frames=None, select=None, stream=None):
+        """Append the landmarks of record records[i] of `blob` (default i), with their covariance block, behind the state of the running filter
+        trajs[i] (default i): the two maps are taken as INDEPENDENT (zero cross-covariance), which is the caller's to ensure.  `blob`: bytes, a
+        host uint8 array, a uint8 torch tensor on the device, or a (device pointer, bytes) pair; the record may come from either filter kind.
+        `frames`: None (identity, zero covariance) or one (tx, ty, phi, cov3x3) per entry -- source frame -> this filter's frame, see
+        mapjoin.frame / mapjoin.align.  `select`: None (every landmark of the record) or a [count, L] bool / uint8 array, entry (i, k) != 0
+        takes landmark k of entry i's record.  Returns the landmarks appended per entry, int32 [count].  A refused call (AslamError) leaves the
+        context unchanged.  Asynchronous on `stream` for a device blob, which must stay alive until the stream has passed."""
+        r = None if records is None else np.ascontiguousarray(records, np.int32)
+        t = None if trajs is None else np.ascontiguousarray(trajs, np.int32)
+        if isinstance(blob, tuple):
+            ptr, size, dev = int(blob[0]), int(blob[1]), True
+        elif hasattr(blob, "data_ptr"):
+            ptr, size, dev = blob.data_ptr(), blob.numel(), True
+        else:
+            blob = np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else np.ascontiguousarray(blob, np.uint8)
+            ptr, size, dev = blob.ctypes.data, blob.size, False
+        if r is not None or t is not None:
+            cnt = len(r if r is not None else t)
+        elif dev:
+            raise ValueError("name the records or the slots of a device blob (its count is on the device)")
+        else:
+            from . import snapshot as snapfmt
+
+            cnt = snapfmt.blob_info(blob)[1]
+        if frames is not None and len(frames) != cnt:
+            raise ValueError("one frame per entry")
+        m = None
+        if select is not None:
+            m = np.ascontiguousarray(np.asarray(select) != 0, np.uint8)
+            if m.ndim != 2 or m.shape[0] != cnt:
+                raise ValueError("`select` is [count, L]")
+        return self.join_maps_ptr(r, t, cnt, ptr, size, dev, frames, None if m is None else m.ctypes.data, 0 if m is None else m.shape[1], stream)
+
+    def join_maps_ptr(self, records, trajs, count, blob_ptr, nbytes, is_device, frames=None, select_ptr=None, ld=0, stream=None):
+        """aslam_join_maps as it is: raw pointers (ints) to the blob and to a host [count][ld] u8 selection (or None); `records` / `trajs`:
+        int32 arrays or None; `frames`: None, one Frame / (tx, ty, phi, cov) per entry, or a ready (Frame * count) array.  Returns joined_out
+        [count]."""
+        fr = frames if frames is None or isinstance(frames, ctypes.Array) else (Frame * int(count))(*(Frame.make(f) for f in frames))
+        out = np.zeros(int(count), np.int32)
+        _chk(core_lib().aslam_join_maps(self._h, _ptr(records, ctypes.c_int32), _ptr(trajs, ctypes.c_int32), int(count), blob_ptr, int(nbytes),
+                                        1 if is_device else 0, fr, select_ptr, int(ld), _ptr(out, ctypes.c_int32), stream))
+        return out
+
     def save(self, path, trajs=None):
         """snapshot() to a file: the file IS the blob."""
         self.snapshot(trajs).tofile(path)
@@ -966,6 +1028,22 @@ class Node:
     def merge_duplicates(self, gate, max_dist, noise_var=0.0):
         """FilterNode::mergeDuplicates: aslam_select_duplicates + mergeLandmarks, passes until one merges nothing (4 at the most)."""
         k = node_lib().aslam_node_merge_duplicates(self._h, float(gate), float(max_dist), float(noise_var))
+        if k < 0:
+            raise AslamError(node_lib().aslam_node_error().decode())
+        return k
+
+    def join_map(self, blob, record=0, frame=None, select=None):
+        """FilterNode::joinMap: the landmarks of record `record` of a host snapshot `blob` (bytes or a uint8 array), with their covariance
+        block, behind this filter's state as an independent map (Core.join_maps).  `frame`: None or (tx, ty, phi, cov3x3); `select`: None or one
+        bool per landmark of the record.  Returns how many were joined."""
+        b = np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else np.ascontiguousarray(blob, np.uint8)
+        f12 = None
+        if frame is not None:
+            fr = Frame.make(frame)
+            f12 = np.array([fr.tx, fr.ty, fr.phi] + list(fr.cov), np.float64)
+        m = None if select is None else np.ascontiguousarray(np.asarray(select).reshape(-1) != 0, np.uint8)
+        k = node_lib().aslam_node_join_map(self._h, b.ctypes.data, b.size, int(record), _ptr(f12, ctypes.c_double), _ptr(m, ctypes.c_uint8),
+                                           0 if m is None else len(m))
         if k < 0:
             raise AslamError(node_lib().aslam_node_error().decode())
         return k

@@ -26,6 +26,7 @@
 #include "snapshot.h"
 #include "prune.h"
 #include "merge.h"
+#include "join.h"
 #include "assoc.h"
 #if ASLAM_HAVE_UKF
 #include "ukf_small.h"
@@ -1205,6 +1206,65 @@ int aslam_snapshot(aslam_ctx *c, const int32_t *trajs, int count, void *blob, in
         return ASLAM_OK;
 }
 
+namespace
+{
+/// The blob header, the offset table and every record header of a blob, validated, on the host (aslam_restore, aslam_join_maps).  A device
+/// blob's come through `st`: the blob header, the offset table, and all record headers through one gather launch -- three small copies, each
+/// followed by a synchronisation of `st`; the gather stages `front` bytes into the context's block.
+int snap_headers(aslam_ctx *c, const void *blob, int64_t bytes, int is_device, hipStream_t st, size_t front, SnapBlobHeader &h,
+                 std::vector<uint64_t> &table, std::vector<SnapRecHeader> &recs)
+{
+        int rc;
+        const char *b = static_cast<const char *>(blob);
+        int64_t table_end = 0;
+        if (!is_device)
+        {
+                int32_t cnt = 0;
+                if ((rc = aslam_snapshot_check(blob, bytes, nullptr, &cnt)) != ASLAM_OK)
+                        return rc;
+                std::memcpy(&h, b, 64);
+                table.resize(cnt), recs.resize(cnt);
+                for (int i = 0; i < cnt; ++i)
+                {
+                        std::memcpy(&table[i], b + 64 + 8 * (size_t)i, 8);
+                        std::memcpy(&recs[i], b + table[i], 64);
+                }
+                return ASLAM_OK;
+        }
+        if (bytes >= 64)
+        {
+                HIP_TRY(hipMemcpyAsync(&h, b, 64, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipStreamSynchronize(st));
+        }
+        if (const char *e = snap_check_header(h, bytes, &table_end))
+                return fail(ASLAM_ERR_ARG, std::string("snapshot: ") + e);
+        const size_t cnt = h.count;
+        table.resize(cnt), recs.resize(cnt);
+        if (!cnt)
+                return ASLAM_OK;
+        HIP_TRY(hipMemcpyAsync(table.data(), b + 64, 8 * cnt, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (size_t i = 0; i < cnt; ++i)
+                if (const char *e = snap_check_offset(table[i], table_end, h.total_bytes))
+                        return fail(ASLAM_ERR_ARG, "snapshot record " + std::to_string(i) + ": " + e);
+        // one gather launch through the validated table, one copy
+        const size_t tbytes = (size_t)snap_pad64(8 * (int64_t)cnt);
+        if ((rc = snap_reserve(c, front + tbytes + 64 * cnt)) != ASLAM_OK)
+                return rc;
+        uint64_t *tdev = reinterpret_cast<uint64_t *>(c->snap_dev + front);
+        SnapRecHeader *hdev = reinterpret_cast<SnapRecHeader *>(c->snap_dev + front + tbytes);
+        HIP_TRY(hipMemcpyAsync(tdev, table.data(), 8 * cnt, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(snapshot_gather, dim3((unsigned)((4 * cnt + SNAP_WG - 1) / SNAP_WG)), dim3(SNAP_WG), 0, st, b, tdev, (int)cnt, hdev);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(recs.data(), hdev, 64 * cnt, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (size_t i = 0; i < cnt; ++i)
+                if (const char *e = snap_check_record(recs[i], table[i], h.total_bytes))
+                        return fail(ASLAM_ERR_ARG, "snapshot record " + std::to_string(i) + ": " + e);
+        return ASLAM_OK;
+}
+} // namespace
+
 int aslam_restore(aslam_ctx *c, const int32_t *records, const int32_t *trajs, int count, const void *blob, int64_t bytes, int is_device,
                   void *stream)
 {
@@ -1223,56 +1283,10 @@ int aslam_restore(aslam_ctx *c, const int32_t *records, const int32_t *trajs, in
 
         // ---- the headers, on the host
         SnapBlobHeader h;
-        int64_t table_end = 0;
         std::vector<uint64_t> table;
         std::vector<SnapRecHeader> recs;
-        if (!is_device)
-        {
-                int32_t cnt = 0;
-                if ((rc = aslam_snapshot_check(blob, bytes, nullptr, &cnt)) != ASLAM_OK)
-                        return rc;
-                std::memcpy(&h, b, 64);
-                table.resize(cnt), recs.resize(cnt);
-                for (int i = 0; i < cnt; ++i)
-                {
-                        std::memcpy(&table[i], b + 64 + 8 * (size_t)i, 8);
-                        std::memcpy(&recs[i], b + table[i], 64);
-                }
-        }
-        else
-        {
-                if (bytes >= 64)
-                {
-                        HIP_TRY(hipMemcpyAsync(&h, b, 64, hipMemcpyDeviceToHost, st));
-                        HIP_TRY(hipStreamSynchronize(st));
-                }
-                if (const char *e = snap_check_header(h, bytes, &table_end))
-                        return fail(ASLAM_ERR_ARG, std::string("snapshot: ") + e);
-                const size_t cnt = h.count;
-                table.resize(cnt), recs.resize(cnt);
-                if (cnt)
-                {
-                        HIP_TRY(hipMemcpyAsync(table.data(), b + 64, 8 * cnt, hipMemcpyDeviceToHost, st));
-                        HIP_TRY(hipStreamSynchronize(st));
-                        for (size_t i = 0; i < cnt; ++i)
-                                if (const char *e = snap_check_offset(table[i], table_end, h.total_bytes))
-                                        return fail(ASLAM_ERR_ARG, "snapshot record " + std::to_string(i) + ": " + e);
-                        // one gather launch through the validated table, one copy
-                        const size_t tbytes = (size_t)snap_pad64(8 * (int64_t)cnt);
-                        if ((rc = snap_reserve(c, dbytes + tbytes + 64 * cnt)) != ASLAM_OK)
-                                return rc;
-                        uint64_t *tdev = reinterpret_cast<uint64_t *>(c->snap_dev + dbytes);
-                        SnapRecHeader *hdev = reinterpret_cast<SnapRecHeader *>(c->snap_dev + dbytes + tbytes);
-                        HIP_TRY(hipMemcpyAsync(tdev, table.data(), 8 * cnt, hipMemcpyHostToDevice, st));
-                        hipLaunchKernelGGL(snapshot_gather, dim3((unsigned)((4 * cnt + SNAP_WG - 1) / SNAP_WG)), dim3(SNAP_WG), 0, st, b, tdev, (int)cnt, hdev);
-                        HIP_TRY(hipGetLastError());
-                        HIP_TRY(hipMemcpyAsync(recs.data(), hdev, 64 * cnt, hipMemcpyDeviceToHost, st));
-                        HIP_TRY(hipStreamSynchronize(st));
-                        for (size_t i = 0; i < cnt; ++i)
-                                if (const char *e = snap_check_record(recs[i], table[i], h.total_bytes))
-                                        return fail(ASLAM_ERR_ARG, "snapshot record " + std::to_string(i) + ": " + e);
-                }
-        }
+        if ((rc = snap_headers(c, blob, bytes, is_device, st, dbytes, h, table, recs)) != ASLAM_OK)
+                return rc;
 
         // ---- the request against the context
         if ((int32_t)h.filter != c->cfg.filter)
@@ -1319,6 +1333,173 @@ int aslam_restore(aslam_ctx *c, const int32_t *records, const int32_t *trajs, in
         HIP_TRY(hipGetLastError());
         for (int i = 0; i < count; ++i) // (nor the mask of the last callback)
                 HIP_TRY(hipMemsetAsync(c->dv.sighted + (size_t)desc[i].slot * (c->NP / 2), 0, (size_t)c->NP / 2, st));
+        return ASLAM_OK;
+}
+
+/* ---- joining maps (join.h) -------------------------------------------------------------------------------------------- */
+int aslam_join_maps(aslam_ctx *c, const int32_t *records, const int32_t *trajs, int count, const void *blob, int64_t bytes, int is_device,
+                    const aslam_frame *frames, const uint8_t *select, int ld, int32_t *joined_out, void *stream)
+{
+        static_assert(sizeof(aslam_frame) == 96, "aslam_frame is part of the C ABI");
+        const std::string who = "aslam_join_maps: ";
+        if (!c || !blob)
+                return fail(ASLAM_ERR_ARG, who + "null argument");
+        const int B = c->cfg.batch;
+        if (count < 1 || count > B)
+                return fail(ASLAM_ERR_ARG, who + "count must be 1 .. batch (a slot is joined into once)");
+        if (is_device && ((uintptr_t)blob & 15))
+                return fail(ASLAM_ERR_ARG, who + "a device blob must be 16-byte aligned");
+        int rc = sync_ctx(c);
+        if (rc != ASLAM_OK)
+                return rc;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+
+        // ---- the headers, on the host (the blob's filter kind is not compared: a map is X and P)
+        SnapBlobHeader h;
+        std::vector<uint64_t> table;
+        std::vector<SnapRecHeader> recs;
+        if ((rc = snap_headers(c, blob, bytes, is_device, st, 0, h, table, recs)) != ASLAM_OK)
+                return rc;
+
+        // ---- the request: indices, slots, the selection and the frames
+        struct Entry
+        {
+                int rec, slot;
+                std::vector<int32_t> idx;
+        };
+        std::vector<Entry> ent(count);
+        std::vector<char> seen(B, 0);
+        for (int i = 0; i < count; ++i)
+        {
+                const int r = records ? records[i] : i, t = trajs ? trajs[i] : i;
+                if (r < 0 || (size_t)r >= recs.size())
+                        return fail(ASLAM_ERR_ARG, who + "records[" + std::to_string(i) + "]: record index out of range");
+                if (t < 0 || t >= B)
+                        return fail(ASLAM_ERR_ARG, who + "trajs[" + std::to_string(i) + "]: trajectory index out of range");
+                if (seen[t]++)
+                        return fail(ASLAM_ERR_ARG, who + "trajs[" + std::to_string(i) + "]: a slot is named twice");
+                const int L_B = (recs[r].n - 3) / 2;
+                if (select && ld < L_B)
+                        return fail(ASLAM_ERR_ARG, who + "ld is smaller than the " + std::to_string(L_B) + " landmarks of the record of entry " + std::to_string(i));
+                ent[i].rec = r, ent[i].slot = t;
+                for (int k = 0; k < L_B; ++k)
+                        if (!select || select[(size_t)i * ld + k])
+                                ent[i].idx.push_back(k);
+                if (!frames)
+                        continue;
+                const aslam_frame &f = frames[i];
+                const std::string fr = who + "frames[" + std::to_string(i) + "]";
+                if (!std::isfinite(f.tx) || !std::isfinite(f.ty) || !std::isfinite(f.phi))
+                        return fail(ASLAM_ERR_ARG, fr + (!std::isfinite(f.tx) ? ".tx" : !std::isfinite(f.ty) ? ".ty" : ".phi") + " is not finite");
+                for (int k = 0; k < 9; ++k)
+                        if (!std::isfinite(f.cov[k]))
+                                return fail(ASLAM_ERR_ARG, fr + ".cov[" + std::to_string(k) + "] is not finite");
+                if (f.cov[1] != f.cov[3] || f.cov[2] != f.cov[6] || f.cov[5] != f.cov[7])
+                        return fail(ASLAM_ERR_ARG, fr + ".cov is not exactly symmetric");
+                for (int k = 0; k < 9; k += 4)
+                        if (f.cov[k] < 0.0)
+                                return fail(ASLAM_ERR_ARG, fr + ".cov[" + std::to_string(k) + "] is negative");
+        }
+
+        // ---- n, the init flags and the list sizes of the batch: the one copy and the one synchronisation of the call
+        const size_t mbytes = (size_t)snap_pad64((int64_t)sizeof(JoinMeta) * B);
+        if ((rc = snap_reserve(c, mbytes)) != ASLAM_OK)
+                return rc;
+        const DevView &dv = c->dv;
+        hipLaunchKernelGGL(join_meta, dim3((unsigned)((B + PRUNE_WAVE - 1) / PRUNE_WAVE)), dim3(PRUNE_WAVE), 0, st, (const int *)dv.n, (const int *)dv.flags,
+                           (const int *)dv.sens_n, (const int *)dv.wait_n, B, reinterpret_cast<JoinMeta *>(c->snap_dev));
+        HIP_TRY(hipGetLastError());
+        std::vector<JoinMeta> meta((size_t)B);
+        HIP_TRY(hipMemcpyAsync(meta.data(), c->snap_dev, sizeof(JoinMeta) * B, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (const Entry &e : ent)
+        {
+                const JoinMeta &m = meta[e.slot];
+                if (m.n < 3 || !(m.n & 1) || m.n >= c->cfg.max_landmark_count || m.n > c->NP)
+                        return fail(ASLAM_ERR_STATE, who + "filter " + std::to_string(e.slot) + " has an invalid dimension");
+                if (m.flags & FLAG_INIT_X)
+                        return fail(ASLAM_ERR_STATE, who + "filter " + std::to_string(e.slot) + " has not run a callback yet (init_x is set: the first one "
+                                                                                                   "would overwrite X with Z)");
+        }
+        for (const Entry &e : ent)
+                if ((int64_t)meta[e.slot].n + 2 * (int64_t)e.idx.size() >= c->cfg.max_landmark_count)
+                        return fail(ASLAM_ERR_UNSUPPORTED, who + "filter " + std::to_string(e.slot) + ": state dimension " + std::to_string(meta[e.slot].n) + " + " +
+                                                                   std::to_string(2 * e.idx.size()) + " does not fit below the context's max_landmark_count");
+
+        // ---- the descriptors of the entries that join something (the others leave their slot untouched)
+        std::vector<SnapDesc> desc;
+        std::vector<JoinDesc> jdesc;
+        std::vector<int32_t> idx;
+        int n_max = 3;
+        for (int i = 0; i < count; ++i)
+        {
+                const Entry &e = ent[i];
+                if (joined_out)
+                        joined_out[i] = (int32_t)e.idx.size();
+                if (e.idx.empty())
+                        continue;
+                const JoinMeta &m = meta[e.slot];
+                const int n_new = m.n + 2 * (int)e.idx.size();
+                desc.push_back(SnapDesc{0, e.slot, n_new, std::min(std::max(m.sens_n, 0), dv.max_obs), std::min(std::max(m.wait_n, 0), dv.max_wait), {0, 0}});
+                JoinDesc j = {};
+                j.src_off = (int64_t)table[e.rec];
+                j.n_A = m.n, j.m = (int32_t)e.idx.size(), j.ld_B = recs[e.rec].n + 1, j.idx_off = (int32_t)idx.size();
+                j.c = 1.0, j.s = 0.0;
+                if (frames)
+                {
+                        const aslam_frame &f = frames[i];
+                        j.c = std::cos(f.phi), j.s = std::sin(f.phi), j.tx = f.tx, j.ty = f.ty;
+                        std::copy(f.cov, f.cov + 9, j.cov);
+                }
+                jdesc.push_back(j);
+                idx.insert(idx.end(), e.idx.begin(), e.idx.end());
+                n_max = std::max(n_max, n_new);
+        }
+        const int joined = (int)desc.size();
+        if (joined == 0)
+                return ASLAM_OK;
+        int64_t off = 64 + snap_pad64(8 * (int64_t)joined);
+        for (SnapDesc &d : desc)
+        {
+                d.off = off;
+                off += snap_pad64(snap_record_bytes(d.n, d.sens_n, d.wait_n));
+        }
+        const int64_t total = off;
+
+        // ---- staging: descriptors | join descriptors | index lists | a host blob's copy | the records; then pack, unpack, the sighting record
+        const size_t o_jd = (size_t)snap_pad64((int64_t)sizeof(SnapDesc) * joined);
+        const size_t o_idx = o_jd + sizeof(JoinDesc) * joined;
+        const size_t o_src = o_idx + (size_t)snap_pad64(4 * (int64_t)idx.size());
+        const size_t o_blob = o_src + (is_device ? 0 : (size_t)snap_pad64((int64_t)h.total_bytes));
+        if ((rc = snap_reserve(c, o_blob + (size_t)total)) != ASLAM_OK)
+                return rc;
+        char *sd = c->snap_dev;
+        HIP_TRY(hipMemcpy(sd, desc.data(), sizeof(SnapDesc) * joined, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(sd + o_jd, jdesc.data(), sizeof(JoinDesc) * joined, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(sd + o_idx, idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice));
+        const char *src = static_cast<const char *>(blob);
+        if (!is_device)
+        {
+                HIP_TRY(hipMemcpy(sd + o_src, blob, (size_t)h.total_bytes, hipMemcpyHostToDevice));
+                src = sd + o_src;
+        }
+        const SnapDesc *ddev = reinterpret_cast<const SnapDesc *>(sd);
+        const JoinDesc *jdev = reinterpret_cast<const JoinDesc *>(sd + o_jd);
+        char *out = sd + o_blob;
+        const SnapCtx sc = snap_ctx(c);
+        c->last_stream = st;
+        hipLaunchKernelGGL(join_pack, snap_grid((int64_t)n_max * (n_max + 1) / 2, joined), dim3(SNAP_WG), 0, st, sc, ddev, jdev,
+                           reinterpret_cast<const int32_t *>(sd + o_idx), joined, (uint32_t)c->cfg.filter, (uint64_t)total, src, out);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(snapshot_unpack, snap_grid((int64_t)c->NP * c->NP / 2, joined), dim3(SNAP_WG), 0, st, sc, ddev, joined, (const char *)out);
+        HIP_TRY(hipGetLastError());
+        // the new landmarks enter the sighting record as aslam_grow enters them; the clock and the old records stay
+        hipLaunchKernelGGL(sight_extend, dim3((unsigned)joined), dim3(PRUNE_WAVE), 0, st, ddev, jdev, c->NP, (const uint32_t *)dv.clock, dv.lm_seen,
+                           dv.lm_hits);
+        HIP_TRY(hipGetLastError());
+        // the mask of the last callback, as after aslam_remove_landmarks
+        for (const SnapDesc &q : desc)
+                HIP_TRY(hipMemsetAsync(dv.sighted + (size_t)q.slot * (c->NP / 2), 0, (size_t)c->NP / 2, st));
         return ASLAM_OK;
 }
 

@@ -3,6 +3,7 @@
 // Build: g++ -O2 -ffp-contract=off (the binary32 rounding points of the reference must not be fused),
 // linked against libaslam_core.so.
 #include "aslam_node.h"
+#include "../../../include/aslam_snapshot.h"
 
 #include <algorithm>
 #include <cmath>
@@ -276,6 +277,40 @@ int FilterNode::mergeLandmarks(const std::vector<std::pair<int, int>> &pairs, do
                 check(aslam_get_state(ctx, 0, param_X.data(), nullptr, nullptr), "aslam_get_state"); // (the constraint moved every entry of X)
         }
         return done;
+}
+
+// aslam_join_maps (aslam_snapshot.h) is bound weakly like aslam_merge_landmarks: a core without it refuses the call, at run time.
+extern "C" {
+int aslam_join_maps(aslam_ctx *, const int32_t *, const int32_t *, int, const void *, int64_t, int, const aslam_frame *, const uint8_t *, int, int32_t *,
+                    void *) __attribute__((weak));
+}
+
+int FilterNode::joinMap(const void *blob, int64_t bytes, int record, const double *frame12, const uint8_t *select, int select_len)
+{
+        if (!aslam_join_maps)
+                throw std::runtime_error("this core cannot join maps");
+        if (!blob)
+                throw std::runtime_error("joinMap: null blob");
+        aslam_frame f = {};
+        if (frame12)
+        {
+                f.tx = frame12[0], f.ty = frame12[1], f.phi = frame12[2];
+                std::copy(frame12 + 3, frame12 + 12, f.cov);
+        }
+        const int32_t rec = record, slot = 0;
+        int32_t joined = 0;
+        check(aslam_join_maps(ctx, &rec, &slot, 1, blob, bytes, 0, frame12 ? &f : nullptr, select, select ? select_len : 0, &joined, nullptr),
+              "aslam_join_maps"); // (the core checks everything and changes nothing when it refuses)
+        if (joined == 0)
+                return 0;
+        N += 2 * (uint32_t)joined;
+        param_X.resize(N);
+        param_Z.resize(N);
+        check(aslam_get_state(ctx, 0, param_X.data(), param_Z.data(), nullptr), "aslam_get_state"); // (the new X and the Z seeded from the pose)
+        lm_seen.resize((N - 3) / 2, sight_clock); // as updateNewLandmark enters a promoted landmark
+        lm_hits.resize((N - 3) / 2, 0);
+        lm_sighted.assign((N - 3) / 2, 0);
+        return joined;
 }
 
 int FilterNode::mergeDuplicates(double gate, double max_dist, double noise_var)
@@ -788,6 +823,21 @@ int aslam_node_merge_duplicates(aslam_node *n, double gate, double max_dist, dou
                 if (!n)
                         throw std::runtime_error("null argument");
                 return n->impl->mergeDuplicates(gate, max_dist, noise_var);
+        }
+        catch (const std::exception &e)
+        {
+                g_node_err = e.what();
+                return -1;
+        }
+}
+
+int aslam_node_join_map(aslam_node *n, const void *blob, int64_t bytes, int record, const double *frame12, const uint8_t *select, int select_len)
+{
+        try
+        {
+                if (!n)
+                        throw std::runtime_error("null argument");
+                return n->impl->joinMap(blob, bytes, record, frame12, select, select_len);
         }
         catch (const std::exception &e)
         {

@@ -152,6 +152,13 @@ class FilterNode
         /// by operation, so the selection is the device selector's), then mergeLandmarks; passes until one merges nothing, 4 at the most.
         /// Returns the landmarks merged.
         int mergeDuplicates(double gate, double max_dist, double noise_var = 0.0);
+        /// Join a foreign map (aslam_join_maps of aslam_snapshot.h): the landmarks of record `record` of the HOST snapshot blob, with their
+        /// covariance block, go behind this filter's state as an independent map.  frame12 (may be null: identity, zero covariance) holds
+        /// tx, ty, phi and the row-major 3 x 3 covariance of the transform source frame -> this filter's frame; select (may be null: every
+        /// landmark) holds select_len entries, one per landmark of the record.  The mirror's X and Z are read back, the new landmarks enter
+        /// lastSeen / hits as promoted ones do.  Returns the landmarks joined; throws where the core refuses (nothing has changed then: before
+        /// the first callback, no room below max_landmark_count, a malformed blob or frame).  Between two callbacks.
+        int joinMap(const void *blob, int64_t bytes, int record = 0, const double *frame12 = nullptr, const uint8_t *select = nullptr, int select_len = 0);
         /// Mahalanobis-gated association (aslam_gate_observations of aslam_core.h).  gate = 0, the default: off, updateZ associates by the
         /// reference's Euclidean rule alone.  gate > 0 (9.21: the 99 % point of chi-square with 2 degrees of freedom), once a landmark is mapped:
         /// updateZ asks the core for the gated landmark of every observation of the stored message in ONE call and copies the indices back (4
@@ -260,6 +267,9 @@ int aslam_node_remove_stale(aslam_node *n, uint32_t max_age);
 int aslam_node_merge_landmarks(aslam_node *n, const int32_t *pairs, int count, double noise_var);
 /* FilterNode::mergeDuplicates: the number of landmarks merged, or -1 with aslam_node_error(). */
 int aslam_node_merge_duplicates(aslam_node *n, double gate, double max_dist, double noise_var);
+/* FilterNode::joinMap: a host blob, frame12 = tx, ty, phi, cov[9] or NULL, select [select_len] or NULL; the number of landmarks joined, or -1
+ * with aslam_node_error(). */
+int aslam_node_join_map(aslam_node *n, const void *blob, int64_t bytes, int record, const double *frame12, const uint8_t *select, int select_len);
 /* FilterNode::setAssocGate (0 = off, the default): 0, or -1 with aslam_node_error() (a negative or NaN gate). */
 int aslam_node_set_assoc_gate(aslam_node *n, double gate);
 /* FilterNode::assocRejected: observations the gate dropped although the Euclidean rule would have associated them. */

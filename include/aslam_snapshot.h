@@ -78,6 +78,60 @@ int aslam_snapshot(aslam_ctx *ctx, const int32_t *trajs, int count, void *blob, 
 int aslam_restore(aslam_ctx *ctx, const int32_t *records, const int32_t *trajs, int count, const void *blob, int64_t bytes, int is_device,
                   void *stream);
 
+/* A rigid 2-D transform with its uncertainty: what takes a point of the source record's frame into the destination filter's frame. */
+typedef struct
+{
+        double tx, ty, phi; /* source frame -> destination frame: p' = t + R(phi) p */
+        double cov[9];      /* covariance of (tx, ty, phi), row-major 3 x 3 */
+} aslam_frame;              /* 96 bytes */
+
+/* JOIN MAPS: append the landmarks of record records[i] of the blob (NULL = i), with their full covariance block, behind the state of the
+ * running filter in slot trajs[i] of ctx (NULL = i), i < count.  records, trajs, count, blob, bytes, is_device and the blob's validation
+ * mean what they mean for aslam_restore -- a record may be named several times, a slot once -- except that the blob's filter kind is NOT
+ * compared with the context's: a map is X and P, so a UKF record joins into an EKF context and the reverse.
+ *
+ * Filter A = slot trajs[i] has dimension n_A, the record L_B landmarks.  The selected ones, in ascending source index k_0 < ... < k_{m-1},
+ * are those with select[i * ld + k] != 0 (host [count][ld]; entries at or beyond L_B are ignored; ld at least the largest L_B among the named
+ * records; select NULL = every landmark of the record).  frames: host [count], NULL = identity with zero covariance.  With c = cos(phi),
+ * s = sin(phi) taken once on the host in the call, R = [[c, -s], [s, c]], S = cov and l_p = (X_B[3 + 2 k_p], X_B[4 + 2 k_p]):
+ *
+ *   x'_p = tx + c lx - s ly          y'_p = ty + s lx + c ly
+ *   G_p  = [[1, 0, -s lx - c ly],
+ *           [0, 1,  c lx - s ly]]
+ *   B_pq = the 2 x 2 block (k_p, k_q) of the record's P, read from its LOWER triangle only (for p = q the upper entry is the lower one: the
+ *          source need not be exactly symmetric)
+ *   P'_pq = R B_pq R^T + G_p S G_q^T   for p >= q;   P'_qp = (P'_pq)^T, the same bits
+ *
+ * After the call filter A has dimension n_A + 2m.  X, Z and P at indices below n_A are what they were, bit for bit;
+ * X[n_A + 2p .. + 1] = (x'_p, y'_p); the new diagonal block of P is P', exactly symmetric; both cross blocks (old rows x new columns and
+ * the mirror) are +0.0 -- the two maps are taken as INDEPENDENT, and ensuring that is the caller's responsibility; the record's pose and its
+ * pose-landmark covariances are not used (the marginal of its landmarks).  Z[n_A + 2p .. + 1] is the reading A's own pose predicts for the
+ * new landmark: with dx = x'_p - X_A[0], dy = y'_p - X_A[1], sqrt(dx^2 + dy^2) and atan2(dy, dx) - X_A[2], the latter wrapped as the
+ * kernels' normalizeAngle wraps (fmod by 2 pi, then one step into [-pi, pi]) -- a joined landmark has zero innovation until it is sighted.
+ * All of this arithmetic is binary64, in ASLAM_F32 contexts too.
+ * Unchanged: A, both init flags, the status bits, the stored sensor message, the wait-list, the parameters, the sighting clock and the
+ * sighting records of the old landmarks (aslam_restore clears those two; a join does not).  The new landmarks enter the sighting record as
+ * aslam_grow enters them (last_seen = clock, hits = 0).  The last-callback innovation record and the sighted mask become what they are
+ * after aslam_remove_landmarks (NaN; zero).  The slot is a FRESH one of the larger dimension, as a restored slot is.  An entry with m = 0
+ * leaves its slot untouched bit for bit, and so does a filter that no entry names.  joined_out (host [count], may be NULL) receives m per
+ * entry.
+ *
+ * Everything is checked before any filter is written; a refused call leaves the context bit for bit as it was:
+ *   ASLAM_ERR_ARG          everything aslam_restore refuses about the blob, the indices and slot uniqueness; a select with ld below a named
+ *                          record's L_B; a frame with a non-finite field, a cov that is not exactly symmetric, or a negative cov diagonal
+ *                          (the message names the argument and the entry)
+ *   ASLAM_ERR_STATE        a destination whose init_x flag is still set: its first callback would overwrite X with Z (ekf.cpp:87-91)
+ *   ASLAM_ERR_UNSUPPORTED  n_A + 2m >= max_landmark_count for some entry (no status bit is set: this is a host request, not the growth path)
+ * The messages of the last two name the filter.
+ *
+ * Synchronises the context's last stream; the headers of a device blob come to the host as in aslam_restore; n, the flags and the list sizes
+ * of the batch come through ONE small device-to-host copy and one synchronisation of `stream`.  Then one pack launch, the unpack launch of
+ * aslam_restore and one launch for the sighting record are enqueued on `stream`, which becomes the context's last stream.  No P, of source or
+ * destination, crosses to the host.  A device blob must stay valid and unchanged until `stream` has passed the launches; a host blob is
+ * copied before the call returns. */
+int aslam_join_maps(aslam_ctx *ctx, const int32_t *records, const int32_t *trajs, int count, const void *blob, int64_t bytes, int is_device,
+                    const aslam_frame *frames, const uint8_t *select, int ld, int32_t *joined_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

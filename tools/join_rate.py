@@ -1,0 +1,256 @@
+#!/usr/bin/env python3
+"""What joining maps costs (aslam_join_maps, csrc/join.h), beside the two things it is made of: aslam_restore of the same filters at the final
+dimension, and the device-to-device copy rate of the machine.
+
+    python tools/join_rate.py [--reps 10] [--filters 256] [--out profiles/join.json] [--md profiles/join.md] [--err-over-bar X] [--bench-line S]
+    python tools/join_rate.py --from-json profiles/join.json      (rewrite the .md from recorded numbers, no GPU)
+
+One EKF fp32 context (P is binary64 in every context), max_landmark_count 1087, 256 filters at 448 landmarks (n = 899), each joining the 64
+landmarks of one record of a device blob under a general frame with a full covariance (n = 1027 afterwards).  Every step is a process of
+its own under its own time limit (a step that fails or runs out of time ends the tool; nothing is started behind it):
+    join      aslam_join_maps, timed between two device events on the default stream; the context is restored from a device snapshot
+              (untimed) before every repetition.  The call holds one device-to-host copy with a stream synchronisation (n and the flags of
+              the batch) and, for a device blob, the three of its headers, so the interval includes host round trips: the time the stream
+              is busy with the call.
+    restore   aslam_restore of the same 256 filters at n = 1027 from a device snapshot, timed the same way
+    copy      aslam_debug_snapshot_rate on the joined context: the pack launch, the unpack launch and a device-to-device copy of the blob
+No figure is a pass/fail condition anywhere; the files record what was measured."""
+import argparse
+import ctypes
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+CAP, L_A, L_B = 1087, 448, 64
+STEP_LIMIT_S = {"join": 240, "restore": 180, "copy": 180}
+
+
+def record(n, rng, max_obs=16, max_wait=16):
+    A = rng.normal(size=(n, n)) * 0.02
+    X = rng.uniform(-20, 20, n)
+    return dict(n=n, flags=0, status=0, A=np.array([1.0, 0.0]), X=X, Z=X.copy(), P=A @ A.T + np.eye(n) * 0.01,
+                sens=rng.normal(size=(max_obs, 2)).astype(np.float32), wait_rb=rng.normal(size=(max_wait, 2)).astype(np.float32),
+                wait_cnt=np.ones(max_wait, np.uint32))
+
+
+def context(B, n):
+    """the context with every filter at dimension n, and its device snapshot"""
+    import torch
+
+    from awesomeslam_amd import core as C
+    from awesomeslam_amd import snapshot
+
+    core = C.Core("ekf", CAP, batch=B, max_obs=16, max_wait=16, dtype=C.F32)
+    core.restore(snapshot.pack([record(n, np.random.default_rng(n))], "ekf"), records=[0] * B, trajs=list(range(B)))
+    full = torch.empty(core.snapshot_bytes(), dtype=torch.uint8, device="cuda")
+    core.snapshot(out=full)
+    torch.cuda.synchronize()
+    return core, full
+
+
+def timed(reps, before, f):
+    import time
+
+    import torch
+
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ms, wall = [], []
+    for r in range(-2, reps):
+        before()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        e0.record()
+        f()
+        e1.record()
+        torch.cuda.synchronize()
+        if r >= 0:
+            ms.append(e0.elapsed_time(e1))
+            wall.append((time.perf_counter() - t0) * 1e3)
+    return {"ms_median": float(np.median(ms)), "ms_min": float(np.min(ms)), "ms_max": float(np.max(ms)), "wall_ms_median": float(np.median(wall))}
+
+
+def source_and_frames(B):
+    import torch
+
+    from awesomeslam_amd import core as C
+    from awesomeslam_amd import snapshot
+
+    nB = 3 + 2 * L_B
+    src = torch.from_numpy(snapshot.pack([record(nB, np.random.default_rng(7), 0, 0)], "ekf")).cuda()
+    F = np.random.default_rng(8).standard_normal((3, 3)) * np.array([[0.02], [0.02], [0.005]])
+    cov = F @ F.T + np.diag([1e-5, 1e-5, 1e-6])
+    cov = np.tril(cov) + np.tril(cov, -1).T
+    frames = (C.Frame * B)(*(C.Frame.make((3.0, -2.0, 0.7, cov)) for _ in range(B)))
+    return src, frames
+
+
+def join_all(core, B, src, frames):
+    rec, slots = np.zeros(B, np.int32), np.arange(B, dtype=np.int32)
+    return core.join_maps_ptr(rec, slots, B, src.data_ptr(), src.numel(), True, frames)
+
+
+def step_join(B, reps):
+    from awesomeslam_amd import snapshot
+
+    nA, n = 3 + 2 * L_A, 3 + 2 * (L_A + L_B)
+    core, full = context(B, nA)
+    src, frames = source_and_frames(B)
+    NP = core.layout()[0]
+    res = timed(reps, lambda: core.restore(full, records=list(range(B))), lambda: join_all(core, B, src, frames))
+    assert [core.dim(b) for b in (0, B - 1)] == [n] * 2
+    got = snapshot.parse(core.snapshot(trajs=[B - 1]))[0]
+    assert np.array_equal(got["P"], got["P"].T) and np.isfinite(got["P"]).all() and np.linalg.eigvalsh(got["P"]).min() > 0
+    assert not got["P"][:nA, nA:].any()
+    # bytes of the two launches per filter: join_pack reads the old block and writes the record; snapshot_unpack reads the record and writes the
+    # padded slot (its scratch clear is counted by the copy step's info)
+    res.update(filters=B, n_A=nA, joined=L_B, n=n, padded_dim=NP, reps=reps,
+               pack_bytes=B * (8 * nA * nA + 8 * (n + 1) * (n + 2)), unpack_bytes=B * (8 * (n + 1) * (n + 2) + 8 * NP * NP))
+    core.close()
+    return res
+
+
+def step_restore(B, reps):
+    n = 3 + 2 * (L_A + L_B)
+    core, full = context(B, n)
+    res = timed(reps, lambda: None, lambda: core.restore(full, records=list(range(B))))
+    res.update(blob_bytes=int(full.numel()))
+    core.close()
+    return res
+
+
+def step_copy(B, reps):
+    import torch
+
+    from awesomeslam_amd import core as C
+
+    nA = 3 + 2 * L_A
+    core, _ = context(B, nA)
+    src, frames = source_and_frames(B)
+    join_all(core, B, src, frames)  # the joined context: what the copy is compared with
+    blob_bytes = core.snapshot_bytes()
+    buf = torch.empty(2 * blob_bytes, dtype=torch.uint8, device="cuda")
+    lib = C.core_lib()
+    lib.aslam_debug_snapshot_rate.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    ms = np.zeros((3, reps), np.float32)
+    info = (ctypes.c_int64 * 3)()
+    C._chk(lib.aslam_debug_snapshot_rate(core._h, buf.data_ptr(), buf.numel(), reps, ms.ctypes.data, info))
+    pack, unpack, copy = (float(np.median(ms[k])) for k in range(3))
+    core.close()
+    # a copy reads and writes every byte of the blob
+    return {"blob_bytes": blob_bytes, "snapshot_pack_ms": pack, "snapshot_unpack_ms": unpack, "copy_ms_median": copy,
+            "copy_TB_per_s": 2 * blob_bytes / (copy * 1e-3) / 1e12, "unpack_clear_bytes": int(info[2])}
+
+
+STEPS = {"join": step_join, "restore": step_restore, "copy": step_copy}
+
+
+def measure(B, reps):
+    out = {}
+    for name in STEPS:
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", name, "--filters", str(B), "--reps", str(reps)],
+                           stdout=subprocess.PIPE, timeout=STEP_LIMIT_S[name], check=True)
+        out[name] = json.loads(p.stdout.decode().strip().splitlines()[-1])
+    j, r, c = out["join"], out["restore"], out["copy"]
+    out["join_over_restore"] = j["ms_median"] / r["ms_median"]
+    moved = j["pack_bytes"] + j["unpack_bytes"] + c["unpack_clear_bytes"]
+    out["join_bytes"] = moved
+    out["join_TB_per_s"] = moved / (j["ms_median"] * 1e-3) / 1e12
+    out["join_over_copy_rate"] = out["join_TB_per_s"] / c["copy_TB_per_s"]
+    return out
+
+
+def write_md(path, res):
+    s = res["shape"]
+    j, r, c = s["join"], s["restore"], s["copy"]
+    ratio = res.get("err_over_bar")
+    ratio_txt = (f"The worst error / bar seen on the GPU over every case of `tests/test_gpu_join.py` is **{ratio:.3f}** (bar = max(32 x the spread of the "
+                 "binary64 reference against the long-double one, 64 x 2^-52)).") if ratio is not None else \
+        "The worst error / bar of the GPU tests was not recorded with this run."
+    bench = res.get("bench_line")
+    bench_txt = f"`bench.py` (default workload, the path this change does not touch): {bench}" if bench else \
+        "`bench.py` was not recorded with this run."
+    txt = f"""# Joining maps: what a call costs
+
+Written by `tools/join_rate.py` ({res['device']}); the numbers are in `join.json`.
+
+EKF fp32 context (P is binary64), max_landmark_count {CAP} (padded {j['padded_dim']}), {j['filters']} filters at {L_A} landmarks (n = {j['n_A']}), each joining
+the {j['joined']} landmarks of one record of a device blob under a general frame with a full covariance (n = {j['n']} afterwards), all in one call.
+Median of {j['reps']} repetitions between two device events on the default stream after 2 warm-up rounds; the context is restored (untimed) before
+each.  Every step ran in a process of its own.
+
+| | ms (median) | min .. max | host wall clock, ms |
+|---|---|---|---|
+| `aslam_join_maps`, {j['filters']} filters | {j['ms_median']:.2f} | {j['ms_min']:.2f} .. {j['ms_max']:.2f} | {j['wall_ms_median']:.2f} |
+| `aslam_restore` of the same {j['filters']} filters at n = {j['n']} (device blob) | {r['ms_median']:.2f} | {r['ms_min']:.2f} .. {r['ms_max']:.2f} | {r['wall_ms_median']:.2f} |
+
+Join / restore: **{s['join_over_restore']:.2f}**.  On the joined context `aslam_debug_snapshot_rate` times the pack launch at {c['snapshot_pack_ms']:.2f} ms, the
+unpack launch at {c['snapshot_unpack_ms']:.2f} ms and the device-to-device copy of the blob ({c['blob_bytes'] / 1e9:.2f} GB, read + written) at
+{c['copy_ms_median']:.2f} ms = {c['copy_TB_per_s']:.2f} TB/s.  The join's two large launches move {s['join_bytes'] / 1e9:.2f} GB for the batch (join_pack: the old block read,
+the record written; snapshot_unpack: the record read, the padded slot written, the scratch cleared); over the whole call, host round trips
+included, that is {s['join_TB_per_s']:.2f} TB/s = **{s['join_over_copy_rate']:.2f}** of the copy rate.
+
+How to read it.  A join is the header reads of a device blob (three small copies, each with a synchronisation, as in `aslam_restore`),
+`join_meta` with the call's one copy and synchronisation, three small host-to-device copies of descriptors, then `join_pack`,
+`snapshot_unpack` and `sight_extend`.  It is a restore (one unpack launch) with a pack launch in front of it: the call takes
+{j['ms_median'] - r['ms_median']:.2f} ms more than the restore, beside {c['snapshot_pack_ms']:.2f} ms for `snapshot_pack` of the same records, so `join_pack` runs at about the
+rate of the plain gather; the new block is {(2 * j['joined']) ** 2 / j['n'] ** 2 * 100:.1f} % of the entries written.
+
+Which structure was built, and why.  `join_pack` writes one complete staged record of `snapshot.h` per joined filter and the unchanged
+`snapshot_unpack` makes the slot a fresh one of the larger dimension (the shape of `prune.h`).  Growing in place would write only the new rows
+and columns, about a third of the bytes; it was not built because the slot would not be fresh -- zero padding, cleared scratch and the layout
+of every kernel family would need a second piece of code -- and because this is a maintenance call.  Inside `join_pack`, lanes on and below
+the diagonal of the new block read contiguous segments of two source rows; lanes above it read the mirrored entries, a column walk through a
+source block that stays in the L2 ({8 * (2 * j['joined']) ** 2 / 1e3:.0f} KB here).  No LDS transpose was built for that share of the traffic, and its cost was not
+measured separately.
+
+{ratio_txt}
+
+{bench_txt}
+
+This is a maintenance call, not a per-callback one; no figure here is a bar.
+"""
+    with open(path, "w") as f:
+        f.write(txt)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--filters", type=int, default=256)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "join.json"))
+    ap.add_argument("--md", default=os.path.join(ROOT, "profiles", "join.md"))
+    ap.add_argument("--err-over-bar", type=float, default=None, help="worst error / bar printed by tests/test_gpu_join.py (-s), recorded as given")
+    ap.add_argument("--bench-line", default=None, help="the rate of bench.py beside the parent commit's, recorded as given")
+    ap.add_argument("--from-json", default=None)
+    ap.add_argument("--step", choices=list(STEPS), default=None, help="run one step in this process and print its JSON (used by the tool itself)")
+    a = ap.parse_args()
+    if a.step:
+        print(json.dumps(STEPS[a.step](a.filters, a.reps)))
+        return
+    if a.from_json:
+        res = json.load(open(a.from_json))
+    else:
+        import torch
+
+        res = {"tool": "tools/join_rate.py", "device": torch.cuda.get_device_name(0),
+               "timing": "device events around aslam_join_maps / aslam_restore (device blobs, default stream), median of reps after 2 warm-up rounds; "
+                         "aslam_debug_snapshot_rate on the joined context; every step a process of its own under a time limit",
+               "shape": measure(a.filters, a.reps)}
+    for k, v in (("err_over_bar", a.err_over_bar), ("bench_line", a.bench_line)):
+        if v is not None:
+            res[k] = v
+    with open(a.from_json or a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    write_md(a.md, res)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
