@@ -33,6 +33,7 @@ CORE_SYMBOLS = (
     "aslam_sighted_update_enable", "aslam_get_sighted", "aslam_ekf_step_sighted", "aslam_ekf_step_batch_sighted",
     "aslam_merge_landmarks", "aslam_select_duplicates",
     "aslam_gate_observations",
+    "aslam_set_replay_gate", "aslam_get_replay_gate", "aslam_get_assoc_rejected",
 )
 NODE_SYMBOLS = (
     "aslam_node_create", "aslam_node_create_at", "aslam_node_destroy", "aslam_node_error", "aslam_node_sensor", "aslam_node_odom",
@@ -212,6 +213,9 @@ def core_lib():
         L.aslam_merge_landmarks.argtypes = [vp, vp, ci, ci, cd, vp, vp]
         L.aslam_select_duplicates.argtypes = [vp, pd, pd, vp, ci, vp]
         L.aslam_gate_observations.argtypes = [vp, vp, ci, ci, ctypes.POINTER(ctypes.c_int32), pd, vp, vp, vp]
+        L.aslam_set_replay_gate.argtypes = [vp, ci, cd]
+        L.aslam_get_replay_gate.argtypes = [vp, ci, pd]
+        L.aslam_get_assoc_rejected.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_uint64)]
         pb = ctypes.POINTER(ctypes.c_uint8)
         L.aslam_sighted_update_enable.argtypes = [vp, ci]
         L.aslam_get_sighted.argtypes = [vp, ci, pb, ci, pi]
@@ -889,15 +893,35 @@ class Core:
         _chk(core_lib().aslam_gate_observations(self._h, obs_ptr, int(ldo), 1 if is_device else 0, _ptr(k, ctypes.c_int32), _ptr(g, ctypes.c_double),
                                                 assoc_ptr, mdist_ptr, stream))
 
+    # ---- the same gate inside the replay seam (aslam_set_replay_gate)
+    def set_replay_gate(self, gate, traj=None):
+        """Associate by the Mahalanobis gate inside replay() / replay_stats() for filter `traj` (None: every filter): 0 = the Euclidean rule (the
+        default), > 0 (inf allowed) = accept the landmark of smallest m if m < gate, drop what only the Euclidean rule would have matched (counted:
+        assoc_rejected), hand the rest to the wait-list.  Kept by reset(), not carried by snapshots.  Synchronises.  AslamError on a NaN or
+        negative gate or a bad `traj`."""
+        _chk(core_lib().aslam_set_replay_gate(self._h, -1 if traj is None else int(traj), float(gate)))
+
+    def replay_gate(self, traj=0):
+        """The gate of filter `traj` as the kernels read it (synchronises)."""
+        g = ctypes.c_double()
+        _chk(core_lib().aslam_get_replay_gate(self._h, int(traj), ctypes.byref(g)))
+        return g.value
+
+    def assoc_rejected(self, traj=0):
+        """Observations of filter `traj` the gate has dropped since the last reset() / restore of the slot (synchronises)."""
+        k = ctypes.c_uint64()
+        _chk(core_lib().aslam_get_assoc_rejected(self._h, int(traj), ctypes.byref(k)))
+        return int(k.value)
+
     def layout(self):
         npad, nbytes = ctypes.c_int(), ctypes.c_int64()
         _chk(core_lib().aslam_get_layout(self._h, ctypes.byref(npad), ctypes.byref(nbytes)))
         return npad.value, nbytes.value
 
     def kernel_info(self):
-        name = ctypes.create_string_buffer(192)
+        name = ctypes.create_string_buffer(320)
         g, b, l = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        _chk(core_lib().aslam_kernel_info(self._h, name, 192, ctypes.byref(g), ctypes.byref(b), ctypes.byref(l)))
+        _chk(core_lib().aslam_kernel_info(self._h, name, 320, ctypes.byref(g), ctypes.byref(b), ctypes.byref(l)))
         return {"name": name.value.decode(), "grid": g.value, "block": b.value, "lds_bytes": l.value}
 
     def launch_info(self):

@@ -84,6 +84,9 @@ struct aslam_ctx
         bool innov_on = false;
         // aslam_sighted_update_enable: the EKF update takes the rows of the landmarks sighted in the callback alone (dv.sighted); off by default
         bool sighted_on = false;
+        // aslam_set_replay_gate: the host copy of dv.gate ([batch] doubles in HBM).  Some gate > 0: the replay seam launches the GATED instantiations
+        std::vector<double> gates;
+        bool gated() const { return std::any_of(gates.begin(), gates.end(), [](double g) { return g > 0.0; }); }
         // aslam_set_params: the host copy of dv.prm ([batch] records in HBM); aslam_grow and init_state read p0_landmark / p0_pose from it
         std::vector<aslam_params> params;
         aslam_params *params_dev = nullptr;
@@ -266,6 +269,7 @@ int init_state(aslam_ctx *c)
         HIP_TRY(hipMemset(d.lm_seen, 0, sizeof(uint32_t) * B * (NP / 2)));
         HIP_TRY(hipMemset(d.lm_hits, 0, sizeof(uint32_t) * B * (NP / 2)));
         HIP_TRY(hipMemset(d.sighted, 0, sizeof(uint8_t) * B * (NP / 2)));
+        HIP_TRY(hipMemset(d.rejected, 0, sizeof(*d.rejected) * B)); // (the gates stay, like the parameters)
         std::vector<int> n(B, 3), fl(B, FLAG_INIT_X | FLAG_INIT_Z);
         std::vector<double> A(2 * B, 0.0);
         for (size_t b = 0; b < B; ++b)
@@ -308,19 +312,32 @@ int launch(aslam_ctx *c, int grid, int64_t t0, int nsteps, double *poses, int32_
 #if ASLAM_HAVE_UKF
         if (c->large && c->cfg.filter == ASLAM_UKF)
         {
+                c->lh.gated = c->gated();
                 HIP_TRY(launch_ukf_large<MODE>(c->lh, c->dv, c->lv64, c->ukfl, c->skipped, t0, nsteps, poses, dims, sa, st, sv));
                 return ASLAM_OK;
         }
 #endif
+        // aslam_set_replay_gate: the GATED instantiations, in the replay seam of a context with some gate > 0 alone; every other launch is what it was
+        const bool gated = MODE == MODE_REPLAY && c->gated();
         if (c->large)
                 return with_large_view(c, [&](auto &lv) -> int {
                         c->lh.sighted = c->sighted_on;
+                        c->lh.gated = gated;
                         HIP_TRY(launch_large<MODE>(c->lh, c->dv, lv, c->skipped, t0, nsteps, poses, dims, sa, st, sv));
                         return ASLAM_OK;
                 });
         if (c->cfg.filter == ASLAM_EKF)
                 return with_NT(c->NT, [&](auto nt) {
                         constexpr int NT = decltype(nt)::value;
+                        if constexpr (MODE == MODE_REPLAY)
+                        {
+                                if (gated && c->sighted_on)
+                                        return sv.any() ? launch_small<SmallLayout<NT>>(ekf_small_kernel<NT, MODE, true, true, true>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv)
+                                                        : launch_small<SmallLayout<NT>>(ekf_small_kernel<NT, MODE, false, true, true>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv);
+                                if (gated)
+                                        return sv.any() ? launch_small<SmallLayout<NT>>(ekf_small_kernel<NT, MODE, true, false, true>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv)
+                                                        : launch_small<SmallLayout<NT>>(ekf_small_kernel<NT, MODE, false, false, true>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv);
+                        }
                         if (c->sighted_on) // the information-form instantiations (ekf_small.h); off: exactly the launches below
                                 return sv.any() ? launch_small<SmallLayout<NT>>(ekf_small_kernel<NT, MODE, true, true>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv)
                                                 : launch_small<SmallLayout<NT>>(ekf_small_kernel<NT, MODE, false, true>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv);
@@ -331,6 +348,12 @@ int launch(aslam_ctx *c, int grid, int64_t t0, int nsteps, double *poses, int32_
         if (c->cfg.filter == ASLAM_UKF)
                 return with_NT(c->NT, [&](auto nt) {
                         constexpr int NT = decltype(nt)::value;
+                        if constexpr (MODE == MODE_REPLAY)
+                        {
+                                if (gated)
+                                        return sv.any() ? launch_small<UkfLayout<NT>>(ukf_small_kernel<NT, MODE, true, true>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv, c->ukf)
+                                                        : launch_small<UkfLayout<NT>>(ukf_small_kernel<NT, MODE, false, true>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv, c->ukf);
+                        }
                         return sv.any() ? launch_small<UkfLayout<NT>>(ukf_small_kernel<NT, MODE, true>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv, c->ukf)
                                         : launch_small<UkfLayout<NT>>(ukf_small_kernel<NT, MODE, false>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv, c->ukf);
                 });
@@ -460,7 +483,8 @@ int aslam_create(const aslam_config *cfg, aslam_ctx **out)
         for_each_array(d, [&](auto *&p, size_t per, bool) {
                 if (large && same_slot(p, d.P))
                         take_large();
-                else if (same_slot(p, d.clock) || same_slot(p, d.lm_seen) || same_slot(p, d.lm_hits) || same_slot(p, d.sighted))
+                else if (same_slot(p, d.clock) || same_slot(p, d.lm_seen) || same_slot(p, d.lm_hits) || same_slot(p, d.sighted) || same_slot(p, d.gate) ||
+                         same_slot(p, d.rejected))
                         rc = rc == ASLAM_OK ? dev_alloc(c, &p, B * per, c->owned, false) : rc; // (bookkeeping, outside the reported bytes)
                 else
                         take(p, per);
@@ -470,6 +494,7 @@ int aslam_create(const aslam_config *cfg, aslam_ctx **out)
         d.step_in = c->step_in;
         c->params_dev = const_cast<aslam_params *>(d.prm);
         c->params.assign(B, aslam_params ASLAM_PARAMS_DEFAULT_INIT);
+        c->gates.assign(B, 0.0); // (dev_alloc zeroes dv.gate: the Euclidean rule)
         if (rc == ASLAM_OK && hipMemcpy(c->params_dev, c->params.data(), sizeof(aslam_params) * B, hipMemcpyHostToDevice) != hipSuccess)
                 rc = fail(ASLAM_ERR_HIP, "hipMemcpy of the default parameters failed");
 #ifdef ASLAM_STAMPS
@@ -567,6 +592,51 @@ int aslam_set_params(aslam_ctx *c, int traj, const aslam_params *p)
         const std::vector<aslam_params> recs(count, *p);
         HIP_TRY(hipMemcpy(c->params_dev + first, recs.data(), sizeof(aslam_params) * count, hipMemcpyHostToDevice));
         std::copy(recs.begin(), recs.end(), c->params.begin() + first); // (behind the copy: the host copy never disagrees with what the kernels read)
+        return ASLAM_OK;
+}
+
+int aslam_set_replay_gate(aslam_ctx *c, int traj, double gate)
+{
+        if (!(gate >= 0.0)) // (a NaN fails the comparison)
+                return fail(ASLAM_ERR_ARG, "aslam_set_replay_gate: gate must be 0 (the Euclidean rule) or positive (infinity allowed), not negative or NaN");
+        if (!c)
+                return fail(ASLAM_ERR_ARG, "aslam_set_replay_gate: null context");
+        if (traj < -1 || traj >= c->cfg.batch)
+                return fail(ASLAM_ERR_ARG, "aslam_set_replay_gate: traj out of range (-1 = every filter)");
+        int rc = sync_ctx(c);
+        if (rc != ASLAM_OK)
+                return rc;
+        const size_t first = traj < 0 ? 0 : (size_t)traj, count = traj < 0 ? (size_t)c->cfg.batch : 1;
+        const std::vector<double> g(count, gate);
+        HIP_TRY(hipMemcpy(c->dv.gate + first, g.data(), sizeof(double) * count, hipMemcpyHostToDevice));
+        std::copy(g.begin(), g.end(), c->gates.begin() + first); // (behind the copy: the host copy never disagrees with what the kernels read)
+        return ASLAM_OK;
+}
+
+int aslam_get_replay_gate(aslam_ctx *c, int traj, double *gate)
+{
+        int rc = check_traj(c, traj);
+        if (rc != ASLAM_OK)
+                return rc;
+        if (!gate)
+                return fail(ASLAM_ERR_ARG, "aslam_get_replay_gate: null gate");
+        if ((rc = sync_ctx(c)) != ASLAM_OK)
+                return rc;
+        HIP_TRY(hipMemcpy(gate, c->dv.gate + traj, sizeof(double), hipMemcpyDeviceToHost)); // (what the kernels read)
+        return ASLAM_OK;
+}
+
+int aslam_get_assoc_rejected(aslam_ctx *c, int traj, uint64_t *count)
+{
+        int rc = check_traj(c, traj);
+        if (rc != ASLAM_OK)
+                return rc;
+        if (!count)
+                return fail(ASLAM_ERR_ARG, "aslam_get_assoc_rejected: null count");
+        if ((rc = sync_ctx(c)) != ASLAM_OK)
+                return rc;
+        static_assert(sizeof(*c->dv.rejected) == sizeof(uint64_t), "the counter is 64 bits");
+        HIP_TRY(hipMemcpy(count, c->dv.rejected + traj, sizeof(uint64_t), hipMemcpyDeviceToHost));
         return ASLAM_OK;
 }
 
@@ -1331,8 +1401,11 @@ int aslam_restore(aslam_ctx *c, const int32_t *records, const int32_t *trajs, in
         hipLaunchKernelGGL(sight_clear, dim3((unsigned)count), dim3(PRUNE_WAVE), 0, st, reinterpret_cast<const SnapDesc *>(c->snap_dev), c->NP,
                            c->dv.clock, c->dv.lm_seen, c->dv.lm_hits);
         HIP_TRY(hipGetLastError());
-        for (int i = 0; i < count; ++i) // (nor the mask of the last callback)
+        for (int i = 0; i < count; ++i) // (nor the mask of the last callback, nor the count of gated-out observations; the slot's gate stays)
+        {
                 HIP_TRY(hipMemsetAsync(c->dv.sighted + (size_t)desc[i].slot * (c->NP / 2), 0, (size_t)c->NP / 2, st));
+                HIP_TRY(hipMemsetAsync(c->dv.rejected + desc[i].slot, 0, sizeof(*c->dv.rejected), st));
+        }
         return ASLAM_OK;
 }
 
@@ -2182,7 +2255,7 @@ int aslam_kernel_info(aslam_ctx *c, char *name, int name_cap, int *grid, int *bl
 {
         if (!c)
                 return fail(ASLAM_ERR_ARG, "null context");
-        char buf[192];
+        char buf[320];
         size_t lds = 0;
         if (c->large)
         {
@@ -2205,22 +2278,30 @@ int aslam_kernel_info(aslam_ctx *c, char *name, int name_cap, int *grid, int *bl
                         std::snprintf(buf, sizeof(buf), "large_trsm_pipe<17> + large_syrk_bf16x3 (%d-launch chain per callback: multi-workgroup Cholesky)", plan.launches);
                 else
                         std::snprintf(buf, sizeof(buf), "large_update_panel<double> (%d-launch chain per callback, %d stream groups)", plan.launches, c->lh.knobs.groups);
-                lds = LargeLds::bytes(c->NP);
+                lds = c->gated() ? LargeLds::bytes_gated(c->NP) : LargeLds::bytes(c->NP);
                 if (c->sighted_on && c->cfg.filter == ASLAM_EKF)
                 {
                         const std::string with = std::string("large_build_GS<T,sighted> + ") + buf;
                         std::snprintf(buf, sizeof(buf), "%s", with.c_str());
                 }
+                if (c->gated()) // (the replay seam's front end)
+                {
+                        const std::string with = std::string(c->cfg.filter == ASLAM_EKF ? "large_frontend_kernel<T,gated> + " : "ukf_large_frontend_kernel<gated> + ") + buf;
+                        std::snprintf(buf, sizeof(buf), "%s", with.c_str());
+                }
         }
         else if (c->cfg.filter == ASLAM_EKF)
         {
-                std::snprintf(buf, sizeof(buf), c->sighted_on ? "ekf_small_kernel<%d,0,false,true>" : "ekf_small_kernel<%d,0>", c->NT);
+                if (c->gated())
+                        std::snprintf(buf, sizeof(buf), c->sighted_on ? "ekf_small_kernel<%d,0,false,true,true>" : "ekf_small_kernel<%d,0,false,false,true>", c->NT);
+                else
+                        std::snprintf(buf, sizeof(buf), c->sighted_on ? "ekf_small_kernel<%d,0,false,true>" : "ekf_small_kernel<%d,0>", c->NT);
                 lds = with_NT(c->NT, [](auto nt) -> size_t { return SmallLayout<decltype(nt)::value>::total; });
         }
 #if ASLAM_HAVE_UKF
         else
         {
-                std::snprintf(buf, sizeof(buf), "ukf_small_kernel<%d,0>", c->NT);
+                std::snprintf(buf, sizeof(buf), c->gated() ? "ukf_small_kernel<%d,0,false,true>" : "ukf_small_kernel<%d,0>", c->NT);
                 lds = with_NT(c->NT, [](auto nt) -> size_t { return UkfLayout<decltype(nt)::value>::total; });
         }
 #endif

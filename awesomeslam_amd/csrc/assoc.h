@@ -16,6 +16,7 @@
 // here to what a padded row holds (the landmark count).  The whole-wave exchange sits outside every lane-dependent branch.
 #pragma once
 
+#include "gate_math.h"
 #include "prune.h"
 
 namespace aslam
@@ -23,6 +24,7 @@ namespace aslam
 constexpr int ASSOC_WG = 256;     // 4 waves
 constexpr int ASSOC_LMAX = 542;   // landmarks of the largest state a context accepts: (1087 - 3) / 2
 constexpr int ASSOC_LPAD = 544;
+static_assert(PRUNE_WAVE == 64, "gate_math.h deals landmarks to the 64 lanes of a wave");
 
 /// grid: filters, block: ASSOC_WG.  obs [batch][ldo][2] f32 (range, bearing), n_obs, gate [batch]; assoc [batch][ldo] i32, mdist [batch][ldo]
 /// f64 or null.  assoc[b][j] = the valid landmark of smallest m if that m < gate[b], else -1; mdist[b][j] = that smallest m, +inf without a
@@ -32,7 +34,7 @@ __global__ __launch_bounds__(ASSOC_WG) void assoc_gate(const double *__restrict_
                                                        const int32_t *__restrict__ n_obs, const double *__restrict__ gate,
                                                        int32_t *__restrict__ assoc, double *__restrict__ mdist)
 {
-        __shared__ double s_rh[ASSOC_LPAD], s_bh[ASSOC_LPAD], s_00[ASSOC_LPAD], s_10[ASSOC_LPAD], s_11[ASSOC_LPAD], s_det[ASSOC_LPAD];
+        __shared__ double s_tab[6 * ASSOC_LPAD]; // rh, bh, s00, s10, s11, det (gate_math.h: the arithmetic is shared with the replay front end)
         const int b = blockIdx.x, tid = threadIdx.x, lane = tid % PRUNE_WAVE;
         const int L = prune_landmarks(n[b], NP, ASSOC_LMAX);
         const double *x = X + (size_t)b * NP;
@@ -41,55 +43,20 @@ __global__ __launch_bounds__(ASSOC_WG) void assoc_gate(const double *__restrict_
         const double rr = prm[b].r_range, rb = prm[b].r_bearing;
         for (int k = tid; k < L; k += ASSOC_WG)
         {
-                const int a0 = 3 + 2 * k, a1 = a0 + 1;
-                const double dx = x[a0] - px, dy = x[a1] - py;
-                const double q = dx * dx + dy * dy;
-                const double rh = sqrt(q);
-                const double h[2][5] = {{-dx / rh, -dy / rh, 0.0, dx / rh, dy / rh}, {dy / q, -dx / q, -1.0, -dy / q, dx / q}};
-                // P5 from the lower triangle: rows and columns 0, 1, 2, a0, a1 (ascending, so row >= column names a lower-triangle entry)
-                const int idx[5] = {0, 1, 2, a0, a1};
-                double p[5][5];
-#pragma unroll
-                for (int i = 0; i < 5; ++i)
-#pragma unroll
-                        for (int j = 0; j <= i; ++j)
-                                p[i][j] = p[j][i] = Pb[(size_t)idx[i] * NP + idx[j]];
-                double t[2][5];
-#pragma unroll
-                for (int r = 0; r < 2; ++r)
-#pragma unroll
-                        for (int j = 0; j < 5; ++j)
-                        {
-                                double v = 0.0;
-#pragma unroll
-                                for (int i = 0; i < 5; ++i)
-                                        v = fma(h[r][i], p[i][j], v);
-                                t[r][j] = v;
-                        }
-                double S00 = 0.0, S10 = 0.0, S11 = 0.0;
-#pragma unroll
-                for (int j = 0; j < 5; ++j)
-                {
-                        S00 = fma(t[0][j], h[0][j], S00);
-                        S10 = fma(t[1][j], h[0][j], S10);
-                        S11 = fma(t[1][j], h[1][j], S11);
-                }
-                const double s00 = S00 + rr, s11 = S11 + rb, s10 = S10;
-                const double det = s00 * s11 - s10 * s10;
-                const bool valid = q > 0.0 && s00 > 0.0 && det > 0.0;
-                s_rh[k] = rh;
-                s_bh[k] = atan2(dy, dx) - th;
-                s_00[k] = s00;
-                s_10[k] = s10;
-                s_11[k] = s11;
-                s_det[k] = valid ? det : 0.0;
+                const int a0 = 3 + 2 * k;
+                const GateLandmark g = gate_landmark(px, py, th, x[a0], x[a0 + 1], a0, rr, rb, [&](int i, int j) { return Pb[(size_t)i * NP + j]; });
+                s_tab[k] = g.rh;
+                s_tab[ASSOC_LPAD + k] = g.bh;
+                s_tab[2 * ASSOC_LPAD + k] = g.s00;
+                s_tab[3 * ASSOC_LPAD + k] = g.s10;
+                s_tab[4 * ASSOC_LPAD + k] = g.s11;
+                s_tab[5 * ASSOC_LPAD + k] = g.det;
         }
         __syncthreads();
         const int wave = __builtin_amdgcn_readfirstlane(tid / PRUNE_WAVE);
         const int no = min(max(n_obs[b], 0), ldo);
         const double g = gate[b];
         const double inf = __builtin_inf();
-        const double two_pi = 6.283185307179586; // 2 pi rounded to binary64
         for (int j = wave; j < ldo; j += ASSOC_WG / PRUNE_WAVE) // (j is the same in every lane of a wave)
         {
                 double best = inf;
@@ -97,24 +64,9 @@ __global__ __launch_bounds__(ASSOC_WG) void assoc_gate(const double *__restrict_
                 if (j < no)
                 {
                         const float2 o = *reinterpret_cast<const float2 *>(obs + ((size_t)b * ldo + j) * 2);
-                        const double r = (double)o.x, beta = (double)o.y;
-                        for (int k = lane; k < L; k += PRUNE_WAVE)
-                        {
-                                const double det = s_det[k];
-                                const double v0 = r - s_rh[k];
-                                const double v1 = remainder(beta - s_bh[k], two_pi);
-                                const double m = (s_11[k] * v0 * v0 - 2.0 * s_10[k] * v0 * v1 + s_00[k] * v1 * v1) / det;
-                                if (det > 0.0 && m < best) // (a NaN m is skipped; k ascends in a lane: the first of equal minima stays)
-                                        best = m, bk = k;
-                        }
+                        gate_scan_lane(s_tab, ASSOC_LPAD, L, lane, (double)o.x, (double)o.y, best, bk);
                 }
-                for (int d = PRUNE_WAVE / 2; d >= 1; d >>= 1)
-                {
-                        const double om = __shfl_xor(best, d);
-                        const int ok = __shfl_xor(bk, d);
-                        if (ok >= 0 && (bk < 0 || om < best || (om == best && ok < bk)))
-                                best = om, bk = ok;
-                }
+                gate_wave_argmin(best, bk);
                 if (lane == 0)
                 {
                         assoc[(size_t)b * ldo + j] = best < g ? bk : -1;

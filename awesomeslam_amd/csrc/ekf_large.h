@@ -306,6 +306,8 @@ struct LargeLds
                 o = (o + 15) & ~(size_t)15;
                 return o + sizeof(SmallShared);
         }
+        /// the GATED front ends: the landmark table of small_frontend (six arrays of NP / 2 doubles) behind everything else
+        static __host__ __device__ size_t bytes_gated(int NP) { return bytes(NP) + 8 * (size_t)6 * (NP / 2); }
         static __device__ __forceinline__ SmallLds carve(unsigned char *smem, int NP)
         {
                 SmallLds L;
@@ -350,7 +352,9 @@ struct LargeLds
 /// callback returned early (no sensor message yet): the rest of the chain then leaves the filter alone.
 /// SIGHTED (aslam_sighted_update_enable): Y is zeroed in the rows of the landmarks this callback did not sight (DevView::sighted, which the front
 /// end has just written in replay and the host has copied down for a step); large_build_GS<T, true> does the rest.
-template <typename T, int MODE, bool SIGHTED = false>
+/// GATED (aslam_set_replay_gate, MODE_REPLAY only; LargeLds::bytes_gated of dynamic LDS): the front end associates by the Mahalanobis gate in the
+/// filters whose gate is > 0 (small_frontend); P is read through L2.
+template <typename T, int MODE, bool SIGHTED = false, bool GATED = false>
 __global__ __launch_bounds__(SMALL_WG) void large_frontend_kernel(DevView d, LargeView<T> lv, int64_t t, int s, int nsteps,
                                                                    double *poses_out, int32_t *dims_out, StepArgs sa, int *skipped)
 {
@@ -373,11 +377,14 @@ __global__ __launch_bounds__(SMALL_WG) void large_frontend_kernel(DevView d, Lar
         small_load<MODE>(d, L, b, tid, NP);
         if (MODE == MODE_REPLAY && tid == 0)
                 small_mask_ptr(L) = d.sighted + (size_t)b * (NP / 2); // (read behind the front end's barriers)
+        static_assert(!GATED || MODE == MODE_REPLAY, "the gate belongs to the replay seam");
+        if (GATED && tid == 0)
+                small_gate(L) = d.gate[b]; // (likewise)
         ASLAM_STAMP(0);
         if (MODE == MODE_REPLAY)
         {
-                if (small_frontend<true, LARGE_OBS_CAP, LARGE_WAIT_CAP, LARGE_NP_MAX / 2, double>(d, L, Pg, NP, b, t, s, nsteps, poses_out,
-                                                                                               dims_out, tid))
+                if (small_frontend<true, LARGE_OBS_CAP, LARGE_WAIT_CAP, LARGE_NP_MAX / 2, double, GATED>(
+                            d, L, Pg, NP, b, t, s, nsteps, poses_out, dims_out, tid, nullptr, GATED ? reinterpret_cast<double *>(smem + LargeLds::bytes(NP)) : nullptr))
                 {
                         if (tid == 0)
                                 skipped[b] = 1;

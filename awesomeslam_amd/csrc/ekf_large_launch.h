@@ -121,6 +121,7 @@ struct LargeHost
         int last_launches = 0;      // kernel launches per callback and stream group of that launch (large_stats included)
         bool last_resident = false; // that launch ran LargeChain::F32_RESIDENT
         bool last_syrk_tail = false; // the views of that launch carried the syrk's tail rule (LargeView::syrk_tail; aslam_get_syrk_tail)
+        bool gated = false;         // aslam_set_replay_gate: some filter's gate is > 0 -- the GATED instantiations of the replay front ends (either filter)
         bool sighted = false;       // aslam_sighted_update_enable: the SIGHTED instantiations of the front end and of large_build_GS (which then also stands in for large_build_GS_tiles)
 };
 
@@ -225,25 +226,32 @@ int launch_left_looking(const DevView &dv, const LargeView<T> &v, int NB, int gb
         return count;
 }
 
+/// The front-end kernel of a launch: the SIGHTED (aslam_sighted_update_enable) and GATED (aslam_set_replay_gate) instantiations are picked at
+/// run time; GATED exists for the replay seam alone
+template <typename T, int MODE> auto large_frontend_of(bool sighted, bool gated) -> decltype(&large_frontend_kernel<T, MODE>)
+{
+        if constexpr (MODE == MODE_REPLAY)
+        {
+                if (gated)
+                        return sighted ? &large_frontend_kernel<T, MODE, true, true> : &large_frontend_kernel<T, MODE, false, true>;
+        }
+        return sighted ? &large_frontend_kernel<T, MODE, true> : &large_frontend_kernel<T, MODE>;
+}
+
 /// callback s of one group: front end + predict, G, S, blocked factorisation of [S; G; Y^T], P -= V V^T, X += V q
 template <typename T, int MODE>
-void launch_large_chain(const LargePlan &plan, const LargeGroup<T> &g, size_t lds, int64_t t0, int s, int nsteps, StepArgs sa, bool sighted)
+void launch_large_chain(const LargePlan &plan, const LargeGroup<T> &g, size_t lds, int64_t t0, int s, int nsteps, StepArgs sa, bool sighted, bool gated)
 {
         const int NP = g.v.NP, NB = NP / LB, gb = g.nb;
+        // the front end (its SIGHTED / GATED instantiation; `lds` is the caller's LargeLds::bytes or bytes_gated), then G and S.  The sighted-only
+        // update enters in these two launches alone (ASLAM_GS_TILES=1 has no masked form: large_build_GS runs); the gate in the first
+        hipLaunchKernelGGL((large_frontend_of<T, MODE>(sighted, gated)), dim3(gb), dim3(SMALL_WG), lds, g.st, g.dv, g.v, t0 + s, s, nsteps, g.poses, g.dims, sa, g.skip);
         if (sighted)
-        {
-                // the sighted-only update: the mask enters in these two launches alone (ASLAM_GS_TILES=1 has no masked form: large_build_GS runs)
-                hipLaunchKernelGGL((large_frontend_kernel<T, MODE, true>), dim3(gb), dim3(SMALL_WG), lds, g.st, g.dv, g.v, t0 + s, s, nsteps, g.poses, g.dims, sa, g.skip);
                 hipLaunchKernelGGL((large_build_GS<T, true>), dim3(1 + (NP / 2 + GS_ROW_PAIRS - 1) / GS_ROW_PAIRS, gb), dim3(256), 0, g.st, g.dv, g.v, g.skip);
-        }
-        else
-        {
-        hipLaunchKernelGGL((large_frontend_kernel<T, MODE>), dim3(gb), dim3(SMALL_WG), lds, g.st, g.dv, g.v, t0 + s, s, nsteps, g.poses, g.dims, sa, g.skip);
-        if (plan.gs_tiles)
+        else if (plan.gs_tiles)
                 hipLaunchKernelGGL(large_build_GS_tiles<T>, dim3(NB * (NB + 1) / 2, gb), dim3(256), 0, g.st, g.dv, g.v, g.skip);
         else
                 hipLaunchKernelGGL(large_build_GS<T>, dim3(1 + (NP / 2 + GS_ROW_PAIRS - 1) / GS_ROW_PAIRS, gb), dim3(256), 0, g.st, g.dv, g.v, g.skip);
-        }
         const int ntile = (NP + 127) / 128;
         const dim3 syrk_grid(8 * (ntile * (ntile + 1) / 2) * ((gb + 7) / 8));
         if constexpr (sizeof(T) == 8)
@@ -311,9 +319,9 @@ template <int MODE, typename T>
 hipError_t launch_large(LargeHost &h, const DevView &dv, const LargeView<T> &lv, int *skipped, int64_t t0, int nsteps, double *poses, int32_t *dims,
                         StepArgs sa, hipStream_t st, StatsView sv = {})
 {
-        const size_t lds = LargeLds::bytes(dv.NP);
-        if (hipError_t e = h.sighted ? hipFuncSetAttribute(reinterpret_cast<const void *>(large_frontend_kernel<T, MODE, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                                     : hipFuncSetAttribute(reinterpret_cast<const void *>(large_frontend_kernel<T, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
+        const bool gated = MODE == MODE_REPLAY && h.gated;
+        const size_t lds = gated ? LargeLds::bytes_gated(dv.NP) : LargeLds::bytes(dv.NP);
+        if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(large_frontend_of<T, MODE>(h.sighted, gated)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
                 return e;
         const LaunchSlice sl = launch_slice<MODE>(sa, dv.B);
         const int first = sl.first, Bz = sl.count;
@@ -347,7 +355,7 @@ hipError_t launch_large(LargeHost &h, const DevView &dv, const LargeView<T> &lv,
         for (int s = 0; s < nsteps; ++s)
                 for (int q = 0; q < NG; ++q)
                         if (g[q].nb > 0)
-                                launch_large_chain<T, MODE>(plan, g[q], lds, t0, s, nsteps, sl.sa, h.sighted);
+                                launch_large_chain<T, MODE>(plan, g[q], lds, t0, s, nsteps, sl.sa, h.sighted, gated);
         for (int q = 1; q < NG && e == hipSuccess; ++q)
                 if ((e = hipEventRecord(h.ev_join[q - 1], h.aux[q - 1])) == hipSuccess)
                         e = hipStreamWaitEvent(st, h.ev_join[q - 1], 0);

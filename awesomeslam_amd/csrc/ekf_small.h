@@ -138,7 +138,9 @@ template <bool FWD> __device__ __forceinline__ void congruence_tiles(double *Lt,
 ///     P~_new = (P~^-1 + D)^-1,        u = K~ Y = P~_new (D Y)
 /// -- two in-place inversions of the tiles (cholesky_inverse_tiles<NT, true>), D added to the diagonal between them, D Y riding through the second.
 /// D and D Y live in the front end's wait-list scratch (sWx, sWy: only read inside small_frontend).  The other instantiations keep their code.
-template <int NT, int MODE, bool STATS = false, bool SIGHTED = false>
+/// GATED (aslam_set_replay_gate, MODE_REPLAY only): the front end associates by the Mahalanobis gate in the filters whose gate is > 0 (small_frontend).
+/// It reads P from the LDS tiles; its landmark table overlays sH, whose coefficients are formed behind the front end and dead in front of it.
+template <int NT, int MODE, bool STATS = false, bool SIGHTED = false, bool GATED = false>
 __global__ __launch_bounds__(SMALL_WG) void ekf_small_kernel(DevView d, int64_t t0, int nsteps, double *poses_out,
                                                               int32_t *dims_out, StepArgs sa, StatsView sv)
 {
@@ -152,6 +154,7 @@ __global__ __launch_bounds__(SMALL_WG) void ekf_small_kernel(DevView d, int64_t 
         // SIGHTED: D [NP], D Y [NP] and, from sD[NP] on, 64 partial products of the first factor's inverted diagonal (2 KB of scratch each)
         double *const sD = reinterpret_cast<double *>(L.sWx), *const sDY = reinterpret_cast<double *>(L.sWy);
         static_assert(!SIGHTED || (NP + 64) * 8 <= 4 * SMALL_WAIT_CAP, "D and D Y fit the wait-list scratch");
+        static_assert(!GATED || MODE == MODE_REPLAY, "the gate belongs to the replay seam");
 
         const int tid_launch = threadIdx.x, tid = tid_launch;
         const int b = (MODE == MODE_STEP && sa.traj >= 0) ? sa.traj : (int)blockIdx.x; // sa.traj < 0: the batched step, one workgroup per filter
@@ -164,6 +167,8 @@ __global__ __launch_bounds__(SMALL_WG) void ekf_small_kernel(DevView d, int64_t 
         small_load<MODE>(d, L, b, tid, NP);
         if (MODE == MODE_REPLAY && tid == 0)
                 small_mask_ptr(L) = d.sighted + (size_t)b * NLM; // (read behind the front end's barriers)
+        if (GATED && tid == 0)
+                small_gate(L) = d.gate[b]; // (likewise)
         // P stays in LDS for the whole launch, as the lower 16x16 tiles of the symmetric matrix (the tile storage the solver
         // factors in place): HBM sees it once on the way in and once on the way out
         for (int idx = tid; idx < LY::NTILES * 256; idx += SMALL_WG)
@@ -184,7 +189,7 @@ __global__ __launch_bounds__(SMALL_WG) void ekf_small_kernel(DevView d, int64_t 
                 const int64_t t = t0 + s;
                 if (MODE == MODE_REPLAY)
                 {
-                        if (small_frontend<true, SMALL_OBS_CAP, SMALL_WAIT_CAP, NP / 2, double>(d, L, Pg, NP, b, t, s, nsteps, poses_out, dims_out, tid, Lt))
+                        if (small_frontend<true, SMALL_OBS_CAP, SMALL_WAIT_CAP, NP / 2, double, GATED>(d, L, Pg, NP, b, t, s, nsteps, poses_out, dims_out, tid, Lt, sH))
                         {
                                 if constexpr (STATS)
                                         stats_skip(sv, b, s, nsteps, tid);

@@ -32,6 +32,7 @@
 #include <type_traits>
 
 #include "device_common.h"
+#include "gate_math.h"
 
 namespace aslam
 {
@@ -83,6 +84,10 @@ struct DevView
         // the mask of the last callback (aslam_get_sighted): 1 where the association walk gave landmark k an observation.  Written by the replay front
         // end of the EKF families every callback and by the *_step_sighted seams; read by the kernels only under aslam_sighted_update_enable
         uint8_t *sighted;  // [B][NP/2]
+        // the gate of the replay seam (aslam_set_replay_gate): 0 = the Euclidean rule, > 0 = the Mahalanobis gate of small_frontend<..., GATED>; read by
+        // the GATED instantiations alone, which also count the observations the gate dropped (aslam_get_assoc_rejected)
+        double *gate;                 // [B]
+        unsigned long long *rejected; // [B]
 };
 
 /// The per-filter arrays of a DevView (host side): f(pointer, elements per filter, zero) once per array, in the order aslam_create allocates
@@ -112,6 +117,8 @@ template <typename F> void for_each_array(DevView &d, F &&f)
         f(d.lm_seen, np / 2, false);
         f(d.lm_hits, np / 2, false);
         f(d.sighted, np / 2, false);
+        f(d.gate, 1, false);
+        f(d.rejected, 1, false);
 }
 
 #ifdef ASLAM_STAMPS
@@ -1215,6 +1222,13 @@ __device__ __forceinline__ uint8_t *&small_mask_ptr(const SmallLds &L)
         return *reinterpret_cast<uint8_t **>(L.sPd + 12);
 }
 
+/// This filter's gate (DevView::gate), kept in LDS for the launch by the GATED kernels behind small_load: the last two spare floats in front of the
+/// staging area (entries 14, 15 of sPd; 12, 13 are small_mask_ptr's).  The ungated instantiations never look at it.
+__device__ __forceinline__ double &small_gate(const SmallLds &L)
+{
+        return *reinterpret_cast<double *>(L.sPd + 14);
+}
+
 /// Bring filter `b` from HBM into LDS (vectors, scalars, stored sensor message, wait-list).
 template <int MODE> __device__ __forceinline__ void small_load(const DevView &d, const SmallLds &L, int b, int tid, int NP)
 {
@@ -1337,9 +1351,20 @@ template <int OBS_CAP> __device__ __forceinline__ void small_prefetch_intake(con
 /// association, wait-list (ekf.cpp:217-253), promotion and growth (ekf.cpp:255-290), A (EKF), init_x.
 /// Returns true when cbOdom returned early (no sensor message yet): the caller skips slam().
 /// On return sm.vx / sm.az / sm.dt hold slam()'s binary32 arguments.
-template <bool IS_EKF, int OBS_CAP, int WAIT_CAP, int NEW_CAP, typename TP>
+///
+/// GATED (aslam_set_replay_gate; MODE_REPLAY kernels only): a filter whose gate (small_gate) is > 0 associates, in a callback that starts with
+/// landmarks (n0 > 3) and a non-empty stored message, by the individual-compatibility gate of assoc.h instead of the Euclidean threshold --
+/// FilterNode::associateGated of the host mirror, on the device.  Evaluation point: the X and P the previous callback left (sX; tilesP or Pg).
+///   phase 1 (behind the barrier that ends toPoint + narrowing): lanes over landmarks, the six terms of gate_landmark into `gtab`
+///           (six arrays of stride d.NP / 2 doubles: LDS the rest of the front end does not use);
+///   phase 2 (behind the Euclidean scan, whose nearest distance stays the verdict for what the gate does not accept): a wave per observation,
+///           arg-min of gate_pair over the landmarks.  Accepted (m_min < gate): a match with that landmark (sCid = 2k, the last observation in
+///           message order wins as ever).  Else dropped (sCid = -2; the scan's best_d < assoc_dist: neither a match nor wait-list evidence,
+///           counted in DevView::rejected) or handed to the wait-list walk (sCid = -4), which is unchanged.
+/// A filter with gate 0, a callback with n0 == 3 or an empty message takes the ungated path of this very instantiation, branch for branch.
+template <bool IS_EKF, int OBS_CAP, int WAIT_CAP, int NEW_CAP, typename TP, bool GATED = false>
 __device__ __forceinline__ bool small_frontend(const DevView &d, const SmallLds &L, TP *Pg, int NP, int b, int64_t t, int s,
-                                               int nsteps, double *poses_out, int32_t *dims_out, int tid, double *tilesP = nullptr)
+                                               int nsteps, double *poses_out, int32_t *dims_out, int tid, double *tilesP = nullptr, double *gtab = nullptr)
 {
         SmallShared &sm = *L.sm;
         double *const sX = L.sX, *const sZ = L.sZ;
@@ -1393,6 +1418,8 @@ __device__ __forceinline__ bool small_frontend(const DevView &d, const SmallLds 
                 sm.any_miss = 0;
                 sm.grew = 0;
                 sm.nnew = 0;
+                if constexpr (GATED)
+                        sm.skip = 0; // observations the gate drops in this callback
         }
         __syncthreads();
         if (sm.obs_new)
@@ -1530,6 +1557,35 @@ __device__ __forceinline__ bool small_frontend(const DevView &d, const SmallLds 
         }
         __syncthreads();
         FE_STAMP(6); // toPoint + landmark narrowing + A
+        // whether this callback associates by the gate: LDS values published by barriers, the same in every thread -- and a scalar to the compiler
+        // (readfirstlane), so that the phases below, with their whole-wave exchange and their barrier, sit under scalar branches
+        bool gact = false;
+        if constexpr (GATED)
+                gact = __builtin_amdgcn_readfirstlane((int)(small_gate(L) > 0.0 && n0 > 3 && sm.sn > 0)) != 0;
+        if constexpr (GATED)
+        {
+                if (gact)
+                {
+                        const int gld = d.NP / 2; // stride of the six arrays of gtab
+                        // phase 1: the terms of every landmark at the X and P the previous callback left (the motion of this period is not added)
+                        const double gx = sX[0], gy = sX[1], gth = sX[2];
+                        const double rr = sm.prm.r_range, rb = sm.prm.r_bearing;
+                        for (int k = tid; k < nl; k += SMALL_WG)
+                        {
+                                const int a0 = 3 + 2 * k;
+                                const GateLandmark g = gate_landmark(gx, gy, gth, sX[a0], sX[a0 + 1], a0, rr, rb, [&](int i, int j) -> double {
+                                        return tilesP ? *tile_elem(tilesP, i, j) : (double)Pg[(size_t)i * NP + j]; // (the single-CU EKF's HBM copy is stale inside a launch)
+                                });
+                                gtab[k] = g.rh;
+                                gtab[gld + k] = g.bh;
+                                gtab[2 * gld + k] = g.s00;
+                                gtab[3 * gld + k] = g.s10;
+                                gtab[4 * gld + k] = g.s11;
+                                gtab[5 * gld + k] = g.det;
+                        }
+                        // (published by the barrier behind the scan)
+                }
+        }
         // nearest mapped landmark of every observation (ekf.cpp:159-173).  Eight lanes per observation scan the landmarks
         // k = c, c+8, c+16, ... each (adjacent LDS words across the eight: no bank conflicts), in index order with the
         // reference's strict `dist < mindist`.  sqrtf is correctly rounded, hence monotonic: a candidate whose squared
@@ -1614,6 +1670,11 @@ __device__ __forceinline__ bool small_frontend(const DevView &d, const SmallLds 
                         }
                         sMd[j] = bd;
                         sCid[j] = 2 * bk;
+                        if constexpr (GATED)
+                        {
+                                if (gact)
+                                        continue; // phase 2 decides
+                        }
                         if (n0 != 3 && bd < assoc_dist)
                                 atomicMax(&sNew[bk], j); // observations are walked in order: the last one wins (ekf.cpp:175-181)
                         else
@@ -1622,9 +1683,61 @@ __device__ __forceinline__ bool small_frontend(const DevView &d, const SmallLds 
         }
         FE_STAMP(7); // scan + combine
         __syncthreads();
+        if constexpr (GATED)
+        {
+                if (gact)
+                {
+                        // phase 2: a wave per observation (j is scalar: the whole-wave exchange sits under scalar branches only), lanes over landmarks.  The
+                        // result is a minimum of exactly computed values with an index tie-break: it does not depend on how the pairs are dealt
+                        const int gw = __builtin_amdgcn_readfirstlane(tid) >> 6, gl = tid & 63;
+                        const int gsn = __builtin_amdgcn_readfirstlane(sm.sn), gnl = __builtin_amdgcn_readfirstlane(nl);
+                        const double gate = small_gate(L);
+                        const int gld = d.NP / 2;
+                        for (int j = gw; j < gsn; j += SMALL_WG / 64)
+                        {
+                                double best = __builtin_inf();
+                                int bk = -1;
+                                gate_scan_lane(gtab, gld, gnl, gl, (double)sSr[j], (double)sSb[j], best, bk);
+                                gate_wave_argmin(best, bk);
+                                if (gl == 0)
+                                {
+                                        if (best < gate) // accepted (bk >= 0: best is finite or the gate could not exceed it)
+                                        {
+                                                sCid[j] = 2 * bk;
+                                                atomicMax(&sNew[bk], j); // the last accepted observation of a landmark in message order wins
+                                        }
+                                        else if (sMd[j] < assoc_dist) // the reference's own test: Euclid would have matched, the gate says it is none
+                                        {
+                                                sCid[j] = -2;
+                                                atomicAdd(&sm.skip, 1);
+                                        }
+                                        else
+                                        {
+                                                sCid[j] = -4;
+                                                sm.any_miss = 1;
+                                        }
+                                }
+                        }
+                        __syncthreads();
+                        if (tid == 0 && sm.skip)
+                                d.rejected[b] += (unsigned long long)sm.skip;
+                }
+        }
         // associated observations: Z(3 + corr_id) = range, Z(4 + corr_id) = bearing
         for (int j = tid; j < sm.sn; j += SMALL_WG)
         {
+                if constexpr (GATED)
+                {
+                        if (gact)
+                        {
+                                if (sCid[j] >= 0 && sNew[sCid[j] >> 1] == j) // accepted, and the last one of its landmark
+                                {
+                                        sZ[3 + sCid[j]] = (double)sSr[j];
+                                        sZ[4 + sCid[j]] = (double)sSb[j];
+                                }
+                                continue;
+                        }
+                }
                 if (n0 != 3 && sMd[j] < assoc_dist && sNew[sCid[j] >> 1] == j)
                 {
                         sZ[3 + sCid[j]] = (double)sSr[j];
@@ -1674,7 +1787,12 @@ __device__ __forceinline__ bool small_frontend(const DevView &d, const SmallLds 
                 constexpr int NWAVE = SMALL_WG / 64;
                 for (int j = 0; j < sm.sn; ++j) // (workgroup-uniform: every condition below reads LDS values published by a barrier)
                 {
-                        if (n0 != 3 && sMd[j] < assoc_dist)
+                        if constexpr (GATED)
+                        {
+                                if (gact && sCid[j] != -4) // a match, or dropped by the gate
+                                        continue;
+                        }
+                        if (!(GATED && gact) && n0 != 3 && sMd[j] < assoc_dist)
                                 continue;
                         const int wn = sm.wn;
                         if (wn > 0)

@@ -93,7 +93,9 @@ __device__ __forceinline__ double ukf_xsig(double x, double l, int c, double sg,
 // ------------------------------------------------------------------------------------------------------------------
 /// Per-filter front end (one workgroup of SMALL_WG threads per filter, LargeLds::bytes(NP) of dynamic LDS).  `skipped` [B] is set to 1
 /// when the callback returned early (no sensor message yet): the rest of the chain then leaves the filter alone.
-template <int MODE>
+/// GATED (aslam_set_replay_gate, MODE_REPLAY only; LargeLds::bytes_gated of dynamic LDS): the front end associates by the Mahalanobis gate in the
+/// filters whose gate is > 0 (small_frontend); P is read through L2.
+template <int MODE, bool GATED = false>
 __global__ __launch_bounds__(SMALL_WG) void ukf_large_frontend_kernel(DevView d, LargeView<double> lv, UkfLargeView uv, int64_t t, int s, int nsteps,
                                                                        double *poses_out, int32_t *dims_out, StepArgs sa, int *skipped)
 {
@@ -104,10 +106,14 @@ __global__ __launch_bounds__(SMALL_WG) void ukf_large_frontend_kernel(DevView d,
         const int tid = threadIdx.x;
         const int b = (MODE == MODE_STEP && sa.traj >= 0) ? sa.traj : (int)blockIdx.x; // sa.traj < 0: the batched step, one workgroup per filter
         double *Pg = lv.P + (size_t)b * NP * NP;
+        static_assert(!GATED || MODE == MODE_REPLAY, "the gate belongs to the replay seam");
         small_load<MODE>(d, L, b, tid, NP);
+        if (GATED && tid == 0)
+                small_gate(L) = d.gate[b]; // (read behind the front end's barriers)
         if (MODE == MODE_REPLAY)
         {
-                if (small_frontend<false, LARGE_OBS_CAP, LARGE_WAIT_CAP, LARGE_NP_MAX / 2, double>(d, L, Pg, NP, b, t, s, nsteps, poses_out, dims_out, tid))
+                if (small_frontend<false, LARGE_OBS_CAP, LARGE_WAIT_CAP, LARGE_NP_MAX / 2, double, GATED>(
+                            d, L, Pg, NP, b, t, s, nsteps, poses_out, dims_out, tid, nullptr, GATED ? reinterpret_cast<double *>(smem + LargeLds::bytes(NP)) : nullptr))
                 {
                         if (tid == 0)
                                 skipped[b] = 1;

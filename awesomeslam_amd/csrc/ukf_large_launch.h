@@ -42,8 +42,11 @@ hipError_t launch_ukf_large(LargeHost &h, const DevView &dv0, const LargeView<do
                             double *poses, int32_t *dims, StepArgs sa, hipStream_t st, StatsView sv0 = {})
 {
         const int NP = dv0.NP;
-        const size_t lds = LargeLds::bytes(NP);
-        if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(ukf_large_frontend_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
+        const bool gated = MODE == MODE_REPLAY && h.gated; // aslam_set_replay_gate: the GATED front end, with its landmark table behind the rest of the LDS
+        constexpr int MG = MODE == MODE_REPLAY ? MODE : MODE_REPLAY; // (the GATED flag is instantiated for the replay seam alone)
+        const size_t lds = gated ? LargeLds::bytes_gated(NP) : LargeLds::bytes(NP);
+        if (hipError_t e = gated ? hipFuncSetAttribute(reinterpret_cast<const void *>(ukf_large_frontend_kernel<MG, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
+                                 : hipFuncSetAttribute(reinterpret_cast<const void *>(ukf_large_frontend_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
                 return e;
         const LaunchSlice sl = launch_slice<MODE>(sa, dv0.B);
         const size_t first = (size_t)sl.first;
@@ -64,7 +67,10 @@ hipError_t launch_ukf_large(LargeHost &h, const DevView &dv0, const LargeView<do
         for (int s = 0; s < nsteps; ++s)
         {
                 int count = 0;
-                hipLaunchKernelGGL((ukf_large_frontend_kernel<MODE>), dim3(gb), dim3(SMALL_WG), lds, st, dv, lv, uv, t0 + s, s, nsteps, poses, dims, sl.sa, skip);
+                if (gated)
+                        hipLaunchKernelGGL((ukf_large_frontend_kernel<MG, true>), dim3(gb), dim3(SMALL_WG), lds, st, dv, lv, uv, t0 + s, s, nsteps, poses, dims, sl.sa, skip);
+                else
+                        hipLaunchKernelGGL((ukf_large_frontend_kernel<MODE>), dim3(gb), dim3(SMALL_WG), lds, st, dv, lv, uv, t0 + s, s, nsteps, poses, dims, sl.sa, skip);
                 count += plan.frontend;
                 count += launch_left_looking(dv, lv, NB, gb, skip, st, 1, false); // L = chol(P) in S
                 hipLaunchKernelGGL(ukf_large_sigma_pose, dim3(gb), dim3(256), 0, st, dv, lv, uv, skip);

@@ -220,9 +220,37 @@ __device__ __forceinline__ void gemm_wabt(const double *A, const double *B, int 
                                         if (pdelta && i >= 3 && j >= 3 && i < n_true && j < n_true)
                                                 old = fma(pcll, old, pwsum * pdelta[i] * pdelta[j]);
                                         const double nv = old - (gvec ? fma(gscale * gvec[i], gvec[j], acc[q][r]) : acc[q][r]);
-                                        Cg[(size_t)i * NP + j] = nv;
+                                        if (ib != jb) // (a diagonal tile is stored below, symmetrised)
+                                                Cg[(size_t)i * NP + j] = nv;
                                         acc[q][r] = nv; // (the mirror image is stored below, tile by tile, through an LDS scratch tile)
                                 }
+                        }
+                        if (MODE == GEMM_SUBTRACT_SYM && ib == jb)
+                        {
+                                // A diagonal tile holds both halves of its block, each computed on its own: the MFMA sums of (i, j) and (j, i) agree bit for
+                                // bit, the rank-one terms (gscale g_i) g_j and (pwsum d_i) d_j and whatever the predict left in `old` need not (a last bit
+                                // in a few entries).  The upper half takes the lower half's values, so that P leaves every callback exactly symmetric.
+                                // The tile goes out through the scratch tile like the mirror images below: a lane stores four consecutive entries of a row
+                                typedef double dbl2 __attribute__((ext_vector_type(2)));
+                                double *scr = stage + wave * TSZ;
+#pragma unroll
+                                for (int r = 0; r < 4; ++r)
+                                        scr[(lg + 4 * r) * TLD + li] = acc[q][r]; // scr[row of the tile][column of the tile]
+                                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                                __builtin_amdgcn_wave_barrier();
+                                const int orow = lane >> 2, oc = 4 * (lane & 3);
+                                double v[4];
+#pragma unroll
+                                for (int c = 0; c < 4; ++c)
+                                {
+                                        const int col = oc + c;
+                                        v[c] = scr[(col > orow ? col : orow) * TLD + (col > orow ? orow : col)]; // the lower triangle's entry
+                                }
+                                double *dst = Cg + (size_t)(16 * ib + orow) * NP + 16 * jb + oc;
+                                *reinterpret_cast<dbl2 *>(dst) = (dbl2){v[0], v[1]};
+                                *reinterpret_cast<dbl2 *>(dst + 2) = (dbl2){v[2], v[3]};
+                                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                                __builtin_amdgcn_wave_barrier(); // (the next tile overwrites the scratch)
                         }
                         if (MODE == GEMM_SUBTRACT_SYM && ib != jb)
                         {
@@ -343,7 +371,9 @@ __device__ __forceinline__ void gemm_l_et(const double *Lt, const double *ETg, i
 
 // ------------------------------------------------------------------------------------------------------
 /// STATS: also the innovation statistics of every callback and the pose block of P (StatsView); the STATS = false instantiations do not read `sv`.
-template <int NT, int MODE, bool STATS = false>
+/// GATED (aslam_set_replay_gate, MODE_REPLAY only): the front end associates by the Mahalanobis gate in the filters whose gate is > 0 (small_frontend).
+/// It reads P through L2 (Pg is current at the start of every callback); its landmark table lies in SmallLayout's sH, which this kernel never uses.
+template <int NT, int MODE, bool STATS = false, bool GATED = false>
 __global__ __launch_bounds__(SMALL_WG) void ukf_small_kernel(DevView d, UkfView uv, int64_t t0, int nsteps, double *poses_out,
                                                               int32_t *dims_out, StepArgs sa, StatsView sv)
 {
@@ -376,7 +406,10 @@ __global__ __launch_bounds__(SMALL_WG) void ukf_small_kernel(DevView d, UkfView 
         unsigned long long stamp_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         unsigned long long stamp_last = __builtin_amdgcn_s_memtime();
 #endif
+        static_assert(!GATED || MODE == MODE_REPLAY, "the gate belongs to the replay seam");
         small_load<MODE>(d, L, b, tid, NP);
+        if (GATED && tid == 0)
+                small_gate(L) = d.gate[b]; // (read behind the front end's barriers)
 
         for (int s = 0; s < nsteps; ++s)
         {
@@ -386,7 +419,7 @@ __global__ __launch_bounds__(SMALL_WG) void ukf_small_kernel(DevView d, UkfView 
                 const int64_t t = t0 + s;
                 if (MODE == MODE_REPLAY)
                 {
-                        if (small_frontend<false, SMALL_OBS_CAP, SMALL_WAIT_CAP, NP / 2, double>(d, L, Pg, NP, b, t, s, nsteps, poses_out, dims_out, tid))
+                        if (small_frontend<false, SMALL_OBS_CAP, SMALL_WAIT_CAP, NP / 2, double, GATED>(d, L, Pg, NP, b, t, s, nsteps, poses_out, dims_out, tid, nullptr, L.sH))
                         {
                                 if constexpr (STATS)
                                         stats_skip(sv, b, s, nsteps, tid);

@@ -11,7 +11,7 @@ from . import consistency
 from .core import CFG_UKF_LARGE, F64, Core, Params
 
 
-def sweep(kind, trajectory, candidates, max_landmark_count, dtype=F64, truth=None, device=0):
+def sweep(kind, trajectory, candidates, max_landmark_count, dtype=F64, truth=None, device=0, gates=None):
     """Replay `trajectory` once per candidate, all candidates in one launch.
 
     kind                'ekf' or 'ukf'
@@ -19,6 +19,8 @@ def sweep(kind, trajectory, candidates, max_landmark_count, dtype=F64, truth=Non
     candidates          parameter sets: core.Params objects or dicts of overrides of the defaults (Core.set_params)
     max_landmark_count  as for Core
     truth               [T, 3] ground-truth poses; default: the trace's own, when it has one
+    gates               one association gate per candidate (Core.set_replay_gate: 0 = the Euclidean rule, > 0 = the Mahalanobis gate), so that a
+                        gate can be ranked like a noise model; None: the Euclidean rule everywhere, and the result is what it was without the argument
 
     Returns a list with one dict per candidate, in the order given:
         params          the record the filter ran with (dict)
@@ -28,6 +30,9 @@ def sweep(kind, trajectory, candidates, max_landmark_count, dtype=F64, truth=Non
         N               the final state dimension
         status          the filter's ASLAM_ST_* bits (0 = nothing happened)
         pose_nees       mean consistency.pose_nees over those callbacks (None without ground truth)
+    and, with `gates`:
+        gate            the gate the filter ran with
+        rejected        observations the gate dropped (Core.assoc_rejected)
 
     A larger log-likelihood is a better account of the recorded innovations.  UKF caveat: the UKF's S is the reference's signed form -- the
     central weight (1 - N) / 3 is negative, so S may be indefinite; nis is then a signed quadratic form and ln |det S| is not the normaliser of
@@ -44,6 +49,8 @@ def sweep(kind, trajectory, candidates, max_landmark_count, dtype=F64, truth=Non
     B = len(candidates)
     if B < 1:
         raise ValueError("no candidates")
+    if gates is not None and len(gates) != B:
+        raise ValueError("`gates` holds one gate per candidate")
     tr = trajectory.select([0] * B)
     T = tr.T
     if truth is None and tr.truth is not None:
@@ -55,6 +62,9 @@ def sweep(kind, trajectory, candidates, max_landmark_count, dtype=F64, truth=Non
         try:
             for b, cand in enumerate(candidates):
                 core.set_params(cand, b)
+            if gates is not None:
+                for b, g in enumerate(gates):
+                    core.set_replay_gate(g, b)
             core.reset()  # p0_pose applies at initialize(): every candidate runs under its own record from the first callback on
             core.set_trace(tr)
             dev = torch.device("cuda", device)
@@ -75,6 +85,8 @@ def sweep(kind, trajectory, candidates, max_landmark_count, dtype=F64, truth=Non
                 out.append(dict(params=Params.as_dict(core.params(b)), log_likelihood=float(ll.sum()),
                                 nis_per_dim=float((nis[b][ran] / dims[b][ran]).mean()) if ran.any() else float("nan"), callbacks=int(ran.sum()),
                                 N=core.dim(b), status=core.status(b), pose_nees=nees))
+                if gates is not None:
+                    out[-1].update(gate=core.replay_gate(b), rejected=core.assoc_rejected(b))
             return out
         finally:
             core.close()

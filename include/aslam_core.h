@@ -336,9 +336,33 @@ int aslam_select_duplicates(aslam_ctx *ctx, const double *gate, const double *ma
    gate[b] that is not > 0 (infinity is allowed), a misaligned device pointer.  A refused call launches nothing.
    Synchronises the context first, then runs on `stream` (one launch, one workgroup per filter); the outputs are complete when the stream
    is.  The call reads X, P, the dimensions and the parameters and writes nothing a filter owns.  It works on every kind of context; for the
-   UKF it is this same linearised gate, not the S of the sigma points.  The replay seam (aslam_replay) keeps the Euclidean rule. */
+   UKF it is this same linearised gate, not the S of the sigma points.  The replay seam (aslam_replay) keeps the Euclidean rule unless
+   aslam_set_replay_gate switches this gate on there. */
 int aslam_gate_observations(aslam_ctx *ctx, const float *obs, int ldo, int is_device, const int32_t *n_obs, const double *gate, int32_t *assoc_dev,
                             double *mdist_dev, void *stream);
+
+/* The same gate inside the replay seam (aslam_replay[_stats]): per filter, off by default.  A callback of a filter whose gate is > 0, that
+   starts with landmarks (n0 > 3) and has a non-empty stored message, associates as follows.  The evaluation point is the X and P the previous
+   callback left (the motion of this odometry period is not added); bearings are normalised first, as ever.  For every observation j, m against
+   every landmark k < (n0 - 3) / 2 exactly as aslam_gate_observations defines it (the same device functions compute both), arg-min with ties to
+   the smaller k.
+       accepted (m_min < gate):  Z(3+2k), Z(4+2k) take the observation (of several accepted observations of one landmark the last in message order);
+                                 k is sighted (mask, last_seen, hits: one hit per callback)
+       dropped  (not accepted, but the reference's own nearest-landmark distance is below assoc_dist):  neither a match nor wait-list evidence;
+                                 the filter's rejected counter goes up by one
+       otherwise:                the observation goes through the wait-list, which is unchanged and stays Euclidean
+   Landmarks promoted in a callback are gated from the next one on.  n0 == 3, an empty message and every filter whose gate is 0 take the
+   Euclidean rule, bit for bit what they compute without this call; a context in which no gate is > 0 launches exactly the kernels it launched
+   before (aslam_kernel_info names the gated instantiation while one is in use; the gate adds no launch).  Everything behind association is
+   untouched, and the gate composes with aslam_replay_stats and aslam_sighted_update_enable.  All four kernel families take it, the single-CU
+   UKF included.  Not part of it: joint compatibility, a gate on the wait-list.  aslam_*_step* run no association and are unaffected.
+   aslam_set_replay_gate: gate of filter traj (-1 = all); 0 = the Euclidean rule (default), > 0 (infinity allowed) = gated.  ASLAM_ERR_ARG,
+   naming the argument, on a NaN or negative gate or a bad traj; a refused call changes nothing.  aslam_reset keeps the gates, like the
+   parameters; snapshots do not carry them, and aslam_restore, prune, merge and join leave them alone.  The counter is zeroed by aslam_reset and,
+   for the restored slots, by aslam_restore; prune, merge and join leave it alone.  All three synchronise the context first. */
+int aslam_set_replay_gate(aslam_ctx *ctx, int traj, double gate);
+int aslam_get_replay_gate(aslam_ctx *ctx, int traj, double *gate);
+int aslam_get_assoc_rejected(aslam_ctx *ctx, int traj, uint64_t *count);
 
 /* ---- read-back (synchronises the context's last stream) ------------------------------------------- */
 int aslam_get_dim(aslam_ctx *ctx, int traj, int *n);
