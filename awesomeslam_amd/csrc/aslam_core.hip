@@ -14,6 +14,7 @@
 #include <cstring>
 #include <cstdlib>
 #include <algorithm>
+#include <utility>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -90,11 +91,9 @@ struct aslam_ctx
         // aslam_set_params: the host copy of dv.prm ([batch] records in HBM); aslam_grow and init_state read p0_landmark / p0_pose from it
         std::vector<aslam_params> params;
         aslam_params *params_dev = nullptr;
-        // aslam_snapshot / aslam_restore: descriptors, gathered headers and the staged copy of a host blob (grown on demand, not state)
+        // the staging block of the maintenance calls (Staging below): descriptors, reports, staged host arrays, records (grown on demand, not state)
         char *snap_dev = nullptr;
         size_t snap_cap = 0;
-        int snap_count = 0, snap_nmax = 0; // the last pack launch (aslam_debug_snapshot_rate repeats it)
-        int64_t snap_total = 0;
 };
 
 namespace
@@ -377,6 +376,62 @@ int clear_innovation(aslam_ctx *c)
         return ASLAM_OK;
 }
 
+/// at least `bytes` of device staging for a maintenance call (the context is synchronised: nothing reads the old block).  When the block has
+/// to grow, the first `keep` bytes of the old one are carried over; with keep = 0 the old block goes before the new one is allocated.
+int snap_reserve(aslam_ctx *c, size_t bytes, size_t keep = 0)
+{
+        if (bytes <= c->snap_cap)
+                return ASLAM_OK;
+        if (!keep && c->snap_dev)
+        {
+                (void)hipFree(c->snap_dev);
+                c->snap_dev = nullptr, c->snap_cap = 0;
+        }
+        void *q = nullptr;
+        HIP_TRY(hipMalloc(&q, bytes));
+        const hipError_t e = keep ? hipMemcpy(q, c->snap_dev, keep, hipMemcpyDeviceToDevice) : hipSuccess;
+        if (e != hipSuccess)
+        {
+                (void)hipFree(q);
+                HIP_TRY(e);
+        }
+        if (c->snap_dev)
+                (void)hipFree(c->snap_dev);
+        c->snap_dev = static_cast<char *>(q);
+        c->snap_cap = bytes;
+        return ASLAM_OK;
+}
+
+/// The layout of a call's staging in the context's block: sections in the order they are taken, each starting on a 64-byte boundary.  A
+/// pointer from at() holds until the next reserve() that has to grow the block.
+struct Staging
+{
+        aslam_ctx *c;
+        size_t size = 0;
+        size_t take(size_t bytes) { return std::exchange(size, size + (size_t)snap_pad64((int64_t)bytes)); }
+        int reserve(size_t keep = 0) const { return snap_reserve(c, size, keep); }
+        template <typename T> T *at(size_t off) const { return reinterpret_cast<T *>(c->snap_dev + off); }
+};
+
+/// rows a mask must have: the landmarks a filter of this context can hold, (max_landmark_count - 3) / 2 rounded up
+int landmark_capacity(const aslam_ctx *c)
+{
+        return std::max(0, (c->cfg.max_landmark_count - 2) / 2);
+}
+
+/// empty, or which of the arguments the per-landmark calls share is refused; `noun`: what the call's array is, "mask" or "into"
+std::string bad_mask(const aslam_ctx *c, const void *mask, int ld, int is_device, const char *noun)
+{
+        if (!c)
+                return "null context";
+        if (!mask)
+                return std::string("null ") + noun;
+        if (ld < landmark_capacity(c))
+                return "ld is smaller than the context's landmark capacity, (max_landmark_count - 3) / 2 rounded up";
+        if (is_device && ((uintptr_t)mask & 15))
+                return std::string("a device ") + noun + " must be 16-byte aligned";
+        return std::string();
+}
 } // namespace
 
 extern "C" {
@@ -1140,19 +1195,58 @@ int aslam_get_layout(aslam_ctx *c, int *padded_dim, int64_t *hbm_bytes)
 /* ---- include/aslam_snapshot.h ------------------------------------------------------------------------------------- */
 namespace
 {
-/// at least `bytes` of device staging for a snapshot call (the context is synchronised: nothing reads the old block)
-int snap_reserve(aslam_ctx *c, size_t bytes)
+/// true where n cannot be the dimension of a filter of this context
+bool bad_dimension(const aslam_ctx *c, int n)
 {
-        if (bytes <= c->snap_cap)
-                return ASLAM_OK;
-        if (c->snap_dev)
-                (void)hipFree(c->snap_dev);
-        c->snap_dev = nullptr;
-        c->snap_cap = 0;
-        void *q = nullptr;
-        HIP_TRY(hipMalloc(&q, bytes));
-        c->snap_dev = static_cast<char *>(q);
-        c->snap_cap = bytes;
+        return n < 3 || !(n & 1) || n >= c->cfg.max_landmark_count || n > c->NP;
+}
+
+/// the descriptor of a record written from slot `slot`: the list sizes clamped to what the slot's lists hold; place_records sets the offset
+SnapDesc slot_desc(const aslam_ctx *c, int slot, int n, int sens_n, int wait_n)
+{
+        return SnapDesc{0, slot, n, std::min(std::max(sens_n, 0), c->dv.max_obs), std::min(std::max(wait_n, 0), c->dv.max_wait), {0, 0}};
+}
+
+/// the blob the records of `desc` make, in their order: the offsets into desc; the blob's size and the largest dimension (the pack grid's) back
+struct Placed
+{
+        int64_t total;
+        int n_max;
+};
+Placed place_records(std::vector<SnapDesc> &desc)
+{
+        Placed p = {64 + snap_pad64(8 * (int64_t)desc.size()), 3};
+        for (SnapDesc &d : desc)
+        {
+                d.off = p.total;
+                p.total += snap_pad64(snap_record_bytes(d.n, d.sens_n, d.wait_n));
+                p.n_max = std::max(p.n_max, d.n);
+        }
+        return p;
+}
+
+/// n, the init flags and the list sizes of the batch, on the host: one launch, one copy, one synchronisation on `st`; overwrites the staging
+int fetch_filter_meta(aslam_ctx *c, hipStream_t st, std::vector<FilterMeta> &meta)
+{
+        const int B = c->cfg.batch;
+        Staging s{c};
+        const size_t o_meta = s.take(sizeof(FilterMeta) * B);
+        if (int rc = s.reserve(); rc != ASLAM_OK)
+                return rc;
+        hipLaunchKernelGGL(filter_meta, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, (const int *)c->dv.n, (const int *)c->dv.flags,
+                           (const int *)c->dv.sens_n, (const int *)c->dv.wait_n, B, s.at<FilterMeta>(o_meta));
+        HIP_TRY(hipGetLastError());
+        meta.resize((size_t)B);
+        HIP_TRY(hipMemcpyAsync(meta.data(), s.at<FilterMeta>(o_meta), sizeof(FilterMeta) * B, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return ASLAM_OK;
+}
+
+/// the mask of the last callback of every slot of `desc` to zero: it indexes landmarks that are gone, have moved, or were never sighted there
+int clear_sighted(aslam_ctx *c, const std::vector<SnapDesc> &desc, hipStream_t st)
+{
+        for (const SnapDesc &d : desc)
+                HIP_TRY(hipMemsetAsync(c->dv.sighted + (size_t)d.slot * (c->NP / 2), 0, (size_t)c->NP / 2, st));
         return ASLAM_OK;
 }
 
@@ -1213,6 +1307,33 @@ int aslam_snapshot_check(const void *host_blob, int64_t bytes, int32_t *filter, 
         return ASLAM_OK;
 }
 
+namespace
+{
+/// the records a snapshot of slots trajs[0 .. count) (null: slot i) holds, described and placed; the context is synchronised
+int snap_describe(aslam_ctx *c, const int32_t *trajs, int count, hipStream_t st, std::vector<SnapDesc> &desc, Placed &placed)
+{
+        std::vector<FilterMeta> meta;
+        if (int rc = fetch_filter_meta(c, st, meta); rc != ASLAM_OK)
+                return rc;
+        for (int i = 0; i < count; ++i)
+        {
+                const FilterMeta &m = meta[trajs ? trajs[i] : i];
+                if (bad_dimension(c, m.n))
+                        return fail(ASLAM_ERR_STATE, "a filter of the context has an invalid dimension");
+                desc.push_back(slot_desc(c, trajs ? trajs[i] : i, m.n, m.sens_n, m.wait_n));
+        }
+        placed = place_records(desc);
+        return ASLAM_OK;
+}
+
+/// the pack launch of a snapshot: records of `desc_dev` (count of them, the largest of dimension n_max) from the slots as they are
+void launch_snapshot_pack(aslam_ctx *c, const SnapDesc *desc_dev, int count, const Placed &placed, char *out, hipStream_t st)
+{
+        hipLaunchKernelGGL(record_pack<SnapshotSrc>, snap_grid((int64_t)placed.n_max * (placed.n_max + 1) / 2, count), dim3(SNAP_WG), 0, st, snap_ctx(c),
+                           desc_dev, count, (uint32_t)c->cfg.filter, (uint64_t)placed.total, SnapshotSrc{}, out);
+}
+} // namespace
+
 int aslam_snapshot(aslam_ctx *c, const int32_t *trajs, int count, void *blob, int64_t cap_bytes, int is_device, int64_t *bytes_needed,
                    void *stream)
 {
@@ -1229,26 +1350,12 @@ int aslam_snapshot(aslam_ctx *c, const int32_t *trajs, int count, void *blob, in
         int rc = sync_ctx(c);
         if (rc != ASLAM_OK)
                 return rc;
-        // n, sens_n, wait_n of the batch: three small copies, whatever `count` is
-        std::vector<int> meta(3 * (size_t)B);
-        HIP_TRY(hipMemcpy(&meta[0], c->dv.n, sizeof(int) * B, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(&meta[B], c->dv.sens_n, sizeof(int) * B, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(&meta[2 * (size_t)B], c->dv.wait_n, sizeof(int) * B, hipMemcpyDeviceToHost));
-        std::vector<SnapDesc> desc(count);
-        int64_t off = 64 + snap_pad64(8 * (int64_t)count);
-        int n_max = 3;
-        for (int i = 0; i < count; ++i)
-        {
-                const int t = trajs ? trajs[i] : i;
-                SnapDesc &d = desc[i];
-                d = SnapDesc{off, t, meta[t], std::min(std::max(meta[B + t], 0), c->dv.max_obs), std::min(std::max(meta[2 * (size_t)B + t], 0), c->dv.max_wait), {0, 0}};
-                const int64_t rb = snap_record_bytes(d.n, d.sens_n, d.wait_n);
-                if (rb < 0 || d.n >= c->cfg.max_landmark_count)
-                        return fail(ASLAM_ERR_STATE, "a filter of the context has an invalid dimension");
-                off += snap_pad64(rb);
-                n_max = std::max(n_max, d.n);
-        }
-        const int64_t total = off;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        std::vector<SnapDesc> desc;
+        Placed placed;
+        if ((rc = snap_describe(c, trajs, count, st, desc, placed)) != ASLAM_OK)
+                return rc;
+        const int64_t total = placed.total;
         if (bytes_needed)
                 *bytes_needed = total;
         if (!blob)
@@ -1257,16 +1364,15 @@ int aslam_snapshot(aslam_ctx *c, const int32_t *trajs, int count, void *blob, in
                 return fail(ASLAM_ERR_ARG, "blob capacity below the snapshot's size (" + std::to_string(total) + " bytes)");
         if (is_device && ((uintptr_t)blob & 15))
                 return fail(ASLAM_ERR_ARG, "a device blob must be 16-byte aligned");
-        const size_t dbytes = (size_t)snap_pad64((int64_t)sizeof(SnapDesc) * count);
-        if ((rc = snap_reserve(c, dbytes + (is_device ? 0 : (size_t)total))) != ASLAM_OK)
+        // staging: descriptors | the records of a host blob
+        Staging s{c};
+        const size_t o_desc = s.take(sizeof(SnapDesc) * count), o_blob = s.take(is_device ? 0 : (size_t)total);
+        if ((rc = s.reserve()) != ASLAM_OK)
                 return rc;
-        HIP_TRY(hipMemcpy(c->snap_dev, desc.data(), sizeof(SnapDesc) * count, hipMemcpyHostToDevice));
-        hipStream_t st = static_cast<hipStream_t>(stream);
-        char *out = is_device ? static_cast<char *>(blob) : c->snap_dev + dbytes;
+        HIP_TRY(hipMemcpy(s.at<SnapDesc>(o_desc), desc.data(), sizeof(SnapDesc) * count, hipMemcpyHostToDevice));
+        char *out = is_device ? static_cast<char *>(blob) : s.at<char>(o_blob);
         c->last_stream = st;
-        c->snap_count = count, c->snap_nmax = n_max, c->snap_total = total;
-        hipLaunchKernelGGL(snapshot_pack, snap_grid((int64_t)n_max * (n_max + 1) / 2, count), dim3(SNAP_WG), 0, st, snap_ctx(c),
-                           reinterpret_cast<const SnapDesc *>(c->snap_dev), count, (uint32_t)c->cfg.filter, (uint64_t)total, out);
+        launch_snapshot_pack(c, s.at<SnapDesc>(o_desc), count, placed, out, st);
         HIP_TRY(hipGetLastError());
         if (!is_device)
         {
@@ -1280,8 +1386,8 @@ namespace
 {
 /// The blob header, the offset table and every record header of a blob, validated, on the host (aslam_restore, aslam_join_maps).  A device
 /// blob's come through `st`: the blob header, the offset table, and all record headers through one gather launch -- three small copies, each
-/// followed by a synchronisation of `st`; the gather stages `front` bytes into the context's block.
-int snap_headers(aslam_ctx *c, const void *blob, int64_t bytes, int is_device, hipStream_t st, size_t front, SnapBlobHeader &h,
+/// followed by a synchronisation of `st`; the gather stages at the front of the context's block, which no caller holds data in by then.
+int snap_headers(aslam_ctx *c, const void *blob, int64_t bytes, int is_device, hipStream_t st, SnapBlobHeader &h,
                  std::vector<uint64_t> &table, std::vector<SnapRecHeader> &recs)
 {
         int rc;
@@ -1318,11 +1424,12 @@ int snap_headers(aslam_ctx *c, const void *blob, int64_t bytes, int is_device, h
                 if (const char *e = snap_check_offset(table[i], table_end, h.total_bytes))
                         return fail(ASLAM_ERR_ARG, "snapshot record " + std::to_string(i) + ": " + e);
         // one gather launch through the validated table, one copy
-        const size_t tbytes = (size_t)snap_pad64(8 * (int64_t)cnt);
-        if ((rc = snap_reserve(c, front + tbytes + 64 * cnt)) != ASLAM_OK)
+        Staging s{c};
+        const size_t o_table = s.take(8 * cnt), o_recs = s.take(64 * cnt);
+        if ((rc = s.reserve()) != ASLAM_OK)
                 return rc;
-        uint64_t *tdev = reinterpret_cast<uint64_t *>(c->snap_dev + front);
-        SnapRecHeader *hdev = reinterpret_cast<SnapRecHeader *>(c->snap_dev + front + tbytes);
+        uint64_t *tdev = s.at<uint64_t>(o_table);
+        SnapRecHeader *hdev = s.at<SnapRecHeader>(o_recs);
         HIP_TRY(hipMemcpyAsync(tdev, table.data(), 8 * cnt, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(snapshot_gather, dim3((unsigned)((4 * cnt + SNAP_WG - 1) / SNAP_WG)), dim3(SNAP_WG), 0, st, b, tdev, (int)cnt, hdev);
         HIP_TRY(hipGetLastError());
@@ -1348,14 +1455,12 @@ int aslam_restore(aslam_ctx *c, const int32_t *records, const int32_t *trajs, in
         if (rc != ASLAM_OK)
                 return rc;
         hipStream_t st = static_cast<hipStream_t>(stream);
-        const char *b = static_cast<const char *>(blob);
-        const size_t dbytes = (size_t)snap_pad64((int64_t)sizeof(SnapDesc) * count);
 
         // ---- the headers, on the host
         SnapBlobHeader h;
         std::vector<uint64_t> table;
         std::vector<SnapRecHeader> recs;
-        if ((rc = snap_headers(c, blob, bytes, is_device, st, dbytes, h, table, recs)) != ASLAM_OK)
+        if ((rc = snap_headers(c, blob, bytes, is_device, st, h, table, recs)) != ASLAM_OK)
                 return rc;
 
         // ---- the request against the context
@@ -1383,29 +1488,30 @@ int aslam_restore(aslam_ctx *c, const int32_t *records, const int32_t *trajs, in
                 desc[i] = SnapDesc{(int64_t)table[r], t, q.n, q.sens_n, q.wait_n, {0, 0}};
         }
 
-        // ---- one unpack launch
-        if ((rc = snap_reserve(c, dbytes + (is_device ? 0 : (size_t)h.total_bytes))) != ASLAM_OK)
+        // ---- one unpack launch; staging: descriptors | a host blob's copy
+        Staging s{c};
+        const size_t o_desc = s.take(sizeof(SnapDesc) * count), o_blob = s.take(is_device ? 0 : (size_t)h.total_bytes);
+        if ((rc = s.reserve()) != ASLAM_OK)
                 return rc;
-        HIP_TRY(hipMemcpy(c->snap_dev, desc.data(), sizeof(SnapDesc) * count, hipMemcpyHostToDevice));
-        const char *src = b;
+        SnapDesc *ddev = s.at<SnapDesc>(o_desc);
+        HIP_TRY(hipMemcpy(ddev, desc.data(), sizeof(SnapDesc) * count, hipMemcpyHostToDevice));
+        const char *src = static_cast<const char *>(blob);
         if (!is_device)
         {
-                HIP_TRY(hipMemcpy(c->snap_dev + dbytes, b, (size_t)h.total_bytes, hipMemcpyHostToDevice));
-                src = c->snap_dev + dbytes;
+                HIP_TRY(hipMemcpy(s.at<char>(o_blob), blob, (size_t)h.total_bytes, hipMemcpyHostToDevice));
+                src = s.at<char>(o_blob);
         }
         c->last_stream = st;
-        hipLaunchKernelGGL(snapshot_unpack, snap_grid((int64_t)c->NP * c->NP / 2, count), dim3(SNAP_WG), 0, st, snap_ctx(c),
-                           reinterpret_cast<const SnapDesc *>(c->snap_dev), count, src);
+        hipLaunchKernelGGL(snapshot_unpack, snap_grid((int64_t)c->NP * c->NP / 2, count), dim3(SNAP_WG), 0, st, snap_ctx(c), ddev, count, src);
         HIP_TRY(hipGetLastError());
         // (format v1 does not carry the sighting record: the restored slots start at clock 0, every landmark at age 0)
-        hipLaunchKernelGGL(sight_clear, dim3((unsigned)count), dim3(PRUNE_WAVE), 0, st, reinterpret_cast<const SnapDesc *>(c->snap_dev), c->NP,
-                           c->dv.clock, c->dv.lm_seen, c->dv.lm_hits);
+        hipLaunchKernelGGL(sight_clear, dim3((unsigned)count), dim3(PRUNE_WAVE), 0, st, ddev, c->NP, c->dv.clock, c->dv.lm_seen, c->dv.lm_hits);
         HIP_TRY(hipGetLastError());
-        for (int i = 0; i < count; ++i) // (nor the mask of the last callback, nor the count of gated-out observations; the slot's gate stays)
-        {
-                HIP_TRY(hipMemsetAsync(c->dv.sighted + (size_t)desc[i].slot * (c->NP / 2), 0, (size_t)c->NP / 2, st));
-                HIP_TRY(hipMemsetAsync(c->dv.rejected + desc[i].slot, 0, sizeof(*c->dv.rejected), st));
-        }
+        // (nor the mask of the last callback, nor the count of gated-out observations; the slot's gate stays)
+        if ((rc = clear_sighted(c, desc, st)) != ASLAM_OK)
+                return rc;
+        for (const SnapDesc &d : desc)
+                HIP_TRY(hipMemsetAsync(c->dv.rejected + d.slot, 0, sizeof(*c->dv.rejected), st));
         return ASLAM_OK;
 }
 
@@ -1431,7 +1537,7 @@ int aslam_join_maps(aslam_ctx *c, const int32_t *records, const int32_t *trajs, 
         SnapBlobHeader h;
         std::vector<uint64_t> table;
         std::vector<SnapRecHeader> recs;
-        if ((rc = snap_headers(c, blob, bytes, is_device, st, 0, h, table, recs)) != ASLAM_OK)
+        if ((rc = snap_headers(c, blob, bytes, is_device, st, h, table, recs)) != ASLAM_OK)
                 return rc;
 
         // ---- the request: indices, slots, the selection and the frames
@@ -1475,20 +1581,14 @@ int aslam_join_maps(aslam_ctx *c, const int32_t *records, const int32_t *trajs, 
         }
 
         // ---- n, the init flags and the list sizes of the batch: the one copy and the one synchronisation of the call
-        const size_t mbytes = (size_t)snap_pad64((int64_t)sizeof(JoinMeta) * B);
-        if ((rc = snap_reserve(c, mbytes)) != ASLAM_OK)
-                return rc;
         const DevView &dv = c->dv;
-        hipLaunchKernelGGL(join_meta, dim3((unsigned)((B + PRUNE_WAVE - 1) / PRUNE_WAVE)), dim3(PRUNE_WAVE), 0, st, (const int *)dv.n, (const int *)dv.flags,
-                           (const int *)dv.sens_n, (const int *)dv.wait_n, B, reinterpret_cast<JoinMeta *>(c->snap_dev));
-        HIP_TRY(hipGetLastError());
-        std::vector<JoinMeta> meta((size_t)B);
-        HIP_TRY(hipMemcpyAsync(meta.data(), c->snap_dev, sizeof(JoinMeta) * B, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        std::vector<FilterMeta> meta;
+        if ((rc = fetch_filter_meta(c, st, meta)) != ASLAM_OK)
+                return rc;
         for (const Entry &e : ent)
         {
-                const JoinMeta &m = meta[e.slot];
-                if (m.n < 3 || !(m.n & 1) || m.n >= c->cfg.max_landmark_count || m.n > c->NP)
+                const FilterMeta &m = meta[e.slot];
+                if (bad_dimension(c, m.n))
                         return fail(ASLAM_ERR_STATE, who + "filter " + std::to_string(e.slot) + " has an invalid dimension");
                 if (m.flags & FLAG_INIT_X)
                         return fail(ASLAM_ERR_STATE, who + "filter " + std::to_string(e.slot) + " has not run a callback yet (init_x is set: the first one "
@@ -1503,7 +1603,6 @@ int aslam_join_maps(aslam_ctx *c, const int32_t *records, const int32_t *trajs, 
         std::vector<SnapDesc> desc;
         std::vector<JoinDesc> jdesc;
         std::vector<int32_t> idx;
-        int n_max = 3;
         for (int i = 0; i < count; ++i)
         {
                 const Entry &e = ent[i];
@@ -1511,9 +1610,8 @@ int aslam_join_maps(aslam_ctx *c, const int32_t *records, const int32_t *trajs, 
                         joined_out[i] = (int32_t)e.idx.size();
                 if (e.idx.empty())
                         continue;
-                const JoinMeta &m = meta[e.slot];
-                const int n_new = m.n + 2 * (int)e.idx.size();
-                desc.push_back(SnapDesc{0, e.slot, n_new, std::min(std::max(m.sens_n, 0), dv.max_obs), std::min(std::max(m.wait_n, 0), dv.max_wait), {0, 0}});
+                const FilterMeta &m = meta[e.slot];
+                desc.push_back(slot_desc(c, e.slot, m.n + 2 * (int)e.idx.size(), m.sens_n, m.wait_n));
                 JoinDesc j = {};
                 j.src_off = (int64_t)table[e.rec];
                 j.n_A = m.n, j.m = (int32_t)e.idx.size(), j.ld_B = recs[e.rec].n + 1, j.idx_off = (int32_t)idx.size();
@@ -1526,43 +1624,34 @@ int aslam_join_maps(aslam_ctx *c, const int32_t *records, const int32_t *trajs, 
                 }
                 jdesc.push_back(j);
                 idx.insert(idx.end(), e.idx.begin(), e.idx.end());
-                n_max = std::max(n_max, n_new);
         }
         const int joined = (int)desc.size();
         if (joined == 0)
                 return ASLAM_OK;
-        int64_t off = 64 + snap_pad64(8 * (int64_t)joined);
-        for (SnapDesc &d : desc)
-        {
-                d.off = off;
-                off += snap_pad64(snap_record_bytes(d.n, d.sens_n, d.wait_n));
-        }
-        const int64_t total = off;
+        const Placed placed = place_records(desc);
 
         // ---- staging: descriptors | join descriptors | index lists | a host blob's copy | the records; then pack, unpack, the sighting record
-        const size_t o_jd = (size_t)snap_pad64((int64_t)sizeof(SnapDesc) * joined);
-        const size_t o_idx = o_jd + sizeof(JoinDesc) * joined;
-        const size_t o_src = o_idx + (size_t)snap_pad64(4 * (int64_t)idx.size());
-        const size_t o_blob = o_src + (is_device ? 0 : (size_t)snap_pad64((int64_t)h.total_bytes));
-        if ((rc = snap_reserve(c, o_blob + (size_t)total)) != ASLAM_OK)
+        Staging s{c};
+        const size_t o_desc = s.take(sizeof(SnapDesc) * joined), o_jd = s.take(sizeof(JoinDesc) * joined), o_idx = s.take(sizeof(int32_t) * idx.size());
+        const size_t o_src = s.take(is_device ? 0 : (size_t)h.total_bytes), o_blob = s.take((size_t)placed.total);
+        if ((rc = s.reserve()) != ASLAM_OK)
                 return rc;
-        char *sd = c->snap_dev;
-        HIP_TRY(hipMemcpy(sd, desc.data(), sizeof(SnapDesc) * joined, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(sd + o_jd, jdesc.data(), sizeof(JoinDesc) * joined, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(sd + o_idx, idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice));
+        const SnapDesc *ddev = s.at<SnapDesc>(o_desc);
+        const JoinDesc *jdev = s.at<JoinDesc>(o_jd);
+        HIP_TRY(hipMemcpy(s.at<SnapDesc>(o_desc), desc.data(), sizeof(SnapDesc) * joined, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s.at<JoinDesc>(o_jd), jdesc.data(), sizeof(JoinDesc) * joined, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s.at<int32_t>(o_idx), idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice));
         const char *src = static_cast<const char *>(blob);
         if (!is_device)
         {
-                HIP_TRY(hipMemcpy(sd + o_src, blob, (size_t)h.total_bytes, hipMemcpyHostToDevice));
-                src = sd + o_src;
+                HIP_TRY(hipMemcpy(s.at<char>(o_src), blob, (size_t)h.total_bytes, hipMemcpyHostToDevice));
+                src = s.at<char>(o_src);
         }
-        const SnapDesc *ddev = reinterpret_cast<const SnapDesc *>(sd);
-        const JoinDesc *jdev = reinterpret_cast<const JoinDesc *>(sd + o_jd);
-        char *out = sd + o_blob;
+        char *out = s.at<char>(o_blob);
         const SnapCtx sc = snap_ctx(c);
         c->last_stream = st;
-        hipLaunchKernelGGL(join_pack, snap_grid((int64_t)n_max * (n_max + 1) / 2, joined), dim3(SNAP_WG), 0, st, sc, ddev, jdev,
-                           reinterpret_cast<const int32_t *>(sd + o_idx), joined, (uint32_t)c->cfg.filter, (uint64_t)total, src, out);
+        hipLaunchKernelGGL(join_pack, snap_grid((int64_t)placed.n_max * (placed.n_max + 1) / 2, joined), dim3(SNAP_WG), 0, st, sc, ddev, jdev,
+                           (const int32_t *)s.at<int32_t>(o_idx), joined, (uint32_t)c->cfg.filter, (uint64_t)placed.total, src, out);
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(snapshot_unpack, snap_grid((int64_t)c->NP * c->NP / 2, joined), dim3(SNAP_WG), 0, st, sc, ddev, joined, (const char *)out);
         HIP_TRY(hipGetLastError());
@@ -1571,59 +1660,14 @@ int aslam_join_maps(aslam_ctx *c, const int32_t *records, const int32_t *trajs, 
                            dv.lm_hits);
         HIP_TRY(hipGetLastError());
         // the mask of the last callback, as after aslam_remove_landmarks
-        for (const SnapDesc &q : desc)
-                HIP_TRY(hipMemsetAsync(dv.sighted + (size_t)q.slot * (c->NP / 2), 0, (size_t)c->NP / 2, st));
-        return ASLAM_OK;
+        return clear_sighted(c, desc, st);
 }
 
 /* ---- removing landmarks (prune.h) ------------------------------------------------------------------------------------ */
-namespace
-{
-/// snap_reserve that keeps the first `keep` bytes of the old block when it has to grow
-int snap_reserve_keep(aslam_ctx *c, size_t bytes, size_t keep)
-{
-        if (bytes <= c->snap_cap)
-                return ASLAM_OK;
-        void *q = nullptr;
-        HIP_TRY(hipMalloc(&q, bytes));
-        hipError_t e = keep ? hipMemcpy(q, c->snap_dev, keep, hipMemcpyDeviceToDevice) : hipSuccess;
-        if (e != hipSuccess)
-        {
-                (void)hipFree(q);
-                HIP_TRY(e);
-        }
-        if (c->snap_dev)
-                (void)hipFree(c->snap_dev);
-        c->snap_dev = static_cast<char *>(q);
-        c->snap_cap = bytes;
-        return ASLAM_OK;
-}
-
-/// rows a mask must have: the landmarks a filter of this context can hold, (max_landmark_count - 3) / 2 rounded up
-int landmark_capacity(const aslam_ctx *c)
-{
-        return std::max(0, (c->cfg.max_landmark_count - 2) / 2);
-}
-
-/// null, or which of the arguments the two calls share is refused
-const char *bad_mask(const aslam_ctx *c, const void *mask, int ld, int is_device)
-{
-        if (!c)
-                return "null context";
-        if (!mask)
-                return "null mask";
-        if (ld < landmark_capacity(c))
-                return "ld is smaller than the context's landmark capacity, (max_landmark_count - 3) / 2 rounded up";
-        if (is_device && ((uintptr_t)mask & 15))
-                return "a device mask must be 16-byte aligned";
-        return nullptr;
-}
-} // namespace
-
 int aslam_select_beyond(aslam_ctx *c, const double *max_range, uint8_t *mask_dev, int ld, void *stream)
 {
-        if (const char *e = bad_mask(c, mask_dev, ld, 1))
-                return fail(ASLAM_ERR_ARG, std::string("aslam_select_beyond: ") + e);
+        if (const std::string e = bad_mask(c, mask_dev, ld, 1, "mask"); !e.empty())
+                return fail(ASLAM_ERR_ARG, "aslam_select_beyond: " + e);
         if (!max_range)
                 return fail(ASLAM_ERR_ARG, "aslam_select_beyond: null max_range");
         const int B = c->cfg.batch;
@@ -1650,8 +1694,8 @@ int aslam_select_beyond(aslam_ctx *c, const double *max_range, uint8_t *mask_dev
 
 int aslam_select_stale(aslam_ctx *c, const uint32_t *max_age, uint8_t *mask_dev, int ld, void *stream)
 {
-        if (const char *e = bad_mask(c, mask_dev, ld, 1))
-                return fail(ASLAM_ERR_ARG, std::string("aslam_select_stale: ") + e);
+        if (const std::string e = bad_mask(c, mask_dev, ld, 1, "mask"); !e.empty())
+                return fail(ASLAM_ERR_ARG, "aslam_select_stale: " + e);
         if (!max_age)
                 return fail(ASLAM_ERR_ARG, "aslam_select_stale: null max_age");
         const int B = c->cfg.batch;
@@ -1671,212 +1715,215 @@ int aslam_select_stale(aslam_ctx *c, const uint32_t *max_age, uint8_t *mask_dev,
 
 namespace
 {
-/// aslam_remove_landmarks behind its argument checks and the synchronisation of the context.  The staging begins `base` bytes into the
-/// context's block: what a caller keeps in front of it (aslam_merge_landmarks: its plan, with the mask at mask_off when `mask` is null)
-/// survives.  meta_out (may be null) receives what prune_map reported: n and n_new of every filter.
-int remove_landmarks_at(aslam_ctx *c, const uint8_t *mask, size_t mask_off, int ld, int is_device, hipStream_t st, size_t base,
-                        std::vector<PruneMeta> *meta_out)
+/// a mask on the device: a pointer, or (null) the mask at offset `off` of the context's staging block, wherever the block lies by then
+struct DevMask
+{
+        const uint8_t *ptr = nullptr;
+        size_t off = 0;
+        const uint8_t *get(const Staging &s) const { return ptr ? ptr : s.at<uint8_t>(off); }
+};
+
+/// the remove path's own front part of the staging: descriptors | what prune_map reports | the survivor lists.  A caller that launches work
+/// on its own sections before remove_landmarks_at takes these too before it reserves, so that the block does not move under that work.
+struct RemoveFront
+{
+        size_t desc, meta, src;
+};
+RemoveFront remove_front(Staging &s)
+{
+        const size_t B = (size_t)s.c->cfg.batch;
+        return RemoveFront{s.take(sizeof(SnapDesc) * B), s.take(sizeof(PruneMeta) * B), s.take(sizeof(int) * (size_t)s.c->NP * B)};
+}
+
+/// aslam_remove_landmarks behind its argument checks and the synchronisation of the context.  `s`: the sections the caller holds in the
+/// staging block (aslam_merge_landmarks: its plan, with the mask among them), which survive; this call's sections follow them.  The mask is
+/// `host_mask` or, when that is null, `mask`.  meta_out (may be null) receives what prune_map reported: n and n_new of every filter.
+int remove_landmarks_at(aslam_ctx *c, Staging s, DevMask mask, const uint8_t *host_mask, int ld, hipStream_t st, std::vector<PruneMeta> *meta_out)
 {
         int rc;
         const int B = c->cfg.batch;
-        const size_t NP = (size_t)c->NP;
         // staging: descriptors | what prune_map reports | the survivor lists | a host mask's copy | the records
-        const size_t o_meta = base + (size_t)snap_pad64((int64_t)sizeof(SnapDesc) * B);
-        const size_t o_src = o_meta + (size_t)snap_pad64((int64_t)sizeof(PruneMeta) * B);
-        const size_t o_mask = o_src + (size_t)snap_pad64((int64_t)(sizeof(int) * NP) * B);
-        const size_t o_blob = o_mask + (is_device ? 0 : (size_t)snap_pad64((int64_t)B * ld));
-        if ((rc = base ? snap_reserve_keep(c, o_blob, base) : snap_reserve(c, o_blob)) != ASLAM_OK)
+        const size_t held = s.size;
+        const RemoveFront o = remove_front(s);
+        if (host_mask)
+                mask = DevMask{nullptr, s.take((size_t)B * ld)};
+        if ((rc = s.reserve(held)) != ASLAM_OK)
                 return rc;
-        const uint8_t *mdev = mask ? mask : reinterpret_cast<const uint8_t *>(c->snap_dev + mask_off);
-        if (!is_device)
-        {
-                HIP_TRY(hipMemcpy(c->snap_dev + o_mask, mask, (size_t)B * ld, hipMemcpyHostToDevice));
-                mdev = reinterpret_cast<const uint8_t *>(c->snap_dev + o_mask);
-        }
+        if (host_mask)
+                HIP_TRY(hipMemcpy(s.at<uint8_t>(mask.off), host_mask, (size_t)B * ld, hipMemcpyHostToDevice));
         c->last_stream = st;
-        hipLaunchKernelGGL(prune_map, dim3((unsigned)B), dim3(PRUNE_WAVE), 0, st, mdev, ld, (const int *)c->dv.n, (const int *)c->dv.sens_n,
-                           (const int *)c->dv.wait_n, c->NP, reinterpret_cast<int *>(c->snap_dev + o_src),
-                           reinterpret_cast<PruneMeta *>(c->snap_dev + o_meta));
+        hipLaunchKernelGGL(prune_map, dim3((unsigned)B), dim3(PRUNE_WAVE), 0, st, mask.get(s), ld, (const int *)c->dv.n, (const int *)c->dv.sens_n,
+                           (const int *)c->dv.wait_n, c->NP, s.at<int>(o.src), s.at<PruneMeta>(o.meta));
         HIP_TRY(hipGetLastError());
         // the one copy and the one synchronisation of the call: n, n_new and the list sizes of the batch
         std::vector<PruneMeta> meta((size_t)B);
-        HIP_TRY(hipMemcpyAsync(meta.data(), c->snap_dev + o_meta, sizeof(PruneMeta) * B, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(meta.data(), s.at<PruneMeta>(o.meta), sizeof(PruneMeta) * B, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         if (meta_out)
                 *meta_out = meta;
         std::vector<SnapDesc> desc;
-        int n_max = 3;
         for (int b = 0; b < B; ++b)
         {
                 const PruneMeta &m = meta[b];
-                if (m.n < 3 || !(m.n & 1) || m.n >= c->cfg.max_landmark_count || (size_t)m.n > NP)
+                if (bad_dimension(c, m.n))
                         return fail(ASLAM_ERR_STATE, "a filter of the context has an invalid dimension");
                 if (m.n_new < 3 || !(m.n_new & 1) || m.n_new > m.n)
                         return fail(ASLAM_ERR_STATE, "aslam_remove_landmarks: the survivor count of filter " + std::to_string(b) + " is invalid");
                 if (m.n_new == m.n)
                         continue; // loses nothing: not touched at all
-                desc.push_back(SnapDesc{0, b, m.n_new, std::min(std::max(m.sens_n, 0), c->dv.max_obs), std::min(std::max(m.wait_n, 0), c->dv.max_wait), {0, 0}});
-                n_max = std::max(n_max, m.n_new);
+                desc.push_back(slot_desc(c, b, m.n_new, m.sens_n, m.wait_n));
         }
         const int count = (int)desc.size();
         if (count == 0)
                 return ASLAM_OK;
-        int64_t off = 64 + snap_pad64(8 * (int64_t)count);
-        for (SnapDesc &d : desc)
-        {
-                d.off = off;
-                off += snap_pad64(snap_record_bytes(d.n, d.sens_n, d.wait_n));
-        }
-        const int64_t total = off;
-        if ((rc = snap_reserve_keep(c, o_blob + (size_t)total, o_blob)) != ASLAM_OK)
+        const Placed placed = place_records(desc);
+        // (the records' size is known only now: the block may move once more, with everything in front of the records; the mask is not read again)
+        const size_t o_blob = s.take((size_t)placed.total);
+        if ((rc = s.reserve(o_blob)) != ASLAM_OK)
                 return rc;
-        HIP_TRY(hipMemcpy(c->snap_dev + base, desc.data(), sizeof(SnapDesc) * count, hipMemcpyHostToDevice));
-        mdev = nullptr; // (the block may have moved; the mask is not read again)
-        const SnapDesc *ddev = reinterpret_cast<const SnapDesc *>(c->snap_dev + base);
-        char *blob = c->snap_dev + o_blob;
+        HIP_TRY(hipMemcpy(s.at<SnapDesc>(o.desc), desc.data(), sizeof(SnapDesc) * count, hipMemcpyHostToDevice));
+        const SnapDesc *ddev = s.at<SnapDesc>(o.desc);
+        char *blob = s.at<char>(o_blob);
         const SnapCtx sc = snap_ctx(c);
-        hipLaunchKernelGGL(prune_pack, snap_grid((int64_t)n_max * (n_max + 1) / 2, count), dim3(SNAP_WG), 0, st, sc, ddev, count, (uint32_t)c->cfg.filter,
-                           (uint64_t)total, reinterpret_cast<const int *>(c->snap_dev + o_src), blob);
+        PruneSrc ps = {};
+        ps.src = s.at<int>(o.src); // (s, the slot's list, is set per record)
+        hipLaunchKernelGGL(record_pack<PruneSrc>, snap_grid((int64_t)placed.n_max * (placed.n_max + 1) / 2, count), dim3(SNAP_WG), 0, st, sc, ddev, count,
+                           (uint32_t)c->cfg.filter, (uint64_t)placed.total, ps, blob);
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(snapshot_unpack, snap_grid((int64_t)c->NP * c->NP / 2, count), dim3(SNAP_WG), 0, st, sc, ddev, count, (const char *)blob);
         HIP_TRY(hipGetLastError());
         // the sighting record follows its landmarks; the clock stays (a restore clears both, a prune must not: the kernel is launched here, not in the unpack)
-        hipLaunchKernelGGL(sight_compact, dim3((unsigned)B), dim3(PRUNE_WAVE), 0, st, reinterpret_cast<const int *>(c->snap_dev + o_src),
-                           reinterpret_cast<const PruneMeta *>(c->snap_dev + o_meta), c->NP, c->dv.lm_seen, c->dv.lm_hits);
+        hipLaunchKernelGGL(sight_compact, dim3((unsigned)B), dim3(PRUNE_WAVE), 0, st, (const int *)s.at<int>(o.src), (const PruneMeta *)s.at<PruneMeta>(o.meta),
+                           c->NP, c->dv.lm_seen, c->dv.lm_hits);
         HIP_TRY(hipGetLastError());
         // the mask of the last callback indexes landmarks that have moved: zero in every filter that lost one
-        for (const SnapDesc &q : desc)
-                HIP_TRY(hipMemsetAsync(c->dv.sighted + (size_t)q.slot * (c->NP / 2), 0, (size_t)c->NP / 2, st));
-        return ASLAM_OK;
+        return clear_sighted(c, desc, st);
 }
 } // namespace
 
 int aslam_remove_landmarks(aslam_ctx *c, const uint8_t *mask, int ld, int is_device, void *stream)
 {
-        if (const char *e = bad_mask(c, mask, ld, is_device))
-                return fail(ASLAM_ERR_ARG, std::string("aslam_remove_landmarks: ") + e);
+        if (const std::string e = bad_mask(c, mask, ld, is_device, "mask"); !e.empty())
+                return fail(ASLAM_ERR_ARG, "aslam_remove_landmarks: " + e);
         int rc = sync_ctx(c);
         if (rc != ASLAM_OK)
                 return rc;
-        return remove_landmarks_at(c, mask, 0, ld, is_device, static_cast<hipStream_t>(stream), 0, nullptr);
+        return remove_landmarks_at(c, Staging{c}, is_device ? DevMask{mask, 0} : DevMask{}, is_device ? nullptr : mask, ld, static_cast<hipStream_t>(stream),
+                                   nullptr);
 }
 
 /* ---- merging duplicate landmarks (merge.h) ----------------------------------------------------------------------------- */
 namespace
 {
-/// aslam_merge_landmarks.  With `ms` (aslam_debug_merge_rate): plan and the first round's merge_gain as in the call, then that round's
-/// merge_downdate 3 + reps times, each between two device events, and nothing else -- the filters are left mid-merge, for timing alone.
-int merge_landmarks_run(aslam_ctx *c, const int32_t *into, int ld, int is_device, double noise_var, int32_t *merged_out, void *stream, int reps, float *ms)
+/// what the plan stage of a merge leaves behind (the pointers into the staging block hold until the remove path reserves its records)
+struct MergePlan
 {
-        if (const char *e = bad_mask(c, into, ld, is_device))
-        {
-                std::string m(e);
-                for (size_t at; (at = m.find("mask")) != std::string::npos;)
-                        m.replace(at, 4, "into");
-                return fail(ASLAM_ERR_ARG, "aslam_merge_landmarks: " + m);
-        }
+        Staging s;     // the call's own sections ...
+        size_t o_mask; // ... and the removal mask among them
+        hipStream_t st;
+        MergeMeta *meta_dev;
+        int32_t *pi, *pj, *stop;
+        uint8_t *mask;
+        double *V, *P;
+        std::vector<MergeMeta> meta;
+        int ldm, max_count, T; // max_count: pairs of the filter with the most; T: tiles per dimension of the largest filter that merges
+};
+
+/// aslam_merge_landmarks up to the first round: the checks, the staging, merge_plan and its report.  No filter is written.
+int merge_plan_stage(aslam_ctx *c, const int32_t *into, int ld, int is_device, double noise_var, hipStream_t st, MergePlan &p)
+{
+        if (const std::string e = bad_mask(c, into, ld, is_device, "into"); !e.empty())
+                return fail(ASLAM_ERR_ARG, "aslam_merge_landmarks: " + e);
         if (!std::isfinite(noise_var) || noise_var < 0.0)
                 return fail(ASLAM_ERR_ARG, "aslam_merge_landmarks: noise_var must be finite and not negative");
         int rc = sync_ctx(c);
         if (rc != ASLAM_OK)
                 return rc;
-        const int B = c->cfg.batch, NP = c->NP;
-        const int ldm = (ld + 15) & ~15;
-        hipStream_t st = static_cast<hipStream_t>(stream);
-        // staging in front of the remove path's: the plan's report | pairs (i) | pairs (j) | removal mask | stop flags | V | a host array's copy
-        const size_t o_pi = (size_t)snap_pad64((int64_t)sizeof(MergeMeta) * B);
-        const size_t o_pj = o_pi + (size_t)snap_pad64(4 * (int64_t)B * ldm);
-        const size_t o_mask = o_pj + (size_t)snap_pad64(4 * (int64_t)B * ldm);
-        const size_t o_stop = o_mask + (size_t)snap_pad64((int64_t)B * ldm);
-        const size_t o_V = o_stop + (size_t)snap_pad64(4 * (int64_t)B);
-        const size_t o_into = o_V + (size_t)snap_pad64(8 * (int64_t)B * MERGE_K * NP);
-        const size_t base = o_into + (is_device ? 0 : (size_t)snap_pad64(4 * (int64_t)B * ld));
-        // (with the remove path's descriptors, report and survivor lists behind it: the block does not move while the rounds are in flight)
-        const size_t behind = (size_t)(snap_pad64((int64_t)sizeof(SnapDesc) * B) + snap_pad64((int64_t)sizeof(PruneMeta) * B) + snap_pad64(4 * (int64_t)NP * B));
-        if ((rc = snap_reserve(c, base + behind)) != ASLAM_OK)
+        const size_t B = (size_t)c->cfg.batch, NP = (size_t)c->NP, ldm = ((size_t)ld + 15) & ~(size_t)15;
+        // staging: the plan's report | pairs (i) | pairs (j) | removal mask | stop flags | V | a host array's copy
+        Staging s{c};
+        const size_t o_meta = s.take(sizeof(MergeMeta) * B), o_pi = s.take(4 * B * ldm), o_pj = s.take(4 * B * ldm);
+        p.o_mask = s.take(B * ldm);
+        const size_t o_stop = s.take(4 * B), o_V = s.take(8 * B * MERGE_K * NP), o_into = s.take(is_device ? 0 : 4 * B * (size_t)ld);
+        p.s = s;
+        // (with the remove path's front part behind it: the block does not move while the rounds are in flight)
+        remove_front(s);
+        if ((rc = s.reserve()) != ASLAM_OK)
                 return rc;
         const int32_t *idev = into;
         if (!is_device)
         {
-                HIP_TRY(hipMemcpy(c->snap_dev + o_into, into, sizeof(int32_t) * B * ld, hipMemcpyHostToDevice));
-                idev = reinterpret_cast<const int32_t *>(c->snap_dev + o_into);
+                HIP_TRY(hipMemcpy(s.at<int32_t>(o_into), into, sizeof(int32_t) * B * ld, hipMemcpyHostToDevice));
+                idev = s.at<int32_t>(o_into);
         }
-        char *sd = c->snap_dev;
-        MergeMeta *meta_dev = reinterpret_cast<MergeMeta *>(sd);
-        int32_t *pi = reinterpret_cast<int32_t *>(sd + o_pi), *pj = reinterpret_cast<int32_t *>(sd + o_pj), *stop = reinterpret_cast<int32_t *>(sd + o_stop);
-        uint8_t *mask = reinterpret_cast<uint8_t *>(sd + o_mask);
-        double *V = reinterpret_cast<double *>(sd + o_V);
+        p.st = st, p.ldm = (int)ldm, p.meta_dev = s.at<MergeMeta>(o_meta), p.mask = s.at<uint8_t>(p.o_mask);
+        p.pi = s.at<int32_t>(o_pi), p.pj = s.at<int32_t>(o_pj), p.stop = s.at<int32_t>(o_stop);
+        p.V = s.at<double>(o_V), p.P = c->large ? c->largeP : c->dv.P;
         c->last_stream = st;
-        hipLaunchKernelGGL(merge_plan, dim3((unsigned)B), dim3(PRUNE_WAVE), 0, st, idev, ld, (const int *)c->dv.n, NP, ldm, pi, pj, mask, stop, meta_dev);
+        hipLaunchKernelGGL(merge_plan, dim3((unsigned)B), dim3(PRUNE_WAVE), 0, st, idev, ld, (const int *)c->dv.n, c->NP, p.ldm, p.pi, p.pj, p.mask, p.stop,
+                           p.meta_dev);
         HIP_TRY(hipGetLastError());
         // the plan's report, checked before any filter is written: a refused call leaves the context as it was
-        std::vector<MergeMeta> meta((size_t)B);
-        HIP_TRY(hipMemcpyAsync(meta.data(), meta_dev, sizeof(MergeMeta) * B, hipMemcpyDeviceToHost, st));
+        p.meta.resize(B);
+        HIP_TRY(hipMemcpyAsync(p.meta.data(), p.meta_dev, sizeof(MergeMeta) * B, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        int max_count = 0, max_L = 0;
-        for (int b = 0; b < B; ++b)
+        int max_L = p.max_count = 0;
+        for (size_t b = 0; b < B; ++b)
         {
-                const MergeMeta &m = meta[b];
+                const MergeMeta &m = p.meta[b];
                 if (m.bad_j >= 0)
                         return fail(ASLAM_ERR_ARG, "aslam_merge_landmarks: filter " + std::to_string(b) + ", landmark " + std::to_string(m.bad_j) + ": into = " +
                                                        std::to_string(m.bad_i) + " (needs 0 <= into < landmark, and a root that is not merged away itself)");
-                max_count = std::max(max_count, m.count);
+                p.max_count = std::max(p.max_count, m.count);
                 if (m.count > 0)
                         max_L = std::max(max_L, m.L);
         }
-        if (merged_out)
-                std::fill(merged_out, merged_out + B, 0);
-        if (max_count == 0)
-                return ASLAM_OK;
-        double *P = c->large ? c->largeP : c->dv.P;
-        const int T = (3 + 2 * max_L + MERGE_TILE - 1) / MERGE_TILE;
-        for (int r = 0; r * MERGE_ROUND < max_count; ++r)
-        {
-                hipLaunchKernelGGL(merge_gain, dim3((unsigned)B), dim3(MERGE_WG), 0, st, c->dv.X, (const double *)P, (const int *)c->dv.n, NP, ldm,
-                                   (const int32_t *)pi, (const int32_t *)pj, (const MergeMeta *)meta_dev, r, noise_var, V, mask, stop);
-                HIP_TRY(hipGetLastError());
-                if (ms)
-                {
-                        hipEvent_t e0, e1;
-                        HIP_TRY(hipEventCreate(&e0));
-                        HIP_TRY(hipEventCreate(&e1));
-                        for (int k = -3; k < reps; ++k)
-                        {
-                                HIP_TRY(hipEventRecord(e0, st));
-                                hipLaunchKernelGGL(merge_downdate, dim3((unsigned)(T * (T + 1) / 2), (unsigned)B), dim3(MERGE_WG), 0, st, P, (const int *)c->dv.n,
-                                                   NP, (const MergeMeta *)meta_dev, r, (const double *)V, (const int32_t *)stop);
-                                HIP_TRY(hipEventRecord(e1, st));
-                                HIP_TRY(hipEventSynchronize(e1));
-                                float t = 0.f;
-                                HIP_TRY(hipEventElapsedTime(&t, e0, e1));
-                                if (k >= 0)
-                                        ms[k] = t;
-                        }
-                        (void)hipEventDestroy(e0);
-                        (void)hipEventDestroy(e1);
-                        return ASLAM_OK;
-                }
-                hipLaunchKernelGGL(merge_downdate, dim3((unsigned)(T * (T + 1) / 2), (unsigned)B), dim3(MERGE_WG), 0, st, P, (const int *)c->dv.n, NP,
-                                   (const MergeMeta *)meta_dev, r, (const double *)V, (const int32_t *)stop);
-                HIP_TRY(hipGetLastError());
-        }
-        hipLaunchKernelGGL(merge_sightings, dim3((unsigned)B), dim3(PRUNE_WAVE), 0, st, (const uint32_t *)c->dv.clock, c->dv.lm_seen, c->dv.lm_hits, NP, ldm,
-                           (const int32_t *)pi, (const int32_t *)pj, (const MergeMeta *)meta_dev, (const uint8_t *)mask);
-        HIP_TRY(hipGetLastError());
-        // the merged-away landmarks leave through the remove path itself, with the mask the plan wrote (less what a failed pivot took out)
-        std::vector<PruneMeta> pm;
-        if ((rc = remove_landmarks_at(c, nullptr, o_mask, ldm, 1, st, base, &pm)) != ASLAM_OK)
-                return rc;
-        if (merged_out)
-                for (int b = 0; b < B; ++b)
-                        merged_out[b] = (pm[b].n - pm[b].n_new) / 2;
+        p.T = (3 + 2 * max_L + MERGE_TILE - 1) / MERGE_TILE;
         return ASLAM_OK;
+}
+
+/// round r of a planned merge, in its two launches
+void launch_merge_gain(aslam_ctx *c, const MergePlan &p, int r, double noise_var)
+{
+        hipLaunchKernelGGL(merge_gain, dim3((unsigned)c->cfg.batch), dim3(MERGE_WG), 0, p.st, c->dv.X, (const double *)p.P, (const int *)c->dv.n, c->NP, p.ldm,
+                           (const int32_t *)p.pi, (const int32_t *)p.pj, (const MergeMeta *)p.meta_dev, r, noise_var, p.V, p.mask, p.stop);
+}
+void launch_merge_downdate(aslam_ctx *c, const MergePlan &p, int r)
+{
+        hipLaunchKernelGGL(merge_downdate, dim3((unsigned)(p.T * (p.T + 1) / 2), (unsigned)c->cfg.batch), dim3(MERGE_WG), 0, p.st, p.P, (const int *)c->dv.n,
+                           c->NP, (const MergeMeta *)p.meta_dev, r, (const double *)p.V, (const int32_t *)p.stop);
 }
 } // namespace
 
 int aslam_merge_landmarks(aslam_ctx *c, const int32_t *into, int ld, int is_device, double noise_var, int32_t *merged_out, void *stream)
 {
-        return merge_landmarks_run(c, into, ld, is_device, noise_var, merged_out, stream, 0, nullptr);
+        MergePlan p;
+        int rc = merge_plan_stage(c, into, ld, is_device, noise_var, static_cast<hipStream_t>(stream), p);
+        if (rc != ASLAM_OK)
+                return rc;
+        const int B = c->cfg.batch;
+        if (merged_out)
+                std::fill(merged_out, merged_out + B, 0);
+        if (p.max_count == 0)
+                return ASLAM_OK;
+        for (int r = 0; r * MERGE_ROUND < p.max_count; ++r)
+        {
+                launch_merge_gain(c, p, r, noise_var);
+                HIP_TRY(hipGetLastError());
+                launch_merge_downdate(c, p, r);
+                HIP_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(merge_sightings, dim3((unsigned)B), dim3(PRUNE_WAVE), 0, p.st, (const uint32_t *)c->dv.clock, c->dv.lm_seen, c->dv.lm_hits, c->NP,
+                           p.ldm, (const int32_t *)p.pi, (const int32_t *)p.pj, (const MergeMeta *)p.meta_dev, (const uint8_t *)p.mask);
+        HIP_TRY(hipGetLastError());
+        // the merged-away landmarks leave through the remove path itself, with the mask the plan wrote (less what a failed pivot took out)
+        std::vector<PruneMeta> pm;
+        if ((rc = remove_landmarks_at(c, p.s, DevMask{nullptr, p.o_mask}, nullptr, p.ldm, p.st, &pm)) != ASLAM_OK)
+                return rc;
+        if (merged_out)
+                for (int b = 0; b < B; ++b)
+                        merged_out[b] = (pm[b].n - pm[b].n_new) / 2;
+        return ASLAM_OK;
 }
 
 /* diagnostic (tools/merge_rate.py): merge_downdate alone.  The plan and the first round's gain of aslam_merge_landmarks(into_dev), then that
@@ -1886,18 +1933,35 @@ int aslam_debug_merge_rate(aslam_ctx *c, const int32_t *into_dev, int ld, double
 {
         if (!ms || reps < 1)
                 return fail(ASLAM_ERR_ARG, "null argument");
-        return merge_landmarks_run(c, into_dev, ld, 1, noise_var, nullptr, nullptr, reps, ms);
+        MergePlan p;
+        int rc = merge_plan_stage(c, into_dev, ld, 1, noise_var, nullptr, p);
+        if (rc != ASLAM_OK || p.max_count == 0)
+                return rc;
+        launch_merge_gain(c, p, 0, noise_var);
+        HIP_TRY(hipGetLastError());
+        hipEvent_t e0, e1;
+        HIP_TRY(hipEventCreate(&e0));
+        HIP_TRY(hipEventCreate(&e1));
+        for (int k = -3; k < reps; ++k)
+        {
+                HIP_TRY(hipEventRecord(e0, p.st));
+                launch_merge_downdate(c, p, 0);
+                HIP_TRY(hipEventRecord(e1, p.st));
+                HIP_TRY(hipEventSynchronize(e1));
+                float t = 0.f;
+                HIP_TRY(hipEventElapsedTime(&t, e0, e1));
+                if (k >= 0)
+                        ms[k] = t;
+        }
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        return ASLAM_OK;
 }
 
 int aslam_select_duplicates(aslam_ctx *c, const double *gate, const double *max_dist, int32_t *into_dev, int ld, void *stream)
 {
-        if (const char *e = bad_mask(c, into_dev, ld, 1))
-        {
-                std::string m(e);
-                for (size_t at; (at = m.find("mask")) != std::string::npos;)
-                        m.replace(at, 4, "into");
-                return fail(ASLAM_ERR_ARG, "aslam_select_duplicates: " + m);
-        }
+        if (const std::string e = bad_mask(c, into_dev, ld, 1, "into"); !e.empty())
+                return fail(ASLAM_ERR_ARG, "aslam_select_duplicates: " + e);
         if (!gate || !max_dist)
                 return fail(ASLAM_ERR_ARG, "aslam_select_duplicates: null gate or max_dist");
         const int B = c->cfg.batch;
@@ -1912,16 +1976,18 @@ int aslam_select_duplicates(aslam_ctx *c, const double *gate, const double *max_
                 par[(size_t)B + b] = gate[b];
         }
         int rc = sync_ctx(c);
-        const size_t o_partner = (size_t)snap_pad64(16 * (int64_t)B);
+        // staging: max_dist^2, gate | every landmark's partner
+        Staging s{c};
+        const size_t o_par = s.take(sizeof(double) * 2 * B), o_partner = s.take(sizeof(int32_t) * B * ld);
         if (rc == ASLAM_OK)
-                rc = snap_reserve(c, o_partner + (size_t)snap_pad64(4 * (int64_t)B * ld));
+                rc = s.reserve();
         if (rc != ASLAM_OK)
                 return rc;
-        HIP_TRY(hipMemcpy(c->snap_dev, par.data(), sizeof(double) * 2 * B, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s.at<double>(o_par), par.data(), sizeof(double) * 2 * B, hipMemcpyHostToDevice));
         hipStream_t st = static_cast<hipStream_t>(stream);
         c->last_stream = st;
-        const double *pd = reinterpret_cast<const double *>(c->snap_dev);
-        int32_t *partner = reinterpret_cast<int32_t *>(c->snap_dev + o_partner);
+        const double *pd = s.at<double>(o_par);
+        int32_t *partner = s.at<int32_t>(o_partner);
         const int wpb = MERGE_WG / PRUNE_WAVE;
         hipLaunchKernelGGL(merge_select, dim3((unsigned)((ld + wpb - 1) / wpb), (unsigned)B), dim3(MERGE_WG), 0, st, (const double *)c->dv.X,
                            (const double *)(c->large ? c->largeP : c->dv.P), (const int *)c->dv.n, c->NP, pd, pd + B, partner, ld);
@@ -1965,26 +2031,26 @@ int aslam_gate_observations(aslam_ctx *c, const float *obs, int ldo, int is_devi
                 return fail(ASLAM_ERR_ARG, who + "mdist_dev must be 16-byte aligned");
         int rc = sync_ctx(c);
         // staging: gate | n_obs | a host array's copy
-        const size_t o_n = (size_t)snap_pad64(8 * (int64_t)B);
-        const size_t o_obs = o_n + (size_t)snap_pad64(4 * (int64_t)B);
         const size_t obs_bytes = sizeof(float) * 2 * (size_t)B * ldo;
+        Staging s{c};
+        const size_t o_gate = s.take(sizeof(double) * B), o_n = s.take(sizeof(int32_t) * B), o_obs = s.take(is_device ? 0 : obs_bytes);
         if (rc == ASLAM_OK)
-                rc = snap_reserve(c, o_obs + (is_device ? 0 : (size_t)snap_pad64((int64_t)obs_bytes)));
+                rc = s.reserve();
         if (rc != ASLAM_OK)
                 return rc;
-        HIP_TRY(hipMemcpy(c->snap_dev, gate, sizeof(double) * B, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->snap_dev + o_n, n_obs, sizeof(int32_t) * B, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s.at<double>(o_gate), gate, sizeof(double) * B, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s.at<int32_t>(o_n), n_obs, sizeof(int32_t) * B, hipMemcpyHostToDevice));
         const float *odev = obs;
         if (!is_device)
         {
-                HIP_TRY(hipMemcpy(c->snap_dev + o_obs, obs, obs_bytes, hipMemcpyHostToDevice));
-                odev = reinterpret_cast<const float *>(c->snap_dev + o_obs);
+                HIP_TRY(hipMemcpy(s.at<float>(o_obs), obs, obs_bytes, hipMemcpyHostToDevice));
+                odev = s.at<float>(o_obs);
         }
         hipStream_t st = static_cast<hipStream_t>(stream);
         c->last_stream = st;
         hipLaunchKernelGGL(assoc_gate, dim3((unsigned)B), dim3(ASSOC_WG), 0, st, (const double *)c->dv.X, (const double *)(c->large ? c->largeP : c->dv.P),
-                           (const int *)c->dv.n, c->NP, (const aslam_params *)c->params_dev, odev, ldo, reinterpret_cast<const int32_t *>(c->snap_dev + o_n),
-                           reinterpret_cast<const double *>(c->snap_dev), assoc_dev, mdist_dev);
+                           (const int *)c->dv.n, c->NP, (const aslam_params *)c->params_dev, odev, ldo, (const int32_t *)s.at<int32_t>(o_n),
+                           (const double *)s.at<double>(o_gate), assoc_dev, mdist_dev);
         HIP_TRY(hipGetLastError());
         return ASLAM_OK;
 }
@@ -1996,19 +2062,27 @@ int aslam_debug_snapshot_rate(aslam_ctx *c, void *dev_buf, int64_t cap_bytes, in
 {
         if (!c || !dev_buf || !ms || !info || reps < 1)
                 return fail(ASLAM_ERR_ARG, "null argument");
-        int64_t total = 0;
-        int rc = aslam_snapshot(c, nullptr, 0, nullptr, 0, 1, &total, nullptr);
+        // the whole batch, described and placed as aslam_snapshot does it (the first pack of the loop below fills the blob the unpacks read)
+        const int count = c->cfg.batch;
+        std::vector<SnapDesc> hdesc;
+        Placed placed = {};
+        Staging s{c};
+        const size_t o_desc = s.take(sizeof(SnapDesc) * count);
+        int rc = sync_ctx(c);
+        if (rc == ASLAM_OK)
+                rc = snap_describe(c, nullptr, count, nullptr, hdesc, placed);
+        const int64_t total = placed.total;
         if (rc == ASLAM_OK && cap_bytes < 2 * total)
                 rc = fail(ASLAM_ERR_ARG, "aslam_debug_snapshot_rate needs twice the snapshot's size");
         if (rc == ASLAM_OK)
-                rc = aslam_snapshot(c, nullptr, 0, dev_buf, total, 1, nullptr, nullptr); // leaves the descriptors of the batch on the device
+                rc = s.reserve();
         if (rc != ASLAM_OK)
                 return rc;
-        HIP_TRY(hipStreamSynchronize(nullptr));
+        const SnapDesc *desc = s.at<SnapDesc>(o_desc);
+        HIP_TRY(hipMemcpy(s.at<SnapDesc>(o_desc), hdesc.data(), sizeof(SnapDesc) * count, hipMemcpyHostToDevice));
         const SnapCtx sc = snap_ctx(c);
-        const SnapDesc *desc = reinterpret_cast<const SnapDesc *>(c->snap_dev);
-        const int count = c->snap_count;
         char *blob = static_cast<char *>(dev_buf);
+        c->last_stream = nullptr;
         auto bytes = [&](auto m) { return per_filter(c->dv, m) * sizeof(*(c->dv.*m)); }; // (P: the large path's has the same shape)
         info[0] = total;
         info[1] = (int64_t)count * (int64_t)(bytes(&DevView::X) + bytes(&DevView::Z) + bytes(&DevView::P) + bytes(&DevView::sens) +
@@ -2024,8 +2098,7 @@ int aslam_debug_snapshot_rate(aslam_ctx *c, void *dev_buf, int64_t cap_bytes, in
                 {
                         HIP_TRY(hipEventRecord(e0, nullptr));
                         if (what == 0)
-                                hipLaunchKernelGGL(snapshot_pack, snap_grid((int64_t)c->snap_nmax * (c->snap_nmax + 1) / 2, count), dim3(SNAP_WG), 0, nullptr,
-                                                   sc, desc, count, (uint32_t)c->cfg.filter, (uint64_t)total, blob);
+                                launch_snapshot_pack(c, desc, count, placed, blob, nullptr);
                         else if (what == 1)
                                 hipLaunchKernelGGL(snapshot_unpack, snap_grid((int64_t)c->NP * c->NP / 2, count), dim3(SNAP_WG), 0, nullptr, sc, desc, count,
                                                    (const char *)blob);

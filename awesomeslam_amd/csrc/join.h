@@ -1,14 +1,14 @@
 // join.h -- aslam_join_maps (include/aslam_snapshot.h): put the landmarks of a snapshot record, with their covariance block, behind the state
 // of a running filter on the device.
 //
-//   join_meta      n, the init flags and the list sizes of every filter of the batch, packed for the one copy to the host
 //   join_pack      one complete record of snapshot.h per joined filter: the filter's OWN record, X, Z and P extended by the selected landmarks
-//                  of the source record, moved into the filter's frame -- what snapshot_pack would have written had the filter held them
+//                  of the source record, moved into the filter's frame -- what a snapshot would hold had the filter held them
 //   sight_extend   the sighting record of every joined filter, extended as aslam_grow extends it (last_seen = clock, hits = 0)
 //
 // The records then go through snapshot_unpack, unchanged, into their own slots, as the records of prune.h do: the slot becomes a fresh one of
-// the larger dimension, and the zero padding, the cleared scratch and every kernel family's layout stay that one piece of code.  join_pack
-// takes every size from its descriptors, which the host wrote after validation; it reads nothing of the source record but the X and P
+// the larger dimension, and the zero padding, the cleared scratch and every kernel family's layout stay that one piece of code.  The lists
+// and headers of the record come from snapshot.h's one writer; join_pack keeps the loop of record_pack as a kernel of its own, since as a
+// source of that template it needed more registers and scratch (profiles/record_writer.md).  It takes every size from its descriptors, which the host wrote after validation; it reads nothing of the source record but the X and P
 // entries of the selected landmarks (the selected-index list holds indices below the record's landmark count by construction).
 #pragma once
 
@@ -25,20 +25,6 @@ struct JoinDesc
         double cov[9];                  // covariance of (tx, ty, phi)
 };
 static_assert(sizeof(JoinDesc) == 128, "16-byte multiples: the descriptors are read as they lie in the staging block");
-
-/// what join_meta reports per filter
-struct JoinMeta
-{
-        int32_t n, flags, sens_n, wait_n;
-};
-
-__global__ __launch_bounds__(PRUNE_WAVE) void join_meta(const int *__restrict__ n, const int *__restrict__ flags, const int *__restrict__ sens_n,
-                                                        const int *__restrict__ wait_n, int B, JoinMeta *__restrict__ meta)
-{
-        const int b = blockIdx.x * PRUNE_WAVE + threadIdx.x;
-        if (b < B)
-                meta[b] = JoinMeta{n[b], flags[b], sens_n[b], wait_n[b]};
-}
 
 /// the wrap of device_common.h's normalizeAngle (tools.h:44-50), in binary64
 __device__ __forceinline__ double join_wrap(double theta)
@@ -97,9 +83,9 @@ __device__ __forceinline__ double join_P(const JoinDesc &j, const JoinSrc &s, co
         return a >= b ? join_entry(j, s, a, b) : join_entry(j, s, b, a);
 }
 
-/// The grid of snapshot_pack (row chunks x records).  d.n of a descriptor is the NEW dimension.  The new columns start at the odd index n_A:
+/// The grid and the loop of record_pack (row chunks x records).  d.n of a descriptor is the NEW dimension.  The new columns start at the odd index n_A:
 /// a double2 at an even column straddles the old state and the first new landmark, and later two landmarks, so each half has a source of
-/// its own (as in prune_pack); pairs that lie wholly in the old block are moved 16 bytes at a time.
+/// its own (as in PruneSrc); pairs that lie wholly in the old block are moved 16 bytes at a time.
 __global__ __launch_bounds__(SNAP_WG) void join_pack(SnapCtx c, const SnapDesc *__restrict__ desc, const JoinDesc *__restrict__ jdesc,
                                                      const int32_t *__restrict__ idx, int count, uint32_t filter, uint64_t total,
                                                      const char *__restrict__ src, char *__restrict__ blob)
@@ -135,7 +121,7 @@ __global__ __launch_bounds__(SNAP_WG) void join_pack(SnapCtx c, const SnapDesc *
                 }
                 if (blockIdx.x != 0)
                         continue;
-                // workgroup 0 of the record: X, Z, the lists, the record header, the table entry, the padding behind the record
+                // workgroup 0 of the record: X, Z, then everything else
                 const double *xa = c.X + slot * NP, *za = c.Z + slot * NP;
                 const double ax = xa[0], ay = xa[1], ath = xa[2];
                 double *Xout = reinterpret_cast<double *>(rec + 64), *Zout = Xout + ld;
@@ -155,47 +141,7 @@ __global__ __launch_bounds__(SNAP_WG) void join_pack(SnapCtx c, const SnapDesc *
                         Xout[i] = x;
                         Zout[i] = z;
                 }
-                float *sens = reinterpret_cast<float *>(rec + 64 + 8 * (size_t)ld * (n + 2));
-                float *wrb = sens + 2 * d.sens_n;
-                uint32_t *wcnt = reinterpret_cast<uint32_t *>(wrb + 2 * d.wait_n);
-                for (int i = tid; i < 2 * d.sens_n; i += SNAP_WG)
-                        sens[i] = c.sens[slot * c.max_obs * 2 + i];
-                for (int i = tid; i < 2 * d.wait_n; i += SNAP_WG)
-                        wrb[i] = c.wait_rb[slot * c.max_wait * 2 + i];
-                for (int i = tid; i < d.wait_n; i += SNAP_WG)
-                        wcnt[i] = c.wait_cnt[slot * c.max_wait + i];
-                uint32_t *end = wcnt + d.wait_n;
-                const int tail = (int)((64 - (end - reinterpret_cast<uint32_t *>(rec)) * 4 % 64) % 64) / 4;
-                for (int i = tid; i < tail; i += SNAP_WG)
-                        end[i] = 0u;
-                if (tid == 0)
-                {
-                        SnapRecHeader r = {};
-                        r.n = n;
-                        r.flags = c.flags[slot] & SNAP_KNOWN_FLAGS;
-                        r.status = c.status[slot];
-                        r.sens_n = d.sens_n;
-                        r.wait_n = d.wait_n;
-                        r.ld = ld;
-                        r.A[0] = c.A[2 * slot];
-                        r.A[1] = c.A[2 * slot + 1];
-                        *reinterpret_cast<SnapRecHeader *>(rec) = r;
-                        reinterpret_cast<uint64_t *>(blob + 64)[f] = (uint64_t)d.off;
-                }
-                if (f == 0 && tid == 64)
-                {
-                        SnapBlobHeader bh = {};
-                        const char m[8] = {'A', 'S', 'L', 'S', 'N', 'P', '0', '1'};
-                        for (int i = 0; i < 8; ++i)
-                                bh.magic[i] = m[i];
-                        bh.version = SNAP_VERSION;
-                        bh.filter = filter;
-                        bh.count = (uint32_t)count;
-                        bh.total_bytes = total;
-                        *reinterpret_cast<SnapBlobHeader *>(blob) = bh;
-                        for (int i = count; i & 7; ++i)
-                                reinterpret_cast<uint64_t *>(blob + 64)[i] = 0;
-                }
+                snap_write_lists_and_headers(c, d, f, count, filter, total, rec, blob);
         }
 }
 

@@ -2,8 +2,8 @@
 //
 //   prune_select_beyond   mask[b][i] = 1 where landmark i of filter b lies farther than max_range[b] from the filter's own pose
 //   prune_map             mask row + n of the filter -> the survivor list src[b][0 .. n_new) (source index of every kept row) and n_new[b]
-//   prune_pack            one complete record of snapshot.h per pruned filter, X, Z and P gathered through src: what snapshot_pack would
-//                         have written had the filter never held the removed landmarks
+//   PruneSrc              the source of record_pack (snapshot.h) that gathers X, Z and P through src: one complete record per pruned filter,
+//                         what a snapshot would hold had the filter never held the removed landmarks
 //
 //   prune_select_stale    mask[b][i] = 1 where landmark i of filter b was last sighted more than max_age[b] callbacks ago (the sighting record)
 //   sight_compact         the sighting record of every filter that lost something, moved in place through prune_map's survivor list
@@ -11,8 +11,8 @@
 //
 // The records then go through snapshot_unpack, unchanged, into their own slots: a slot whose dimension shrank is made a FRESH one exactly as
 // a restored slot is (zero padding, cleared scratch -- see the top of snapshot.h), and no second piece of code has to know what "fresh" means.
-// prune_pack takes every size from its descriptors, which the host validated; src holds indices below the padded dimension by construction
-// (prune_map clamps the landmark count it reads to what the padded row holds).
+// The record's lists and headers are written by snapshot.h's one writer.  record_pack takes every size from its descriptors, which the host
+// validated; src holds indices below the padded dimension by construction (prune_map clamps the landmark count it reads to what the row holds).
 #pragma once
 
 #include "snapshot.h"
@@ -21,7 +21,7 @@ namespace aslam
 {
 constexpr int PRUNE_WAVE = 64;
 
-/// what prune_map reports per filter, for the one copy to the host
+/// what prune_map reports per filter, for the one copy to the host: FilterMeta (snapshot.h) with n_new where the flags are, which no prune reads
 struct PruneMeta
 {
         int32_t n, n_new, sens_n, wait_n;
@@ -147,86 +147,24 @@ __global__ __launch_bounds__(PRUNE_WAVE) void sight_clear(const SnapDesc *__rest
                 lm_seen[slot * H + i] = 0u, lm_hits[slot * H + i] = 0u;
 }
 
-/// The grid of snapshot_pack (row chunks x records).  d.n of a descriptor is the NEW dimension; src is indexed by the slot.  A double2 at an
-/// even column straddles two landmarks (column 3 + 2i is odd), so each half has a source of its own.
-__global__ __launch_bounds__(SNAP_WG) void prune_pack(SnapCtx c, const SnapDesc *__restrict__ desc, int count, uint32_t filter, uint64_t total,
-                                                      const int *__restrict__ src, char *__restrict__ blob)
+/// The source of record_pack (snapshot.h) for a pruned filter.  d.n of a descriptor is the NEW dimension; src is indexed by the slot.  A double2
+/// at an even column straddles two landmarks (column 3 + 2i is odd), so each half has a source of its own: two indexed loads per pair.
+struct PruneSrc : SnapshotSrc
 {
-        const int tid = threadIdx.x;
-        const size_t NP = (size_t)c.NP;
-        for (int f = blockIdx.y; f < count; f += gridDim.y)
+        const int *src, *s; // prune_map's survivor lists [B][NP], the slot's
+        __device__ void begin(const SnapCtx &c, const SnapDesc &d, int f)
         {
-                const SnapDesc d = desc[f];
-                const int n = d.n, ld = n + 1, h = ld / 2;
-                const size_t slot = (size_t)d.slot;
-                const int *s = src + slot * NP;
-                char *rec = blob + d.off;
-                double2 *Pout = reinterpret_cast<double2 *>(rec + 64 + 16 * (size_t)ld);
-                const double *Pin = c.P + slot * NP * NP;
-                const int units = n * h;
-                for (int i = blockIdx.x * SNAP_WG + tid; i < units; i += gridDim.x * SNAP_WG)
-                {
-                        const int r = i / h, q = i - r * h;
-                        const double *prow = Pin + (size_t)s[r] * NP;
-                        double2 v;
-                        v.x = prow[s[2 * q]];
-                        v.y = 2 * q + 1 < n ? prow[s[2 * q + 1]] : 0.0;
-                        Pout[i] = v;
-                }
-                if (blockIdx.x != 0)
-                        continue;
-                // workgroup 0 of the record: X, Z, the lists, the record header, the table entry, the padding behind the record
-                double2 *Xout = reinterpret_cast<double2 *>(rec + 64);
-                for (int i = tid; i < 2 * h; i += SNAP_WG)
-                {
-                        const int q = i < h ? i : i - h;
-                        const double *in = (i < h ? c.X : c.Z) + slot * NP;
-                        double2 v;
-                        v.x = in[s[2 * q]];
-                        v.y = 2 * q + 1 < n ? in[s[2 * q + 1]] : 0.0;
-                        Xout[i] = v;
-                }
-                float *sens = reinterpret_cast<float *>(rec + 64 + 8 * (size_t)ld * (n + 2));
-                float *wrb = sens + 2 * d.sens_n;
-                uint32_t *wcnt = reinterpret_cast<uint32_t *>(wrb + 2 * d.wait_n);
-                for (int i = tid; i < 2 * d.sens_n; i += SNAP_WG)
-                        sens[i] = c.sens[slot * c.max_obs * 2 + i];
-                for (int i = tid; i < 2 * d.wait_n; i += SNAP_WG)
-                        wrb[i] = c.wait_rb[slot * c.max_wait * 2 + i];
-                for (int i = tid; i < d.wait_n; i += SNAP_WG)
-                        wcnt[i] = c.wait_cnt[slot * c.max_wait + i];
-                uint32_t *end = wcnt + d.wait_n;
-                const int tail = (int)((64 - (end - reinterpret_cast<uint32_t *>(rec)) * 4 % 64) % 64) / 4;
-                for (int i = tid; i < tail; i += SNAP_WG)
-                        end[i] = 0u;
-                if (tid == 0)
-                {
-                        SnapRecHeader r = {};
-                        r.n = n;
-                        r.flags = c.flags[slot] & SNAP_KNOWN_FLAGS;
-                        r.status = c.status[slot];
-                        r.sens_n = d.sens_n;
-                        r.wait_n = d.wait_n;
-                        r.ld = ld;
-                        r.A[0] = c.A[2 * slot];
-                        r.A[1] = c.A[2 * slot + 1];
-                        *reinterpret_cast<SnapRecHeader *>(rec) = r;
-                        reinterpret_cast<uint64_t *>(blob + 64)[f] = (uint64_t)d.off;
-                }
-                if (f == 0 && tid == 64)
-                {
-                        SnapBlobHeader bh = {};
-                        const char m[8] = {'A', 'S', 'L', 'S', 'N', 'P', '0', '1'};
-                        for (int i = 0; i < 8; ++i)
-                                bh.magic[i] = m[i];
-                        bh.version = SNAP_VERSION;
-                        bh.filter = filter;
-                        bh.count = (uint32_t)count;
-                        bh.total_bytes = total;
-                        *reinterpret_cast<SnapBlobHeader *>(blob) = bh;
-                        for (int i = count; i & 7; ++i)
-                                reinterpret_cast<uint64_t *>(blob + 64)[i] = 0;
-                }
+                SnapshotSrc::begin(c, d, f);
+                s = src + (size_t)d.slot * NP;
         }
-}
+        __device__ double2 pair(const double *p, int q) const
+        {
+                double2 v;
+                v.x = p[s[2 * q]];
+                v.y = 2 * q + 1 < n ? p[s[2 * q + 1]] : 0.0;
+                return v;
+        }
+        __device__ double2 P(int r, int q) const { return pair(Pin + (size_t)s[r] * NP, q); }
+        __device__ double2 XZ(int z, int q) const { return pair(z ? Zin : Xin, q); }
+};
 } // namespace aslam

@@ -1,7 +1,8 @@
 // snapshot.h -- include/aslam_snapshot.h: the record format on the host, and the kernels that move records between a blob and a context's
 // padded layout.
 //
-//   snapshot_pack     strided gather: rows of P with stride NP -> rows with stride ld = n + 1, X, Z, the lists, the headers and the table
+//   record_pack<Src>  writes records: X, Z and P from a source (SnapshotSrc here: a strided gather, rows of P with stride NP -> rows with stride
+//                     ld = n + 1), then the lists, the headers and the table through snap_write_lists_and_headers -- the one writer of the format
 //   snapshot_unpack   the reverse scatter, which also makes the slot a FRESH one: a filter only grows in a normal run, so no filter kernel
 //                     has ever seen a slot whose dimension shrank, and they rely on never-written padding staying zero.  The whole padded
 //                     P, X and Z are written (zero from n on), the lists are zero beyond their counts, and the slot's share of the
@@ -136,84 +137,110 @@ inline const char *snap_check_offset(uint64_t off, int64_t table_end, uint64_t t
 
 // ---- device --------------------------------------------------------------------------------------------------------
 
-__global__ __launch_bounds__(SNAP_WG) void snapshot_pack(SnapCtx c, const SnapDesc *__restrict__ desc, int count, uint32_t filter,
-                                                         uint64_t total, char *__restrict__ blob)
+/// Everything of record f that is not X, Z or P (the lists, the zero tail, both headers, the table entry), for every kernel that writes records;
+/// called by all lanes of workgroup 0 of the record.  This function and snapshot_unpack are the two places that know the record format.
+__device__ __forceinline__ void snap_write_lists_and_headers(const SnapCtx &c, const SnapDesc &d, int f, int count, uint32_t filter, uint64_t total,
+                                                             char *rec, char *__restrict__ blob)
 {
         const int tid = threadIdx.x;
-        const size_t NP = (size_t)c.NP;
+        const int n = d.n, ld = n + 1;
+        const size_t slot = (size_t)d.slot;
+        float *sens = reinterpret_cast<float *>(rec + 64 + 8 * (size_t)ld * (n + 2));
+        float *wrb = sens + 2 * d.sens_n;
+        uint32_t *wcnt = reinterpret_cast<uint32_t *>(wrb + 2 * d.wait_n);
+        for (int i = tid; i < 2 * d.sens_n; i += SNAP_WG)
+                sens[i] = c.sens[slot * c.max_obs * 2 + i];
+        for (int i = tid; i < 2 * d.wait_n; i += SNAP_WG)
+                wrb[i] = c.wait_rb[slot * c.max_wait * 2 + i];
+        for (int i = tid; i < d.wait_n; i += SNAP_WG)
+                wcnt[i] = c.wait_cnt[slot * c.max_wait + i];
+        uint32_t *end = wcnt + d.wait_n; // (4-byte units: every section is a multiple of 4 bytes)
+        const int tail = (int)((64 - (end - reinterpret_cast<uint32_t *>(rec)) * 4 % 64) % 64) / 4;
+        for (int i = tid; i < tail; i += SNAP_WG) // the padding behind the record
+                end[i] = 0u;
+        if (tid == 0)
+        {
+                SnapRecHeader r = {};
+                r.n = n;
+                r.flags = c.flags[slot] & SNAP_KNOWN_FLAGS;
+                r.status = c.status[slot];
+                r.sens_n = d.sens_n;
+                r.wait_n = d.wait_n;
+                r.ld = ld;
+                r.A[0] = c.A[2 * slot];
+                r.A[1] = c.A[2 * slot + 1];
+                *reinterpret_cast<SnapRecHeader *>(rec) = r;
+                reinterpret_cast<uint64_t *>(blob + 64)[f] = (uint64_t)d.off;
+        }
+        if (f == 0 && tid == 64) // (the second wave of record 0's workgroup: the first one's lane 0 writes the record header)
+        {
+                SnapBlobHeader bh = {};
+                const char m[8] = {'A', 'S', 'L', 'S', 'N', 'P', '0', '1'};
+                for (int i = 0; i < 8; ++i)
+                        bh.magic[i] = m[i];
+                bh.version = SNAP_VERSION;
+                bh.filter = filter;
+                bh.count = (uint32_t)count;
+                bh.total_bytes = total;
+                *reinterpret_cast<SnapBlobHeader *>(blob) = bh;
+                for (int i = count; i & 7; ++i) // the table's padding to 64 bytes
+                        reinterpret_cast<uint64_t *>(blob + 64)[i] = 0;
+        }
+}
+
+/// One complete record per descriptor into `blob`.  Src, passed by value, says where X, Z and P come from: begin(c, d, f) is the per-record
+/// setup (d.n: the dimension written), P(r, q) columns 2q, 2q + 1 of row r of P -- the last pair of a row is (P(r, n-1), 0) -- and XZ(z, q)
+/// entries 2q, 2q + 1 of X (z = 0) or Z (z = 1), padded the same way.  The sources: SnapshotSrc below, PruneSrc (prune.h).
+template <class Src>
+__global__ __launch_bounds__(SNAP_WG) void record_pack(SnapCtx c, const SnapDesc *__restrict__ desc, int count, uint32_t filter, uint64_t total, Src src,
+                                                       char *__restrict__ blob)
+{
+        const int tid = threadIdx.x;
         for (int f = blockIdx.y; f < count; f += gridDim.y)
         {
                 const SnapDesc d = desc[f];
                 const int n = d.n, ld = n + 1, h = ld / 2;
-                const size_t slot = (size_t)d.slot;
+                src.begin(c, d, f);
                 char *rec = blob + d.off;
-                // P: n rows of ld, two doubles per access; the last pair of a row is (P(r, n-1), 0)
+                // P: n rows of ld, two doubles per access
                 double2 *Pout = reinterpret_cast<double2 *>(rec + 64 + 16 * (size_t)ld);
-                const double *Pin = c.P + slot * NP * NP;
                 const int units = n * h;
                 for (int i = blockIdx.x * SNAP_WG + tid; i < units; i += gridDim.x * SNAP_WG)
                 {
                         const int r = i / h, q = i - r * h;
-                        double2 v = *reinterpret_cast<const double2 *>(Pin + (size_t)r * NP + 2 * q);
-                        if (2 * q + 1 >= n)
-                                v.y = 0.0;
-                        Pout[i] = v;
+                        Pout[i] = src.P(r, q);
                 }
                 if (blockIdx.x != 0)
                         continue;
-                // workgroup 0 of the record: X, Z, the lists, the record header, the table entry, the padding behind the record
+                // workgroup 0 of the record: X, Z, then everything else
                 double2 *Xout = reinterpret_cast<double2 *>(rec + 64);
                 for (int i = tid; i < 2 * h; i += SNAP_WG)
-                {
-                        const int q = i < h ? i : i - h;
-                        double2 v = *reinterpret_cast<const double2 *>((i < h ? c.X : c.Z) + slot * NP + 2 * q);
-                        if (2 * q + 1 >= n)
-                                v.y = 0.0;
-                        Xout[i] = v;
-                }
-                float *sens = reinterpret_cast<float *>(rec + 64 + 8 * (size_t)ld * (n + 2));
-                float *wrb = sens + 2 * d.sens_n;
-                uint32_t *wcnt = reinterpret_cast<uint32_t *>(wrb + 2 * d.wait_n);
-                for (int i = tid; i < 2 * d.sens_n; i += SNAP_WG)
-                        sens[i] = c.sens[slot * c.max_obs * 2 + i];
-                for (int i = tid; i < 2 * d.wait_n; i += SNAP_WG)
-                        wrb[i] = c.wait_rb[slot * c.max_wait * 2 + i];
-                for (int i = tid; i < d.wait_n; i += SNAP_WG)
-                        wcnt[i] = c.wait_cnt[slot * c.max_wait + i];
-                uint32_t *end = wcnt + d.wait_n; // (4-byte units: every section is a multiple of 4 bytes)
-                const int tail = (int)((64 - (end - reinterpret_cast<uint32_t *>(rec)) * 4 % 64) % 64) / 4;
-                for (int i = tid; i < tail; i += SNAP_WG)
-                        end[i] = 0u;
-                if (tid == 0)
-                {
-                        SnapRecHeader r = {};
-                        r.n = n;
-                        r.flags = c.flags[slot] & SNAP_KNOWN_FLAGS;
-                        r.status = c.status[slot];
-                        r.sens_n = d.sens_n;
-                        r.wait_n = d.wait_n;
-                        r.ld = ld;
-                        r.A[0] = c.A[2 * slot];
-                        r.A[1] = c.A[2 * slot + 1];
-                        *reinterpret_cast<SnapRecHeader *>(rec) = r;
-                        reinterpret_cast<uint64_t *>(blob + 64)[f] = (uint64_t)d.off;
-                }
-                if (f == 0 && tid == 64)
-                {
-                        SnapBlobHeader bh = {};
-                        const char m[8] = {'A', 'S', 'L', 'S', 'N', 'P', '0', '1'};
-                        for (int i = 0; i < 8; ++i)
-                                bh.magic[i] = m[i];
-                        bh.version = SNAP_VERSION;
-                        bh.filter = filter;
-                        bh.count = (uint32_t)count;
-                        bh.total_bytes = total;
-                        *reinterpret_cast<SnapBlobHeader *>(blob) = bh;
-                        for (int i = count; i & 7; ++i) // the table's padding to 64 bytes
-                                reinterpret_cast<uint64_t *>(blob + 64)[i] = 0;
-                }
+                        Xout[i] = src.XZ(i >= h, i < h ? i : i - h);
+                snap_write_lists_and_headers(c, d, f, count, filter, total, rec, blob);
         }
 }
+
+/// the slot as it lies in the context: rows of stride NP, one 16-byte load per pair (NP is a multiple of 16)
+struct SnapshotSrc
+{
+        const double *Pin, *Xin, *Zin; // the slot's P, X, Z
+        size_t NP;
+        int n;
+        __device__ void begin(const SnapCtx &c, const SnapDesc &d, int)
+        {
+                NP = (size_t)c.NP, n = d.n;
+                Pin = c.P + (size_t)d.slot * NP * NP, Xin = c.X + (size_t)d.slot * NP, Zin = c.Z + (size_t)d.slot * NP;
+        }
+        __device__ double2 pair(const double *p, int q) const
+        {
+                double2 v = *reinterpret_cast<const double2 *>(p + 2 * q);
+                if (2 * q + 1 >= n)
+                        v.y = 0.0;
+                return v;
+        }
+        __device__ double2 P(int r, int q) const { return pair(Pin + (size_t)r * NP, q); }
+        __device__ double2 XZ(int z, int q) const { return pair(z ? Zin : Xin, q); }
+};
 
 __global__ __launch_bounds__(SNAP_WG) void snapshot_unpack(SnapCtx c, const SnapDesc *__restrict__ desc, int count, const char *__restrict__ blob)
 {
@@ -300,6 +327,21 @@ __global__ __launch_bounds__(SNAP_WG) void snapshot_gather(const char *__restric
         const int i = blockIdx.x * SNAP_WG + threadIdx.x; // 16 bytes each: four lanes per header
         if (i < 4 * count)
                 reinterpret_cast<uint4 *>(out)[i] = reinterpret_cast<const uint4 *>(blob + off[i >> 2])[i & 3];
+}
+
+/// n, the init flags and the list sizes of a filter, for the host: what a call needs to know of the batch before it can describe records
+struct FilterMeta
+{
+        int32_t n, flags, sens_n, wait_n;
+};
+
+/// lanes over filters: the batch's FilterMeta into one array, for one copy to the host
+__global__ __launch_bounds__(64) void filter_meta(const int *__restrict__ n, const int *__restrict__ flags, const int *__restrict__ sens_n,
+                                                  const int *__restrict__ wait_n, int B, FilterMeta *__restrict__ meta)
+{
+        const int b = blockIdx.x * 64 + threadIdx.x;
+        if (b < B)
+                meta[b] = FilterMeta{n[b], flags[b], sens_n[b], wait_n[b]};
 }
 
 /// grid of a pack / unpack launch: `units` 16-byte accesses of the largest record, four per lane

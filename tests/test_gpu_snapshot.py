@@ -431,3 +431,77 @@ def test_device_blob_on_a_side_stream(case, built):
     assert pg.shape == (3, T - k, 3)
     a.close()
     b.close()
+
+
+# ---- 8. the record writer's edges ---------------------------------------------------------------------------------------------------
+EDGE_CAP, EDGE_OBS, EDGE_WAIT = 24, 4, 6
+# slot -> (n, sens_n, wait_n): sens_n in {0, 1, max_obs}, wait_n in {0, 1, 2, 5, max_wait}; the zeroed tail behind the nine records is
+# 32, 28, 40, 0, 52, 48, 16, 56 and 4 bytes long
+EDGE_SHAPES = [(3, 0, 0), (5, 1, 1), (17, EDGE_OBS, EDGE_WAIT), (3, EDGE_OBS, 0), (5, 0, 5), (17, 1, 2), (3, 1, EDGE_WAIT), (5, EDGE_OBS, 2), (17, 0, 1)]
+
+
+@functools.lru_cache(maxsize=None)
+def edge_records():
+    """nine host records of random content; the n = 5 ones are not waiting for their first callback (a join needs that)"""
+    rng = np.random.default_rng(41)
+    out = []
+    for i, (n, s, w) in enumerate(EDGE_SHAPES):
+        F = rng.standard_normal((n, n))
+        P = F @ F.T / n * 0.02 + 0.01 * np.eye(n)
+        out.append(dict(n=n, flags=(3, 0, 2)[i % 3], status=(0, 1, 4, 16, 31)[i % 5], A=rng.standard_normal(2), X=0.5 * rng.standard_normal(n),
+                        Z=rng.standard_normal(n), P=np.tril(P) + np.tril(P, -1).T, sens=rng.standard_normal((s, 2)).astype(np.float32),
+                        wait_rb=rng.standard_normal((w, 2)).astype(np.float32), wait_cnt=rng.integers(1, 2 ** 32, w, dtype=np.uint32)))
+    return out
+
+
+@pytest.mark.parametrize("kind", ["ekf", "ukf"])
+def test_record_bytes_round_trip(kind, built):
+    """Records whose lists are empty, hold one entry or are full, so that the zeroed tail behind a record takes nine lengths (0 included) and the
+    offset table is padded or not: what the device writes equals snapshot.pack of the same records byte for byte -- as they were restored, after
+    a prune (prune_ref on the host) and after a join (everything but the appended block, which is held to join_ref's bar)."""
+    import torch
+
+    import join_ref as jr
+    import prune_ref
+    from awesomeslam_amd.core import Core, core_lib
+    from test_gpu_join import blob_of, check
+
+    recs = edge_records()
+    host = snapshot.pack(recs, kind)
+    assert snapshot.pack(snapshot.parse(host), kind).tobytes() == host.tobytes()  # the reference writes what it reads
+    sizes = [int(core_lib().aslam_snapshot_record_bytes(*shape)) for shape in EDGE_SHAPES]
+    assert sizes == [snapshot.record_bytes(*shape) for shape in EDGE_SHAPES]
+    tails = {-b % 64 for b in sizes}
+    assert len(tails) == 9 and 0 in tails and all(t % 4 == 0 for t in tails)
+
+    core = Core(kind, EDGE_CAP, batch=9, max_obs=EDGE_OBS, max_wait=EDGE_WAIT)
+    core.restore(host)
+    for count in (1, 8, 9):  # 8: no table padding; 9: the table is padded to 16 entries
+        assert core.snapshot(trajs=list(range(count))).tobytes() == snapshot.pack(recs[:count], kind).tobytes(), count
+    # from a device blob, into other slots
+    perm = [4, 8, 0, 7, 2, 6, 1, 5, 3]
+    core.restore(torch.from_numpy(host).cuda(), records=perm, trajs=list(range(9)))
+    torch.cuda.synchronize()
+    now = [recs[p] for p in perm]
+    assert core.snapshot().tobytes() == snapshot.pack(now, kind).tobytes()
+    assert core.snapshot(trajs=[8, 3]).tobytes() == snapshot.pack([now[8], now[3]], kind).tobytes()
+
+    # after a prune: landmark 0 of the n = 17 slots
+    mask = np.zeros((9, core.landmark_capacity()), np.uint8)
+    mask[[b for b in range(9) if now[b]["n"] == 17], 0] = 1
+    core.remove_landmarks(mask)
+    now = [prune_ref.prune_record(r, [0]) if r["n"] == 17 else r for r in now]
+    assert core.snapshot().tobytes() == snapshot.pack(now, kind).tobytes()
+
+    # after a join of one landmark into an n = 5 slot, identity frame, zero covariance
+    b = next(b for b in range(9) if now[b]["n"] == 5 and len(now[b]["wait_cnt"]) == 5)
+    old = now[b]
+    XB, PB = np.array([0.3, -0.2, 0.1, 12.0, -7.0]), jr.spd(5, np.random.default_rng(5))
+    assert jr.clear_of(old["X"][:3], [XB[3:5]], [jr.identity()])
+    assert core.join_maps(blob_of([(XB, PB)], kind), [0], [b]).tolist() == [1]
+    Xg, Zg, Pg = check(core, b, (old["X"], old["Z"], old["P"], XB, PB), None, jr.identity(), f"edge {kind}", exact=True)
+    new = dict(old, n=7, X=np.r_[old["X"], Xg[5:]], Z=np.r_[old["Z"], Zg[5:]], P=np.zeros((7, 7)))
+    new["P"][:5, :5], new["P"][5:, 5:] = old["P"], Pg[5:, 5:]
+    now[b] = new
+    assert core.snapshot().tobytes() == snapshot.pack(now, kind).tobytes()
+    core.close()

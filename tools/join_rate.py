@@ -196,7 +196,7 @@ the record written; snapshot_unpack: the record read, the padded slot written, t
 included, that is {s['join_TB_per_s']:.2f} TB/s = **{s['join_over_copy_rate']:.2f}** of the copy rate.
 
 How to read it.  A join is the header reads of a device blob (three small copies, each with a synchronisation, as in `aslam_restore`),
-`join_meta` with the call's one copy and synchronisation, three small host-to-device copies of descriptors, then `join_pack`,
+`filter_meta` with the call's one copy and synchronisation, three small host-to-device copies of descriptors, then `join_pack`,
 `snapshot_unpack` and `sight_extend`.  It is a restore (one unpack launch) with a pack launch in front of it: the call takes
 {j['ms_median'] - r['ms_median']:.2f} ms more than the restore, beside {c['snapshot_pack_ms']:.2f} ms for `snapshot_pack` of the same records, so `join_pack` runs at about the
 rate of the plain gather; the new block is {(2 * j['joined']) ** 2 / j['n'] ** 2 * 100:.1f} % of the entries written.
