@@ -303,58 +303,56 @@ template <typename F> auto with_NT(int NT, F &&f)
         return NT == 2 ? f(std::integral_constant<int, 2>{}) : NT == 5 ? f(std::integral_constant<int, 5>{}) : f(std::integral_constant<int, 9>{});
 }
 
+/// The ONE rule of which front-end instantiation a launch of seam MODE takes (FrontendVariant, ekf_large_launch.h): "gated" exists in the
+/// replay seam alone, "sighted" on EKF contexts alone
+template <int MODE> FrontendVariant frontend_variant(const aslam_ctx *c, const StatsView &sv)
+{
+        return {sv.any(), c->cfg.filter == ASLAM_EKF && c->sighted_on, MODE == MODE_REPLAY && c->gated()};
+}
+
+/// the flags of a single-CU kernel as the template arguments of its name in aslam_kernel_info, trailing defaults (false) left out as the code writes them
+std::string variant_args(std::initializer_list<bool> flags)
+{
+        std::string s, pending;
+        for (const bool f : flags)
+                if (pending += f ? ",true" : ",false"; f)
+                        s += std::exchange(pending, std::string());
+        return s;
+}
+
 /// `sv`: the statistics this launch writes (all null: none).  The single-CU kernels have an instantiation of their own for it, the large-state
 /// chains one more launch per callback (large_stats); without statistics both run exactly what they ran before.
 template <int MODE>
 int launch(aslam_ctx *c, int grid, int64_t t0, int nsteps, double *poses, int32_t *dims, StepArgs sa, hipStream_t st, StatsView sv = {})
 {
+        const FrontendVariant fv = frontend_variant<MODE>(c, sv);
 #if ASLAM_HAVE_UKF
         if (c->large && c->cfg.filter == ASLAM_UKF)
         {
-                c->lh.gated = c->gated();
-                HIP_TRY(launch_ukf_large<MODE>(c->lh, c->dv, c->lv64, c->ukfl, c->skipped, t0, nsteps, poses, dims, sa, st, sv));
+                HIP_TRY(launch_ukf_large<MODE>(c->lh, fv, c->dv, c->lv64, c->ukfl, c->skipped, t0, nsteps, poses, dims, sa, st, sv));
                 return ASLAM_OK;
         }
 #endif
-        // aslam_set_replay_gate: the GATED instantiations, in the replay seam of a context with some gate > 0 alone; every other launch is what it was
-        const bool gated = MODE == MODE_REPLAY && c->gated();
         if (c->large)
                 return with_large_view(c, [&](auto &lv) -> int {
-                        c->lh.sighted = c->sighted_on;
-                        c->lh.gated = gated;
-                        HIP_TRY(launch_large<MODE>(c->lh, c->dv, lv, c->skipped, t0, nsteps, poses, dims, sa, st, sv));
+                        HIP_TRY(launch_large<MODE>(c->lh, fv, c->dv, lv, c->skipped, t0, nsteps, poses, dims, sa, st, sv));
                         return ASLAM_OK;
                 });
         if (c->cfg.filter == ASLAM_EKF)
                 return with_NT(c->NT, [&](auto nt) {
                         constexpr int NT = decltype(nt)::value;
-                        if constexpr (MODE == MODE_REPLAY)
-                        {
-                                if (gated && c->sighted_on)
-                                        return sv.any() ? launch_small<SmallLayout<NT>>(ekf_small_kernel<NT, MODE, true, true, true>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv)
-                                                        : launch_small<SmallLayout<NT>>(ekf_small_kernel<NT, MODE, false, true, true>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv);
-                                if (gated)
-                                        return sv.any() ? launch_small<SmallLayout<NT>>(ekf_small_kernel<NT, MODE, true, false, true>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv)
-                                                        : launch_small<SmallLayout<NT>>(ekf_small_kernel<NT, MODE, false, false, true>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv);
-                        }
-                        if (c->sighted_on) // the information-form instantiations (ekf_small.h); off: exactly the launches below
-                                return sv.any() ? launch_small<SmallLayout<NT>>(ekf_small_kernel<NT, MODE, true, true>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv)
-                                                : launch_small<SmallLayout<NT>>(ekf_small_kernel<NT, MODE, false, true>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv);
-                        return sv.any() ? launch_small<SmallLayout<NT>>(ekf_small_kernel<NT, MODE, true>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv)
-                                        : launch_small<SmallLayout<NT>>(ekf_small_kernel<NT, MODE, false>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv);
+                        const auto kern = with_variant<true, true, MODE == MODE_REPLAY>(fv, [](auto stats, auto si, auto ga) {
+                                return &ekf_small_kernel<NT, MODE, decltype(stats)::value, decltype(si)::value, decltype(ga)::value>;
+                        });
+                        return launch_small<SmallLayout<NT>>(kern, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv);
                 });
 #if ASLAM_HAVE_UKF
         if (c->cfg.filter == ASLAM_UKF)
                 return with_NT(c->NT, [&](auto nt) {
                         constexpr int NT = decltype(nt)::value;
-                        if constexpr (MODE == MODE_REPLAY)
-                        {
-                                if (gated)
-                                        return sv.any() ? launch_small<UkfLayout<NT>>(ukf_small_kernel<NT, MODE, true, true>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv, c->ukf)
-                                                        : launch_small<UkfLayout<NT>>(ukf_small_kernel<NT, MODE, false, true>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv, c->ukf);
-                        }
-                        return sv.any() ? launch_small<UkfLayout<NT>>(ukf_small_kernel<NT, MODE, true>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv, c->ukf)
-                                        : launch_small<UkfLayout<NT>>(ukf_small_kernel<NT, MODE, false>, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv, c->ukf);
+                        const auto kern = with_variant<true, false, MODE == MODE_REPLAY>(
+                                fv, [](auto stats, auto, auto ga) { return &ukf_small_kernel<NT, MODE, decltype(stats)::value, decltype(ga)::value>; });
+                        return launch_small<UkfLayout<NT>>(kern, grid, st, t0, nsteps, poses, dims, sa, sv, c->dv, c->ukf);
                 });
 #endif
         return fail(ASLAM_ERR_UNSUPPORTED, "no kernel for this filter/size");
@@ -2329,7 +2327,9 @@ int aslam_kernel_info(aslam_ctx *c, char *name, int name_cap, int *grid, int *bl
         if (!c)
                 return fail(ASLAM_ERR_ARG, "null context");
         char buf[320];
+        std::string nm;
         size_t lds = 0;
+        const FrontendVariant fv = frontend_variant<MODE_REPLAY>(c, StatsView{}); // what aslam_replay launches
         if (c->large)
         {
                 // the plan of a launch over the whole batch.  The names say which pipe each kernel's products run on (bench.py prices them from
@@ -2351,36 +2351,26 @@ int aslam_kernel_info(aslam_ctx *c, char *name, int name_cap, int *grid, int *bl
                         std::snprintf(buf, sizeof(buf), "large_trsm_pipe<17> + large_syrk_bf16x3 (%d-launch chain per callback: multi-workgroup Cholesky)", plan.launches);
                 else
                         std::snprintf(buf, sizeof(buf), "large_update_panel<double> (%d-launch chain per callback, %d stream groups)", plan.launches, c->lh.knobs.groups);
-                lds = c->gated() ? LargeLds::bytes_gated(c->NP) : LargeLds::bytes(c->NP);
-                if (c->sighted_on && c->cfg.filter == ASLAM_EKF)
-                {
-                        const std::string with = std::string("large_build_GS<T,sighted> + ") + buf;
-                        std::snprintf(buf, sizeof(buf), "%s", with.c_str());
-                }
-                if (c->gated()) // (the replay seam's front end)
-                {
-                        const std::string with = std::string(c->cfg.filter == ASLAM_EKF ? "large_frontend_kernel<T,gated> + " : "ukf_large_frontend_kernel<gated> + ") + buf;
-                        std::snprintf(buf, sizeof(buf), "%s", with.c_str());
-                }
+                // the front end's variant shows as a prefix: the sighted-only update by the G, S kernel it switches, the gate by the front end itself
+                nm = std::string(!fv.gated ? "" : c->cfg.filter == ASLAM_EKF ? "large_frontend_kernel<T,gated> + " : "ukf_large_frontend_kernel<gated> + ") +
+                     (fv.sighted ? "large_build_GS<T,sighted> + " : "") + buf;
+                lds = LargeLds::launch_bytes(c->NP, fv.gated);
         }
         else if (c->cfg.filter == ASLAM_EKF)
         {
-                if (c->gated())
-                        std::snprintf(buf, sizeof(buf), c->sighted_on ? "ekf_small_kernel<%d,0,false,true,true>" : "ekf_small_kernel<%d,0,false,false,true>", c->NT);
-                else
-                        std::snprintf(buf, sizeof(buf), c->sighted_on ? "ekf_small_kernel<%d,0,false,true>" : "ekf_small_kernel<%d,0>", c->NT);
+                nm = "ekf_small_kernel<" + std::to_string(c->NT) + ",0" + variant_args({fv.stats, fv.sighted, fv.gated}) + ">";
                 lds = with_NT(c->NT, [](auto nt) -> size_t { return SmallLayout<decltype(nt)::value>::total; });
         }
 #if ASLAM_HAVE_UKF
         else
         {
-                std::snprintf(buf, sizeof(buf), c->gated() ? "ukf_small_kernel<%d,0,false,true>" : "ukf_small_kernel<%d,0>", c->NT);
+                nm = "ukf_small_kernel<" + std::to_string(c->NT) + ",0" + variant_args({fv.stats, fv.gated}) + ">";
                 lds = with_NT(c->NT, [](auto nt) -> size_t { return UkfLayout<decltype(nt)::value>::total; });
         }
 #endif
         if (name && name_cap > 0)
         {
-                std::strncpy(name, buf, name_cap - 1);
+                std::strncpy(name, nm.c_str(), name_cap - 1);
                 name[name_cap - 1] = 0;
         }
         if (grid)

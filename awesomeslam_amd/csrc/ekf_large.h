@@ -2,7 +2,7 @@
 // n = 1027), fp64 or fp32.  One callback = a short chain of launches that use the whole GPU for one filter (and
 // `batch` filters side by side through blockIdx.y/z):
 //
-//   large_frontend   cbSensorLandmark + updateZandA (ekf.cpp:102-213, shared small_frontend code), predict
+//   large_frontend   cbSensorLandmark + updateZandA (ekf.cpp:102-213, shared small_frontend code; LDS: LargeLds = sX, sZ + the block of small_common.h), predict
 //                    (X <- f(X), P <- A P A^T + Q with A = I + 2 entries, ekf.cpp:295-297), updateH coefficients
 //                    (ekf.cpp:117-134), Y = Z - h(X) (ekf.cpp:302-307)                               1 workgroup / filter
 //   large_build_GS   G = P H^T (H has <= 5 non-zeros per row, ekf.cpp:301) and S = H G + R (ekf.cpp:300) in one pass
@@ -291,58 +291,21 @@ __host__ __device__ __forceinline__ bool border_spare(const LargeBorder &bd, int
         return bd.t && row > n && row <= n + bd.t && (col < LB * bd.nbc || (col >= LB * bd.nbc + BORDER_SAVE && col < LB * bd.nbc + BORDER_SAVE + BORDER_SAVE_ROWS));
 }
 
-// ---- LDS layout of the front-end workgroup (runtime NP) -----------------------------------------------------------
+// ---- LDS layout of the front-end workgroup (runtime NP): sX, sZ, then the association block of small_common.h with the LARGE_* capacities ----
 struct LargeLds
 {
-        static __host__ __device__ size_t bytes(int NP)
-        {
-                size_t o = 0;
-                o += 8 * (size_t)NP * 2;                  // sX, sZ
-                o += 4 * (size_t)LARGE_OBS_CAP * 6;       // sSr sSb sPx sPy sMd sCid
-                o += 4 * (size_t)LARGE_WAIT_CAP * 5;      // sWr sWb sWx sWy sWc
-                o += 4 * (size_t)(NP / 2);                // sNew
-                o += 4 * (size_t)LARGE_OBS_CAP * 4 * 2;   // sPd sPi
-                o += 4 * (size_t)NP;                      // sLm
-                o = (o + 15) & ~(size_t)15;
-                return o + sizeof(SmallShared);
-        }
-        /// the GATED front ends: the landmark table of small_frontend (six arrays of NP / 2 doubles) behind everything else
-        static __host__ __device__ size_t bytes_gated(int NP) { return bytes(NP) + 8 * (size_t)6 * (NP / 2); }
+        static __host__ __device__ constexpr size_t bytes(int NP) { return assoc_shared_at(8 * (size_t)NP * 2, LARGE_OBS_CAP, LARGE_WAIT_CAP, NP) + sizeof(SmallShared); }
+        /// the dynamic LDS of a launch: the GATED front ends keep the gate table of small_frontend behind everything else
+        static __host__ __device__ constexpr size_t launch_bytes(int NP, bool gated) { return bytes(NP) + (gated ? 8 * gate_table_doubles(NP) : 0); }
+        static __host__ __device__ constexpr size_t gate_table_at(int NP) { return bytes(NP); } // (byte offset of the table in the workgroup's LDS)
         static __device__ __forceinline__ SmallLds carve(unsigned char *smem, int NP)
         {
-                SmallLds L;
-                unsigned char *p = smem;
-                L.Lt = nullptr;
-                L.Dinv = nullptr;
-                L.sY = nullptr;
-                L.sU = nullptr;
-                L.sH = nullptr;
-                L.sTv = nullptr;
-                L.sX = reinterpret_cast<double *>(p);
-                p += 8 * (size_t)NP;
-                L.sZ = reinterpret_cast<double *>(p);
-                p += 8 * (size_t)NP;
-#define CARVE(field, type, count)                                                                                      \
-        L.field = reinterpret_cast<type *>(p);                                                                         \
-        p += sizeof(type) * (size_t)(count);
-                CARVE(sSr, float, LARGE_OBS_CAP)
-                CARVE(sSb, float, LARGE_OBS_CAP)
-                CARVE(sPx, float, LARGE_OBS_CAP)
-                CARVE(sPy, float, LARGE_OBS_CAP)
-                CARVE(sMd, float, LARGE_OBS_CAP)
-                CARVE(sCid, int, LARGE_OBS_CAP)
-                CARVE(sWr, float, LARGE_WAIT_CAP)
-                CARVE(sWb, float, LARGE_WAIT_CAP)
-                CARVE(sWx, float, LARGE_WAIT_CAP)
-                CARVE(sWy, float, LARGE_WAIT_CAP)
-                CARVE(sWc, uint32_t, LARGE_WAIT_CAP)
-                CARVE(sNew, int, NP / 2)
-                CARVE(sPd, float, LARGE_OBS_CAP * 4)
-                CARVE(sPi, int, LARGE_OBS_CAP * 4)
-                CARVE(sLm, float, NP)
-#undef CARVE
-                const size_t off = ((size_t)(p - smem) + 15) & ~(size_t)15;
-                L.sm = reinterpret_cast<SmallShared *>(smem + off);
+                SmallLds L = {};
+                AssocCarve c = {smem};
+                c(L.sX, NP);
+                c(L.sZ, NP);
+                unsigned char *const p = assoc_carve(L, c.p, LARGE_OBS_CAP, LARGE_WAIT_CAP, NP);
+                L.sm = reinterpret_cast<SmallShared *>(smem + (((size_t)(p - smem) + 15) & ~(size_t)15)); // (= assoc_shared_at)
                 return L;
         }
 };
@@ -352,7 +315,7 @@ struct LargeLds
 /// callback returned early (no sensor message yet): the rest of the chain then leaves the filter alone.
 /// SIGHTED (aslam_sighted_update_enable): Y is zeroed in the rows of the landmarks this callback did not sight (DevView::sighted, which the front
 /// end has just written in replay and the host has copied down for a step); large_build_GS<T, true> does the rest.
-/// GATED (aslam_set_replay_gate, MODE_REPLAY only; LargeLds::bytes_gated of dynamic LDS): the front end associates by the Mahalanobis gate in the
+/// GATED (aslam_set_replay_gate, MODE_REPLAY only; LargeLds::launch_bytes(NP, true) of dynamic LDS): the front end associates by the Mahalanobis gate in the
 /// filters whose gate is > 0 (small_frontend); P is read through L2.
 template <typename T, int MODE, bool SIGHTED = false, bool GATED = false>
 __global__ __launch_bounds__(SMALL_WG) void large_frontend_kernel(DevView d, LargeView<T> lv, int64_t t, int s, int nsteps,
@@ -374,35 +337,19 @@ __global__ __launch_bounds__(SMALL_WG) void large_frontend_kernel(DevView d, Lar
         unsigned long long stamp_last = __builtin_amdgcn_s_memtime();
         const unsigned long long stamp_rt0 = __builtin_amdgcn_s_memrealtime(); // 100 MHz: wall time inside the kernel
 #endif
-        small_load<MODE>(d, L, b, tid, NP);
-        if (MODE == MODE_REPLAY && tid == 0)
-                small_mask_ptr(L) = d.sighted + (size_t)b * (NP / 2); // (read behind the front end's barriers)
-        static_assert(!GATED || MODE == MODE_REPLAY, "the gate belongs to the replay seam");
-        if (GATED && tid == 0)
-                small_gate(L) = d.gate[b]; // (likewise)
+        small_enter<MODE, true, GATED>(d, L, b, tid, NP);
         ASLAM_STAMP(0);
         if (MODE == MODE_REPLAY)
         {
-                if (small_frontend<true, LARGE_OBS_CAP, LARGE_WAIT_CAP, LARGE_NP_MAX / 2, double, GATED>(
-                            d, L, Pg, NP, b, t, s, nsteps, poses_out, dims_out, tid, nullptr, GATED ? reinterpret_cast<double *>(smem + LargeLds::bytes(NP)) : nullptr))
+                if (small_frontend<true, LARGE_OBS_CAP, LARGE_WAIT_CAP, LARGE_NP_MAX / 2, double, GATED>(d, L, Pg, NP, b, t, s, nsteps, poses_out, dims_out, tid, nullptr,
+                                                                                                         GATED ? reinterpret_cast<double *>(smem + LargeLds::gate_table_at(NP)) : nullptr))
                 {
-                        if (tid == 0)
-                                skipped[b] = 1;
-                        small_store<MODE>(d, L, b, tid, NP);
+                        large_frontend_skip<MODE>(d, L, skipped, b, tid, NP);
                         return;
                 }
         }
         else
-        {
-                if (tid == 0)
-                {
-                        // one filter: the arguments of the call; batched step: this filter's entries of the per-call arrays
-                        sm.vx = sa.traj >= 0 ? sa.vx : d.step_in[b];
-                        sm.az = sa.traj >= 0 ? sa.az : d.step_in[d.B + b];
-                        sm.dt = sa.traj >= 0 ? sa.dt : d.step_in[2 * d.B + b];
-                }
-                __syncthreads();
-        }
+                small_step_intake(d, sm, sa, b, tid);
         ASLAM_STAMP(1);
         if (tid == 0)
                 skipped[b] = 0;

@@ -4,6 +4,8 @@
 // The default binary32 chain (LargeChain::F32_RESIDENT on the bf16 pipe) solves a tail of <= 3 rows past the last full 64-block as a border
 // (large_border(), ekf_large.h): LargePlan::border says so, every group's view carries it to the kernels (LargeView::border), and the X update is
 // then launched in front of the syrk.  ASLAM_BORDER=0 is the chain without it.
+// Which front-end instantiation a launch takes is a FrontendVariant, passed in by value; with_variant() turns it into template arguments, so
+// each family names its kernel template in one expression (to add a variant flag: one member and one line per family).
 // The list of the arrays a filter owns is for_each_array(), next to each view's struct (DevView: small_common.h, LargeView: ekf_large.h):
 // to add an array, add the member and one line there -- aslam_create, shifted(), aslam_reset and the clear list of restore follow.
 #pragma once
@@ -121,9 +123,33 @@ struct LargeHost
         int last_launches = 0;      // kernel launches per callback and stream group of that launch (large_stats included)
         bool last_resident = false; // that launch ran LargeChain::F32_RESIDENT
         bool last_syrk_tail = false; // the views of that launch carried the syrk's tail rule (LargeView::syrk_tail; aslam_get_syrk_tail)
-        bool gated = false;         // aslam_set_replay_gate: some filter's gate is > 0 -- the GATED instantiations of the replay front ends (either filter)
-        bool sighted = false;       // aslam_sighted_update_enable: the SIGHTED instantiations of the front end and of large_build_GS (which then also stands in for large_build_GS_tiles)
 };
+
+/// Which instantiation of its front-end family (ekf_small_kernel, ukf_small_kernel, large_frontend_kernel, ukf_large_frontend_kernel) a launch
+/// takes: computed ONCE per launch (frontend_variant() in aslam_core.hip, the one rule), passed by value, and read by the launchers and by
+/// aslam_kernel_info alike.  To add a variant flag: one member here, one line in the rule and one line per family.
+struct FrontendVariant
+{
+        bool stats;   // a StatsView with something to write: the STATS instantiations of the single-CU kernels (the large chains launch large_stats instead)
+        bool sighted; // aslam_sighted_update_enable, EKF contexts alone: SIGHTED (large-state: the front end and large_build_GS, which then also stands in for large_build_GS_tiles)
+        bool gated;   // aslam_set_replay_gate with some gate > 0, the replay seam alone: GATED
+};
+
+/// f(stats, sighted, gated) with the run-time flags as std::bool_constants, so that a family names its kernel template in one expression.  HAS_*:
+/// the flags the family has in this seam; one it has not is std::false_type whatever `v` says, so no instantiation beyond the built ones is formed
+template <bool HAS, typename F> auto with_flag(bool on, F &&f)
+{
+        if constexpr (HAS)
+                if (on)
+                        return f(std::true_type{});
+        return f(std::false_type{});
+}
+template <bool HAS_STATS, bool HAS_SIGHTED, bool HAS_GATED, typename F> auto with_variant(FrontendVariant v, F &&f)
+{
+        return with_flag<HAS_STATS>(v.stats, [&](auto st) {
+                return with_flag<HAS_SIGHTED>(v.sighted, [&](auto si) { return with_flag<HAS_GATED>(v.gated, [&](auto ga) { return f(st, si, ga); }); });
+        });
+}
 
 /// which filters a launch covers: one trajectory (MODE_STEP with sa.traj >= 0; the views then start at it, so the kernels get traj = 0) or the
 /// whole batch of B (sa.traj < 0 is the batched step)
@@ -226,26 +252,21 @@ int launch_left_looking(const DevView &dv, const LargeView<T> &v, int NB, int gb
         return count;
 }
 
-/// The front-end kernel of a launch: the SIGHTED (aslam_sighted_update_enable) and GATED (aslam_set_replay_gate) instantiations are picked at
-/// run time; GATED exists for the replay seam alone
-template <typename T, int MODE> auto large_frontend_of(bool sighted, bool gated) -> decltype(&large_frontend_kernel<T, MODE>)
+/// The front-end kernel of a launch (GATED exists for the replay seam alone)
+template <typename T, int MODE> auto large_frontend_of(FrontendVariant v)
 {
-        if constexpr (MODE == MODE_REPLAY)
-        {
-                if (gated)
-                        return sighted ? &large_frontend_kernel<T, MODE, true, true> : &large_frontend_kernel<T, MODE, false, true>;
-        }
-        return sighted ? &large_frontend_kernel<T, MODE, true> : &large_frontend_kernel<T, MODE>;
+        return with_variant<false, true, MODE == MODE_REPLAY>(
+                v, [](auto, auto si, auto ga) { return &large_frontend_kernel<T, MODE, decltype(si)::value, decltype(ga)::value>; });
 }
 
 /// callback s of one group: front end + predict, G, S, blocked factorisation of [S; G; Y^T], P -= V V^T, X += V q
-template <typename T, int MODE>
-void launch_large_chain(const LargePlan &plan, const LargeGroup<T> &g, size_t lds, int64_t t0, int s, int nsteps, StepArgs sa, bool sighted, bool gated)
+template <typename T, int MODE, typename K>
+void launch_large_chain(const LargePlan &plan, const LargeGroup<T> &g, K frontend, size_t lds, int64_t t0, int s, int nsteps, StepArgs sa, bool sighted)
 {
         const int NP = g.v.NP, NB = NP / LB, gb = g.nb;
-        // the front end (its SIGHTED / GATED instantiation; `lds` is the caller's LargeLds::bytes or bytes_gated), then G and S.  The sighted-only
+        // the front end (`frontend`, `lds`: the caller's large_frontend_of and LargeLds::launch_bytes), then G and S.  The sighted-only
         // update enters in these two launches alone (ASLAM_GS_TILES=1 has no masked form: large_build_GS runs); the gate in the first
-        hipLaunchKernelGGL((large_frontend_of<T, MODE>(sighted, gated)), dim3(gb), dim3(SMALL_WG), lds, g.st, g.dv, g.v, t0 + s, s, nsteps, g.poses, g.dims, sa, g.skip);
+        hipLaunchKernelGGL(frontend, dim3(gb), dim3(SMALL_WG), lds, g.st, g.dv, g.v, t0 + s, s, nsteps, g.poses, g.dims, sa, g.skip);
         if (sighted)
                 hipLaunchKernelGGL((large_build_GS<T, true>), dim3(1 + (NP / 2 + GS_ROW_PAIRS - 1) / GS_ROW_PAIRS, gb), dim3(256), 0, g.st, g.dv, g.v, g.skip);
         else if (plan.gs_tiles)
@@ -316,12 +337,12 @@ void launch_large_chain(const LargePlan &plan, const LargeGroup<T> &g, size_t ld
 /// filters on is split into stream groups.  The enqueue order (callbacks outermost, groups innermost) is what the rates were measured with.
 /// `sv`: statistics to write (one launch more per callback, reported in last_launches), all null for none
 template <int MODE, typename T>
-hipError_t launch_large(LargeHost &h, const DevView &dv, const LargeView<T> &lv, int *skipped, int64_t t0, int nsteps, double *poses, int32_t *dims,
-                        StepArgs sa, hipStream_t st, StatsView sv = {})
+hipError_t launch_large(LargeHost &h, FrontendVariant fv, const DevView &dv, const LargeView<T> &lv, int *skipped, int64_t t0, int nsteps, double *poses,
+                        int32_t *dims, StepArgs sa, hipStream_t st, StatsView sv = {})
 {
-        const bool gated = MODE == MODE_REPLAY && h.gated;
-        const size_t lds = gated ? LargeLds::bytes_gated(dv.NP) : LargeLds::bytes(dv.NP);
-        if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(large_frontend_of<T, MODE>(h.sighted, gated)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
+        const auto frontend = large_frontend_of<T, MODE>(fv);
+        const size_t lds = LargeLds::launch_bytes(dv.NP, fv.gated);
+        if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(frontend), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
                 return e;
         const LaunchSlice sl = launch_slice<MODE>(sa, dv.B);
         const int first = sl.first, Bz = sl.count;
@@ -355,7 +376,7 @@ hipError_t launch_large(LargeHost &h, const DevView &dv, const LargeView<T> &lv,
         for (int s = 0; s < nsteps; ++s)
                 for (int q = 0; q < NG; ++q)
                         if (g[q].nb > 0)
-                                launch_large_chain<T, MODE>(plan, g[q], lds, t0, s, nsteps, sl.sa, h.sighted, gated);
+                                launch_large_chain<T, MODE>(plan, g[q], frontend, lds, t0, s, nsteps, sl.sa, fv.sighted);
         for (int q = 1; q < NG && e == hipSuccess; ++q)
                 if ((e = hipEventRecord(h.ev_join[q - 1], h.aux[q - 1])) == hipSuccess)
                         e = hipStreamWaitEvent(st, h.ev_join[q - 1], 0);

@@ -152,9 +152,7 @@ __global__ __launch_bounds__(SMALL_WG) void ekf_small_kernel(DevView d, int64_t 
                       *const sH = L.sH;
         SmallShared &sm = *L.sm;
         // SIGHTED: D [NP], D Y [NP] and, from sD[NP] on, 64 partial products of the first factor's inverted diagonal (2 KB of scratch each)
-        double *const sD = reinterpret_cast<double *>(L.sWx), *const sDY = reinterpret_cast<double *>(L.sWy);
-        static_assert(!SIGHTED || (NP + 64) * 8 <= 4 * SMALL_WAIT_CAP, "D and D Y fit the wait-list scratch");
-        static_assert(!GATED || MODE == MODE_REPLAY, "the gate belongs to the replay seam");
+        double *const sD = small_sighted_scratch<NP>(L).D, *const sDY = small_sighted_scratch<NP>(L).DY;
 
         const int tid_launch = threadIdx.x, tid = tid_launch;
         const int b = (MODE == MODE_STEP && sa.traj >= 0) ? sa.traj : (int)blockIdx.x; // sa.traj < 0: the batched step, one workgroup per filter
@@ -164,11 +162,7 @@ __global__ __launch_bounds__(SMALL_WG) void ekf_small_kernel(DevView d, int64_t 
         unsigned long long stamp_last = __builtin_amdgcn_s_memtime();
 #endif
 
-        small_load<MODE>(d, L, b, tid, NP);
-        if (MODE == MODE_REPLAY && tid == 0)
-                small_mask_ptr(L) = d.sighted + (size_t)b * NLM; // (read behind the front end's barriers)
-        if (GATED && tid == 0)
-                small_gate(L) = d.gate[b]; // (likewise)
+        small_enter<MODE, true, GATED>(d, L, b, tid, NP);
         // P stays in LDS for the whole launch, as the lower 16x16 tiles of the symmetric matrix (the tile storage the solver
         // factors in place): HBM sees it once on the way in and once on the way out
         for (int idx = tid; idx < LY::NTILES * 256; idx += SMALL_WG)
@@ -189,7 +183,8 @@ __global__ __launch_bounds__(SMALL_WG) void ekf_small_kernel(DevView d, int64_t 
                 const int64_t t = t0 + s;
                 if (MODE == MODE_REPLAY)
                 {
-                        if (small_frontend<true, SMALL_OBS_CAP, SMALL_WAIT_CAP, NP / 2, double, GATED>(d, L, Pg, NP, b, t, s, nsteps, poses_out, dims_out, tid, Lt, sH))
+                        if (small_frontend<true, SMALL_OBS_CAP, SMALL_WAIT_CAP, NP / 2, double, GATED>(d, L, Pg, NP, b, t, s, nsteps, poses_out, dims_out, tid, Lt,
+                                                                                                        small_gate_table(L)))
                         {
                                 if constexpr (STATS)
                                         stats_skip(sv, b, s, nsteps, tid);
@@ -197,16 +192,7 @@ __global__ __launch_bounds__(SMALL_WG) void ekf_small_kernel(DevView d, int64_t 
                         }
                 }
                 else
-                {
-                        if (tid == 0)
-                        {
-                                // one filter: the arguments of the call; batched step: this filter's entries of the per-call arrays
-                                sm.vx = sa.traj >= 0 ? sa.vx : d.step_in[b];
-                                sm.az = sa.traj >= 0 ? sa.az : d.step_in[d.B + b];
-                                sm.dt = sa.traj >= 0 ? sa.dt : d.step_in[2 * d.B + b];
-                        }
-                        __syncthreads();
-                }
+                        small_step_intake(d, sm, sa, b, tid);
 
                 ASLAM_STAMP(0);
                 // ================= slam(), ekf.cpp:293-311

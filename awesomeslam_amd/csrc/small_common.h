@@ -1,6 +1,8 @@
 // small_common.h -- shared device code of the single-CU ("small", n <= 16*NT <= 144) EKF and UKF kernels:
 // HBM/LDS layout, the on-device callback front end (association, wait-list, growth), tile Cholesky and the
 // f64-MFMA triangular solves.  The EKF design notes below apply to ekf_small.h; ukf_small.h has its own.
+// The front end's LDS block is listed ONCE (for_each_assoc_array; to add an LDS field: one line there), with its overlays named next to
+// it; the entry block of the four front-end kernels (small_enter, small_step_intake, large_frontend_skip) sits behind small_store.
 //
 //
 // One 768-thread workgroup (12 wave64) owns one filter ("trajectory") and runs whole callbacks of the
@@ -175,6 +177,72 @@ struct SmallShared
         int nx_new, nx_nobs;
 };
 
+/// LDS pointers of one workgroup: the f64 solver area (null where a layout has none), then the association block of the front end
+struct SmallLds
+{
+        double *Lt, *Dinv, *sX, *sZ, *sY, *sU, *sH, *sTv;
+        float *sSr, *sSb, *sPx, *sPy, *sMd;
+        int *sCid;
+        float *sWr, *sWb, *sWx, *sWy;
+        uint32_t *sWc;
+        int *sNew;
+        float *sPd;
+        int *sPi;
+        float *sLm;
+        SmallShared *sm;
+};
+
+/// The association block of the front end's LDS: f(pointer, elements) once per array, in LDS order.  This is the ONE list of what the block
+/// holds: its byte count (what the host hands the launch) and the pointers the kernel carves are both derived from it, for the single-CU
+/// layout (SmallLayout) and for the large front ends (LargeLds, ekf_large.h) alike.  To add an LDS field: a member of SmallLds and one line here.
+template <typename F> __host__ __device__ constexpr void for_each_assoc_array(SmallLds &L, int obs_cap, int wait_cap, int NP, F &&f)
+{
+        f(L.sSr, obs_cap);      // the stored sensor message: range,
+        f(L.sSb, obs_cap);      // bearing,
+        f(L.sPx, obs_cap);      // world x and
+        f(L.sPy, obs_cap);      // y of the observation
+        f(L.sMd, obs_cap);      // nearest distance
+        f(L.sCid, obs_cap);     // nearest landmark offset (corr_id)
+        f(L.sWr, wait_cap);     // wait-list range,
+        f(L.sWb, wait_cap);     // bearing,
+        f(L.sWx, wait_cap);     // the entry re-projected from the current pose
+        f(L.sWy, wait_cap);
+        f(L.sWc, wait_cap);     // count
+        f(L.sNew, NP / 2);      // wait entries promoted this callback
+        f(L.sPd, 4 * obs_cap);  // association scratch [obs_cap][4] (floats); overlays below
+        f(L.sPi, 4 * obs_cap);  // association scratch [obs_cap][4] (ints)
+        f(L.sLm, NP);           // [NP/2][2] mapped landmarks narrowed to binary32 (NP is even)
+}
+struct AssocBytes
+{
+        size_t o;
+        template <typename T> __host__ __device__ constexpr void operator()(T *&, int count) { o += sizeof(T) * (size_t)count; }
+};
+struct AssocCarve
+{
+        unsigned char *p;
+        template <typename T> __device__ __forceinline__ void operator()(T *&a, int count) { a = reinterpret_cast<T *>(p), p += sizeof(T) * (size_t)count; }
+};
+/// the block placed at byte `at` of a layout: where its SmallShared lies (16-byte aligned, behind the arrays; the block ends behind it)
+__host__ __device__ constexpr size_t assoc_shared_at(size_t at, int obs_cap, int wait_cap, int NP)
+{
+        SmallLds L = {};
+        AssocBytes s = {at};
+        for_each_assoc_array(L, obs_cap, wait_cap, NP, s);
+        return (s.o + 15) & ~(size_t)15;
+}
+/// the array pointers of the block that starts at `p`; returns where the arrays end (SmallShared follows, 16-byte aligned: assoc_shared_at)
+__device__ __forceinline__ unsigned char *assoc_carve(SmallLds &L, unsigned char *p, int obs_cap, int wait_cap, int NP)
+{
+        AssocCarve c = {p};
+        for_each_assoc_array(L, obs_cap, wait_cap, NP, c);
+        return c.p;
+}
+
+/// the landmark table of the GATED front end (small_frontend's gtab): six arrays of NP / 2 doubles
+__host__ __device__ constexpr size_t gate_table_doubles(int NP) { return (size_t)6 * (NP / 2); }
+
+/// LDS of the single-CU kernels: the f64 solver area, then the association block with the SMALL_* capacities (UkfLayout, ukf_small.h, builds on `total`)
 template <int NT> struct SmallLayout
 {
         static constexpr int NP = 16 * NT;
@@ -189,26 +257,68 @@ template <int NT> struct SmallLayout
         static constexpr int oH = oU + NP;           // [8][NP/2], coefficient-major: h00 h01 h10 h11 (rows of H) e00 e01 e10 e11 (of H^-1) per landmark (ekf_small.h lm_coef)
         static constexpr int oTv = oH + (NP / 2) * 8; // scratch vector of the EKF's inverse-based update
         static constexpr int oEnd = oTv + NP;
-        // then floats / ints
         static constexpr size_t bytes_f64 = (size_t)oEnd * 8;
-        static constexpr size_t oSr = bytes_f64;                       // float[OBS_CAP] range
-        static constexpr size_t oSb = oSr + 4 * SMALL_OBS_CAP;         // float bearing
-        static constexpr size_t oPx = oSb + 4 * SMALL_OBS_CAP;         // float world x of the observation
-        static constexpr size_t oPy = oPx + 4 * SMALL_OBS_CAP;
-        static constexpr size_t oMd = oPy + 4 * SMALL_OBS_CAP;         // float nearest distance
-        static constexpr size_t oCid = oMd + 4 * SMALL_OBS_CAP;        // int   nearest landmark offset (corr_id)
-        static constexpr size_t oWr = oCid + 4 * SMALL_OBS_CAP;        // wait-list range
-        static constexpr size_t oWb = oWr + 4 * SMALL_WAIT_CAP;
-        static constexpr size_t oWx = oWb + 4 * SMALL_WAIT_CAP;        // wait-list entry re-projected from the current pose
-        static constexpr size_t oWy = oWx + 4 * SMALL_WAIT_CAP;
-        static constexpr size_t oWc = oWy + 4 * SMALL_WAIT_CAP;        // uint count
-        static constexpr size_t oNew = oWc + 4 * SMALL_WAIT_CAP;       // int[NP/2] wait entries promoted this callback
-        static constexpr size_t oPd = oNew + 4 * (NP / 2);             // float[OBS_CAP][4] partial nearest distances
-        static constexpr size_t oPi = oPd + 16 * SMALL_OBS_CAP;        // int  [OBS_CAP][4] partial nearest indices
-        static constexpr size_t oLm = oPi + 16 * SMALL_OBS_CAP;        // float[NP/2][2] mapped landmarks narrowed to binary32
-        static constexpr size_t oSm = (oLm + 8 * (NP / 2) + 15) & ~(size_t)15;
-        static constexpr size_t total = oSm + sizeof(SmallShared);
+        static constexpr size_t total = assoc_shared_at(bytes_f64, SMALL_OBS_CAP, SMALL_WAIT_CAP, NP) + sizeof(SmallShared);
+        static_assert(gate_table_doubles(NP) <= (size_t)(oTv - oH), "the gate table fits sH");
 };
+
+template <int NT> __device__ __forceinline__ SmallLds small_carve(unsigned char *smem)
+{
+        typedef SmallLayout<NT> LY;
+        double *lds = reinterpret_cast<double *>(smem);
+        SmallLds L;
+        L.Lt = lds + LY::oL;
+        L.Dinv = lds + LY::oDinv;
+        L.sX = lds + LY::oX;
+        L.sZ = lds + LY::oZ;
+        L.sY = lds + LY::oY;
+        L.sU = lds + LY::oU;
+        L.sH = lds + LY::oH;
+        L.sTv = lds + LY::oTv;
+        assoc_carve(L, smem + LY::bytes_f64, SMALL_OBS_CAP, SMALL_WAIT_CAP, LY::NP);
+        L.sm = reinterpret_cast<SmallShared *>(smem + assoc_shared_at(LY::bytes_f64, SMALL_OBS_CAP, SMALL_WAIT_CAP, LY::NP));
+        return L;
+}
+
+// ---- overlays onto the block: what else lives in its arrays, each with the proof that it fits ----------------------
+// sPd / sPi (four entries per observation; the scan combines in registers, so only these users are left), by entry:
+//   0 .. 11         the wait-list walk's per-wave partial results (small_frontend: sPd[wave], sPi[wave])
+//   12, 13 (sPd)    small_mask_ptr
+//   14, 15 (sPd)    small_gate
+//   16 ..           the intake staging of the next callback's message (small_intake_staging): sPd ranges, sPi bearings
+constexpr int FE_MASK_AT = 12, FE_GATE_AT = 14, FE_STAGING_AT = 16;
+static_assert(SMALL_WAVES <= FE_MASK_AT, "the walk's scratch ends in front of the mask pointer");
+static_assert(sizeof(uint8_t *) <= 4 * (FE_GATE_AT - FE_MASK_AT) && sizeof(double) <= 4 * (FE_STAGING_AT - FE_GATE_AT) && FE_MASK_AT % 2 == 0 && FE_GATE_AT % 2 == 0,
+              "the mask pointer and the gate fit their entries, 8-byte aligned");
+
+/// This filter's row of DevView::sighted, kept in LDS for the launch (small_enter puts it there).  The front end writes the mask of every
+/// callback through it; as a kernel argument alive in scalar registers for the whole launch the pointer cost the single-CU EKF kernels
+/// a register (and with it four more bytes of scratch per lane) in front of every phase.
+__device__ __forceinline__ uint8_t *&small_mask_ptr(const SmallLds &L) { return *reinterpret_cast<uint8_t **>(L.sPd + FE_MASK_AT); }
+
+/// This filter's gate (DevView::gate), kept in LDS for the launch by the GATED kernels (small_enter).  The ungated instantiations never look at it.
+__device__ __forceinline__ double &small_gate(const SmallLds &L) { return *reinterpret_cast<double *>(L.sPd + FE_GATE_AT); }
+
+/// The staging area of small_prefetch_intake, read by the next callback's small_frontend: one whole message
+struct IntakeStaging { float *r, *b; }; // range, bearing
+template <int OBS_CAP> __device__ __forceinline__ IntakeStaging small_intake_staging(const SmallLds &L)
+{
+        static_assert(FE_STAGING_AT + OBS_CAP <= 4 * OBS_CAP, "the staging area holds a whole message");
+        return {L.sPd + FE_STAGING_AT, reinterpret_cast<float *>(L.sPi) + FE_STAGING_AT};
+}
+
+/// The sighted-only EKF update (ekf_small.h): D [NP] and D Y [NP], each followed by 64 partial products of the first factor's inverted
+/// diagonal, in the wait-list scratch sWx / sWy, which only small_frontend reads
+struct SightedScratch { double *D, *DY; };
+template <int NP> __device__ __forceinline__ SightedScratch small_sighted_scratch(const SmallLds &L)
+{
+        static_assert((NP + 64) * 8 <= 4 * SMALL_WAIT_CAP, "D and D Y fit the wait-list scratch");
+        return {reinterpret_cast<double *>(L.sWx), reinterpret_cast<double *>(L.sWy)};
+}
+
+/// The gate table of the single-CU kernels: over sH, whose coefficients the EKF forms behind the front end and which the UKF never uses
+/// (SmallLayout asserts the fit).  The large front ends keep theirs behind the block: LargeLds::gate_table_at
+__device__ __forceinline__ double *small_gate_table(const SmallLds &L) { return L.sH; }
 
 /// Sum of x over the 64 lanes of a wave, valid in lane 63, by DPP moves only (quad permutes, row mirrors, row broadcasts: VALU instructions).
 /// __shfl_xor is a ds_bpermute -- an LDS crossbar instruction: the five binary64 sums per row of large_x_update_rows were 60 of them per
@@ -1166,69 +1276,6 @@ template <int NT> __device__ __forceinline__ void cholesky_lookahead(double *Lt,
 }
 
 // ------------------------------------------------------------------------------------------------------
-/// LDS pointers of one workgroup (carved by SmallLayout)
-struct SmallLds
-{
-        double *Lt, *Dinv, *sX, *sZ, *sY, *sU, *sH, *sTv;
-        float *sSr, *sSb, *sPx, *sPy, *sMd;
-        int *sCid;
-        float *sWr, *sWb, *sWx, *sWy;
-        uint32_t *sWc;
-        int *sNew;
-        float *sPd;
-        int *sPi;
-        float *sLm;
-        SmallShared *sm;
-};
-
-template <int NT> __device__ __forceinline__ SmallLds small_carve(unsigned char *smem)
-{
-        typedef SmallLayout<NT> LY;
-        double *lds = reinterpret_cast<double *>(smem);
-        SmallLds L;
-        L.Lt = lds + LY::oL;
-        L.Dinv = lds + LY::oDinv;
-        L.sX = lds + LY::oX;
-        L.sZ = lds + LY::oZ;
-        L.sY = lds + LY::oY;
-        L.sU = lds + LY::oU;
-        L.sH = lds + LY::oH;
-        L.sTv = lds + LY::oTv;
-        L.sSr = reinterpret_cast<float *>(smem + LY::oSr);
-        L.sSb = reinterpret_cast<float *>(smem + LY::oSb);
-        L.sPx = reinterpret_cast<float *>(smem + LY::oPx);
-        L.sPy = reinterpret_cast<float *>(smem + LY::oPy);
-        L.sMd = reinterpret_cast<float *>(smem + LY::oMd);
-        L.sCid = reinterpret_cast<int *>(smem + LY::oCid);
-        L.sWr = reinterpret_cast<float *>(smem + LY::oWr);
-        L.sWb = reinterpret_cast<float *>(smem + LY::oWb);
-        L.sWx = reinterpret_cast<float *>(smem + LY::oWx);
-        L.sWy = reinterpret_cast<float *>(smem + LY::oWy);
-        L.sWc = reinterpret_cast<uint32_t *>(smem + LY::oWc);
-        L.sNew = reinterpret_cast<int *>(smem + LY::oNew);
-        L.sPd = reinterpret_cast<float *>(smem + LY::oPd);
-        L.sPi = reinterpret_cast<int *>(smem + LY::oPi);
-        L.sLm = reinterpret_cast<float *>(smem + LY::oLm);
-        L.sm = reinterpret_cast<SmallShared *>(smem + LY::oSm);
-        return L;
-}
-
-/// This filter's row of DevView::sighted, kept in LDS for the launch (the EKF kernels put it there behind small_load): four spare floats of the association scratch --
-/// entries 0 .. 11 of sPd are the wait-list walk's, the staging area of small_prefetch_intake starts at 16.  The front end writes the mask of
-/// every callback through it; as a kernel argument alive in scalar registers for the whole launch the pointer cost the single-CU EKF kernels
-/// a register (and with it four more bytes of scratch per lane) in front of every phase.
-__device__ __forceinline__ uint8_t *&small_mask_ptr(const SmallLds &L)
-{
-        return *reinterpret_cast<uint8_t **>(L.sPd + 12);
-}
-
-/// This filter's gate (DevView::gate), kept in LDS for the launch by the GATED kernels behind small_load: the last two spare floats in front of the
-/// staging area (entries 14, 15 of sPd; 12, 13 are small_mask_ptr's).  The ungated instantiations never look at it.
-__device__ __forceinline__ double &small_gate(const SmallLds &L)
-{
-        return *reinterpret_cast<double *>(L.sPd + 14);
-}
-
 /// Bring filter `b` from HBM into LDS (vectors, scalars, stored sensor message, wait-list).
 template <int MODE> __device__ __forceinline__ void small_load(const DevView &d, const SmallLds &L, int b, int tid, int NP)
 {
@@ -1312,15 +1359,47 @@ template <int MODE> __device__ __forceinline__ void small_store(const DevView &d
         }
 }
 
+// ---- the entry block of the four front-end kernels (ekf_small, ukf_small, large_frontend, ukf_large_frontend) ------
+/// small_load, then what the front end reads from LDS behind its barriers: the mask pointer (EKF families, replay) and the gate (GATED)
+template <int MODE, bool IS_EKF, bool GATED> __device__ __forceinline__ void small_enter(const DevView &d, const SmallLds &L, int b, int tid, int NP)
+{
+        static_assert(!GATED || MODE == MODE_REPLAY, "the gate belongs to the replay seam");
+        small_load<MODE>(d, L, b, tid, NP);
+        if (IS_EKF && MODE == MODE_REPLAY && tid == 0)
+                small_mask_ptr(L) = d.sighted + (size_t)b * (NP / 2);
+        if (GATED && tid == 0)
+                small_gate(L) = d.gate[b];
+}
+
+/// slam()'s binary32 arguments in the step seams: the arguments of the call (one filter) or this filter's entries of the per-call arrays (batched step)
+__device__ __forceinline__ void small_step_intake(const DevView &d, SmallShared &sm, StepArgs sa, int b, int tid)
+{
+        if (tid == 0)
+        {
+                sm.vx = sa.traj >= 0 ? sa.vx : d.step_in[b];
+                sm.az = sa.traj >= 0 ? sa.az : d.step_in[d.B + b];
+                sm.dt = sa.traj >= 0 ? sa.dt : d.step_in[2 * d.B + b];
+        }
+        __syncthreads();
+}
+
+/// the large front ends, when cbOdom returned early: the rest of the chain leaves the filter alone (the caller returns)
+template <int MODE> __device__ __forceinline__ void large_frontend_skip(const DevView &d, const SmallLds &L, int *skipped, int b, int tid, int NP)
+{
+        if (tid == 0)
+                skipped[b] = 1;
+        small_store<MODE>(d, L, b, tid, NP);
+}
+
 /// The messages of callback t1 (= the next one of this launch) into LDS, by ONE wave with nothing else to do at the call site, while the others compute:
 /// the front end of t1 then starts from LDS instead of two dependent global round trips (~ 2 k cycles per callback; round 4).  The staging area is the
-/// association's partial-result scratch, unused since the scan combines in registers (entries 0 .. 15 stay the wait-list walk's).  Call between two
+/// association's partial-result scratch (small_intake_staging).  Call between two
 /// barriers of the callback, outside the front end; `lane` = 0 .. 63.
 template <int OBS_CAP> __device__ __forceinline__ void small_prefetch_intake(const DevView &d, const SmallLds &L, int b, int64_t t1, int lane)
 {
         SmallShared &sm = *L.sm;
-        const int ocap = min(d.max_obs, OBS_CAP); // (OBS_CAP <= 4 OBS_CAP - 16: the staging area holds a whole message)
-        float *const stg_r = L.sPd + 16, *const stg_b = reinterpret_cast<float *>(L.sPi) + 16;
+        const int ocap = min(d.max_obs, OBS_CAP);
+        float *const stg_r = small_intake_staging<OBS_CAP>(L).r, *const stg_b = small_intake_staging<OBS_CAP>(L).b;
         const float *src = d.tr_obs + ((size_t)b * d.T + t1) * d.max_obs * 2;
         for (int j0 = 0; j0 < ocap; j0 += 128)
         {
@@ -1377,7 +1456,7 @@ __device__ __forceinline__ bool small_frontend(const DevView &d, const SmallLds 
 #endif
         // ================= message intake
         const int ocap = min(d.max_obs, OBS_CAP);
-        float *const stg_r = L.sPd + 16, *const stg_b = reinterpret_cast<float *>(L.sPi) + 16; // (the scratch of the wait-list walk is entries 0 .. 11)
+        float *const stg_r = small_intake_staging<OBS_CAP>(L).r, *const stg_b = small_intake_staging<OBS_CAP>(L).b;
         const bool staged = (sm.staged_t == t); // published by the barriers of the previous callback; uniform
         // Not staged (the first callback of a launch, the large-state front end): the observation row of this callback is fetched next to thread 0's
         // scalars (one global latency instead of two; the row has max_obs entries whatever tr_nobs says, and it is only kept when the message is new).

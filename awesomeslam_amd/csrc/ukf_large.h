@@ -93,7 +93,7 @@ __device__ __forceinline__ double ukf_xsig(double x, double l, int c, double sg,
 // ------------------------------------------------------------------------------------------------------------------
 /// Per-filter front end (one workgroup of SMALL_WG threads per filter, LargeLds::bytes(NP) of dynamic LDS).  `skipped` [B] is set to 1
 /// when the callback returned early (no sensor message yet): the rest of the chain then leaves the filter alone.
-/// GATED (aslam_set_replay_gate, MODE_REPLAY only; LargeLds::bytes_gated of dynamic LDS): the front end associates by the Mahalanobis gate in the
+/// GATED (aslam_set_replay_gate, MODE_REPLAY only; LargeLds::launch_bytes(NP, true) of dynamic LDS): the front end associates by the Mahalanobis gate in the
 /// filters whose gate is > 0 (small_frontend); P is read through L2.
 template <int MODE, bool GATED = false>
 __global__ __launch_bounds__(SMALL_WG) void ukf_large_frontend_kernel(DevView d, LargeView<double> lv, UkfLargeView uv, int64_t t, int s, int nsteps,
@@ -106,32 +106,18 @@ __global__ __launch_bounds__(SMALL_WG) void ukf_large_frontend_kernel(DevView d,
         const int tid = threadIdx.x;
         const int b = (MODE == MODE_STEP && sa.traj >= 0) ? sa.traj : (int)blockIdx.x; // sa.traj < 0: the batched step, one workgroup per filter
         double *Pg = lv.P + (size_t)b * NP * NP;
-        static_assert(!GATED || MODE == MODE_REPLAY, "the gate belongs to the replay seam");
-        small_load<MODE>(d, L, b, tid, NP);
-        if (GATED && tid == 0)
-                small_gate(L) = d.gate[b]; // (read behind the front end's barriers)
+        small_enter<MODE, false, GATED>(d, L, b, tid, NP);
         if (MODE == MODE_REPLAY)
         {
-                if (small_frontend<false, LARGE_OBS_CAP, LARGE_WAIT_CAP, LARGE_NP_MAX / 2, double, GATED>(
-                            d, L, Pg, NP, b, t, s, nsteps, poses_out, dims_out, tid, nullptr, GATED ? reinterpret_cast<double *>(smem + LargeLds::bytes(NP)) : nullptr))
+                if (small_frontend<false, LARGE_OBS_CAP, LARGE_WAIT_CAP, LARGE_NP_MAX / 2, double, GATED>(d, L, Pg, NP, b, t, s, nsteps, poses_out, dims_out, tid, nullptr,
+                                                                                                          GATED ? reinterpret_cast<double *>(smem + LargeLds::gate_table_at(NP)) : nullptr))
                 {
-                        if (tid == 0)
-                                skipped[b] = 1;
-                        small_store<MODE>(d, L, b, tid, NP);
+                        large_frontend_skip<MODE>(d, L, skipped, b, tid, NP);
                         return;
                 }
         }
         else
-        {
-                if (tid == 0)
-                {
-                        // one filter: the arguments of the call; batched step: this filter's entries of the per-call arrays
-                        sm.vx = sa.traj >= 0 ? sa.vx : d.step_in[b];
-                        sm.az = sa.traj >= 0 ? sa.az : d.step_in[d.B + b];
-                        sm.dt = sa.traj >= 0 ? sa.dt : d.step_in[2 * d.B + b];
-                }
-                __syncthreads();
-        }
+                small_step_intake(d, sm, sa, b, tid);
         if (tid == 0)
         {
                 skipped[b] = 0;

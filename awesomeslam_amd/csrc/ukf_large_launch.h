@@ -1,6 +1,6 @@
 // ukf_large_launch.h -- host side of the large-state UKF (ukf_large.h), included by aslam_core.hip: the launch plan (ukf_large_plan() is the ONE
 // place that says how many launches a callback is -- the launcher walks it, aslam_get_launch_info and aslam_kernel_info report it), views
-// shifted to a trajectory, and the chain launcher.  One stream: the caller's (no stream groups on this path).  The list of the arrays a filter
+// shifted to a trajectory, and the chain launcher (its front end picked by the caller's FrontendVariant).  One stream: the caller's (no stream groups on this path).  The list of the arrays a filter
 // owns on this path is for_each_array(UkfLargeView &) in ukf_large.h: to add an array, add the member and one line there.
 #pragma once
 
@@ -38,15 +38,14 @@ inline UkfLargePlan ukf_large_plan(int NP)
 
 /// `nsteps` callbacks of a large-state UKF context: one trajectory (MODE_STEP with sa.traj >= 0) or the whole batch
 template <int MODE>
-hipError_t launch_ukf_large(LargeHost &h, const DevView &dv0, const LargeView<double> &lv0, const UkfLargeView &uv0, int *skipped0, int64_t t0, int nsteps,
-                            double *poses, int32_t *dims, StepArgs sa, hipStream_t st, StatsView sv0 = {})
+hipError_t launch_ukf_large(LargeHost &h, FrontendVariant fv, const DevView &dv0, const LargeView<double> &lv0, const UkfLargeView &uv0, int *skipped0, int64_t t0,
+                            int nsteps, double *poses, int32_t *dims, StepArgs sa, hipStream_t st, StatsView sv0 = {})
 {
         const int NP = dv0.NP;
-        const bool gated = MODE == MODE_REPLAY && h.gated; // aslam_set_replay_gate: the GATED front end, with its landmark table behind the rest of the LDS
-        constexpr int MG = MODE == MODE_REPLAY ? MODE : MODE_REPLAY; // (the GATED flag is instantiated for the replay seam alone)
-        const size_t lds = gated ? LargeLds::bytes_gated(NP) : LargeLds::bytes(NP);
-        if (hipError_t e = gated ? hipFuncSetAttribute(reinterpret_cast<const void *>(ukf_large_frontend_kernel<MG, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                                 : hipFuncSetAttribute(reinterpret_cast<const void *>(ukf_large_frontend_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
+        // the front end of this launch (GATED: the replay seam alone, with its landmark table behind the rest of the LDS)
+        const auto frontend = with_variant<false, false, MODE == MODE_REPLAY>(fv, [](auto, auto, auto ga) { return &ukf_large_frontend_kernel<MODE, decltype(ga)::value>; });
+        const size_t lds = LargeLds::launch_bytes(NP, fv.gated);
+        if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(frontend), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
                 return e;
         const LaunchSlice sl = launch_slice<MODE>(sa, dv0.B);
         const size_t first = (size_t)sl.first;
@@ -67,10 +66,7 @@ hipError_t launch_ukf_large(LargeHost &h, const DevView &dv0, const LargeView<do
         for (int s = 0; s < nsteps; ++s)
         {
                 int count = 0;
-                if (gated)
-                        hipLaunchKernelGGL((ukf_large_frontend_kernel<MG, true>), dim3(gb), dim3(SMALL_WG), lds, st, dv, lv, uv, t0 + s, s, nsteps, poses, dims, sl.sa, skip);
-                else
-                        hipLaunchKernelGGL((ukf_large_frontend_kernel<MODE>), dim3(gb), dim3(SMALL_WG), lds, st, dv, lv, uv, t0 + s, s, nsteps, poses, dims, sl.sa, skip);
+                hipLaunchKernelGGL(frontend, dim3(gb), dim3(SMALL_WG), lds, st, dv, lv, uv, t0 + s, s, nsteps, poses, dims, sl.sa, skip);
                 count += plan.frontend;
                 count += launch_left_looking(dv, lv, NB, gb, skip, st, 1, false); // L = chol(P) in S
                 hipLaunchKernelGGL(ukf_large_sigma_pose, dim3(gb), dim3(256), 0, st, dv, lv, uv, skip);

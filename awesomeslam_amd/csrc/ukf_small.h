@@ -406,10 +406,7 @@ __global__ __launch_bounds__(SMALL_WG) void ukf_small_kernel(DevView d, UkfView 
         unsigned long long stamp_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         unsigned long long stamp_last = __builtin_amdgcn_s_memtime();
 #endif
-        static_assert(!GATED || MODE == MODE_REPLAY, "the gate belongs to the replay seam");
-        small_load<MODE>(d, L, b, tid, NP);
-        if (GATED && tid == 0)
-                small_gate(L) = d.gate[b]; // (read behind the front end's barriers)
+        small_enter<MODE, false, GATED>(d, L, b, tid, NP);
 
         for (int s = 0; s < nsteps; ++s)
         {
@@ -419,7 +416,8 @@ __global__ __launch_bounds__(SMALL_WG) void ukf_small_kernel(DevView d, UkfView 
                 const int64_t t = t0 + s;
                 if (MODE == MODE_REPLAY)
                 {
-                        if (small_frontend<false, SMALL_OBS_CAP, SMALL_WAIT_CAP, NP / 2, double, GATED>(d, L, Pg, NP, b, t, s, nsteps, poses_out, dims_out, tid, nullptr, L.sH))
+                        if (small_frontend<false, SMALL_OBS_CAP, SMALL_WAIT_CAP, NP / 2, double, GATED>(d, L, Pg, NP, b, t, s, nsteps, poses_out, dims_out, tid, nullptr,
+                                                                                                         small_gate_table(L)))
                         {
                                 if constexpr (STATS)
                                         stats_skip(sv, b, s, nsteps, tid);
@@ -427,16 +425,7 @@ __global__ __launch_bounds__(SMALL_WG) void ukf_small_kernel(DevView d, UkfView 
                         }
                 }
                 else
-                {
-                        if (tid == 0)
-                        {
-                                // one filter: the arguments of the call; batched step: this filter's entries of the per-call arrays
-                                sm.vx = sa.traj >= 0 ? sa.vx : d.step_in[b];
-                                sm.az = sa.traj >= 0 ? sa.az : d.step_in[d.B + b];
-                                sm.dt = sa.traj >= 0 ? sa.dt : d.step_in[2 * d.B + b];
-                        }
-                        __syncthreads();
-                }
+                        small_step_intake(d, sm, sa, b, tid);
 
                 ASLAM_STAMP(0);
                 // ================= slam(), ukf.cpp:260-392

@@ -381,18 +381,61 @@ def test_reset_restore_and_refusals(built):
     other.close()
 
 
-@pytest.mark.parametrize("kind,large", [("ukf", False), ("ukf", True), ("ekf", True)])
-def test_kernel_names(kind, large, built):
-    from awesomeslam_amd.core import CFG_UKF_LARGE, Core
+F64_CHAIN = "large_update_panel<double> (10-launch chain per callback, 3 stream groups)"
+UKF_CHAIN = "ukf_large_wabt + large_update_panel<double> + large_syrk<double> (20-launch chain per callback, 1 stream)"
+F32_CHAIN = "large_right_step + large_syrk_bf16x3 (6-launch chain per callback: one right-looking launch per block column)"
+# context -> (kind, landmarks of the capacity, dtype, large UKF, NP, {state: (kernel_info name, dynamic LDS bytes)}): one context per family at its
+# smallest shape, batch 1.  The names are keys (bench.py prices the chain from them, profiles/pmc_traffic.json is looked up by them) and the LDS
+# sizes are what the host hands the launch: both recorded from the library before the front ends got one LDS layout and one variant rule
+KERNEL_INFO = {
+    "ekf-2": ("ekf", 12, "f64", False, 32, {"plain": ("ekf_small_kernel<2,0>", 31064), "sighted": ("ekf_small_kernel<2,0,false,true>", 31064),
+                                            "gated": ("ekf_small_kernel<2,0,false,false,true>", 31064),
+                                            "gated+sighted": ("ekf_small_kernel<2,0,false,true,true>", 31064)}),
+    "ekf-5": ("ekf", 24, "f64", False, 80, {"plain": ("ekf_small_kernel<5,0>", 67448), "sighted": ("ekf_small_kernel<5,0,false,true>", 67448),
+                                            "gated": ("ekf_small_kernel<5,0,false,false,true>", 67448),
+                                            "gated+sighted": ("ekf_small_kernel<5,0,false,true,true>", 67448)}),
+    "ekf-9": ("ekf", 64, "f64", False, 144, {"plain": ("ekf_small_kernel<9,0>", 146424), "sighted": ("ekf_small_kernel<9,0,false,true>", 146424),
+                                             "gated": ("ekf_small_kernel<9,0,false,false,true>", 146424),
+                                             "gated+sighted": ("ekf_small_kernel<9,0,false,true,true>", 146424)}),
+    "ukf-2": ("ukf", 12, "f64", False, 32, {"plain": ("ukf_small_kernel<2,0>", 52336), "gated": ("ukf_small_kernel<2,0,false,true>", 52336)}),
+    "ukf-5": ("ukf", 24, "f64", False, 80, {"plain": ("ukf_small_kernel<5,0>", 119824), "gated": ("ukf_small_kernel<5,0,false,true>", 119824)}),
+    "ukf-9": ("ukf", 64, "f64", False, 144, {"plain": ("ukf_small_kernel<9,0>", 161936), "gated": ("ukf_small_kernel<9,0,false,true>", 161936)}),
+    "ekf-large-f64": ("ekf", 80, "f64", False, 192, {"plain": (F64_CHAIN, 102808), "sighted": ("large_build_GS<T,sighted> + " + F64_CHAIN, 102808),
+                                                     "gated": ("large_frontend_kernel<T,gated> + " + F64_CHAIN, 107416),
+                                                     "gated+sighted": ("large_frontend_kernel<T,gated> + large_build_GS<T,sighted> + " + F64_CHAIN, 107416)}),
+    "ukf-large": ("ukf", 80, "f64", True, 192, {"plain": (UKF_CHAIN, 102808), "gated": ("ukf_large_frontend_kernel<gated> + " + UKF_CHAIN, 107416)}),
+    "ekf-f32-64": ("ekf", 12, "f32", False, 64, {"plain": (F32_CHAIN, 99992), "sighted": ("large_build_GS<T,sighted> + " + F32_CHAIN, 99992),
+                                                 "gated": ("large_frontend_kernel<T,gated> + " + F32_CHAIN, 101528),
+                                                 "gated+sighted": ("large_frontend_kernel<T,gated> + large_build_GS<T,sighted> + " + F32_CHAIN, 101528)}),
+}
 
-    cap = tg.dim_cap(96) if large else tg.dim_cap(12)
-    c = Core(kind, cap, batch=1, max_obs=8, max_wait=2048 if large else 64, flags=CFG_UKF_LARGE if (large and kind == "ukf") else 0)
-    off = c.kernel_info()
-    c.set_replay_gate(GATE)
-    on = c.kernel_info()
-    assert on["name"] != off["name"] and ("gated" in on["name"] or "true" in on["name"])
-    assert on["lds_bytes"] == off["lds_bytes"] + (6 * 8 * (c.layout()[0] // 2) if large else 0)  # the single-CU kernels overlay sH
-    assert on["lds_bytes"] <= 160 * 1024
+
+@pytest.mark.parametrize("ctx", list(KERNEL_INFO))
+def test_kernel_names(ctx, built, monkeypatch):
+    """kernel_info() in every state a context can be in, against the literals above; nothing is launched"""
+    from awesomeslam_amd.core import CFG_UKF_LARGE, Core, F32, F64
+
+    for k in ("ASLAM_LARGE_GROUPS", "ASLAM_CHOL_RESIDENT", "ASLAM_RIGHT_STEP", "ASLAM_BF16_PIPE", "ASLAM_KEEP_L32", "ASLAM_BORDER"):
+        monkeypatch.delenv(k, raising=False)
+    kind, L, dtype, large_ukf, NP, want = KERNEL_INFO[ctx]
+    large = NP > 144 or dtype == "f32"
+    c = Core(kind, tg.dim_cap(L), batch=1, max_obs=8, max_wait=2048 if large else 64, dtype=F32 if dtype == "f32" else F64,
+             flags=CFG_UKF_LARGE if large_ukf else 0)
+    assert c.layout()[0] == NP
+    got = {}
+    for state in ("plain", "sighted", "gated+sighted", "gated"):
+        if state not in want:
+            continue
+        c.set_replay_gate(GATE if "gated" in state else 0.0)
+        if kind == "ekf":
+            c.sighted_only("sighted" in state)
+        info = c.kernel_info()
+        got[state] = (info["name"], info["lds_bytes"])
+    assert got == want
+    off, on = got["plain"], got["gated"]
+    assert on[0] != off[0] and ("gated" in on[0] or "true" in on[0])
+    assert on[1] == off[1] + (6 * 8 * (NP // 2) if large else 0)  # the single-CU kernels overlay sH
+    assert on[1] <= 160 * 1024
     c.close()
 
 
