@@ -32,7 +32,7 @@ CORE_SYMBOLS = (
     "aslam_get_sightings", "aslam_select_stale",
     "aslam_sighted_update_enable", "aslam_get_sighted", "aslam_ekf_step_sighted", "aslam_ekf_step_batch_sighted",
     "aslam_merge_landmarks", "aslam_select_duplicates",
-    "aslam_gate_observations",
+    "aslam_gate_observations", "aslam_joint_compat", "aslam_chi2_point",
     "aslam_set_replay_gate", "aslam_get_replay_gate", "aslam_get_assoc_rejected",
 )
 NODE_SYMBOLS = (
@@ -42,7 +42,7 @@ NODE_SYMBOLS = (
     "aslam_node_set_params", "aslam_node_get_params", "aslam_node_remove_landmarks",
     "aslam_node_get_sightings", "aslam_node_remove_stale", "aslam_node_set_sighted_only",
     "aslam_node_merge_landmarks", "aslam_node_merge_duplicates",
-    "aslam_node_set_assoc_gate", "aslam_node_assoc_rejected",
+    "aslam_node_set_assoc_gate", "aslam_node_assoc_rejected", "aslam_node_set_joint_prob", "aslam_node_joint_rejected",
     "aslam_node_join_map",
 )
 TRACE_FILE_SYMBOLS = (
@@ -213,6 +213,8 @@ def core_lib():
         L.aslam_merge_landmarks.argtypes = [vp, vp, ci, ci, cd, vp, vp]
         L.aslam_select_duplicates.argtypes = [vp, pd, pd, vp, ci, vp]
         L.aslam_gate_observations.argtypes = [vp, vp, ci, ci, ctypes.POINTER(ctypes.c_int32), pd, vp, vp, vp]
+        L.aslam_joint_compat.argtypes = [vp, vp, ci, ci, ctypes.POINTER(ctypes.c_int32), vp, pd, vp, vp, vp, vp, vp]
+        L.aslam_chi2_point.argtypes = [cd, ci, pd]
         L.aslam_set_replay_gate.argtypes = [vp, ci, cd]
         L.aslam_get_replay_gate.argtypes = [vp, ci, pd]
         L.aslam_get_assoc_rejected.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_uint64)]
@@ -271,6 +273,9 @@ def node_lib():
         L.aslam_node_set_assoc_gate.argtypes = [vp, ctypes.c_double]
         L.aslam_node_assoc_rejected.argtypes = [vp]
         L.aslam_node_assoc_rejected.restype = ctypes.c_uint64
+        L.aslam_node_set_joint_prob.argtypes = [vp, ctypes.c_double]
+        L.aslam_node_joint_rejected.argtypes = [vp]
+        L.aslam_node_joint_rejected.restype = ctypes.c_uint64
         # include/aslam_trace_file.h
         L.aslam_trace_file_error.restype = ctypes.c_char_p
         L.aslam_trace_file_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
@@ -293,6 +298,18 @@ def _ptr(a, ct):
 def _chk(rc):
     if rc != 0:
         raise AslamError(f"aslam_core error {rc}: {core_lib().aslam_last_error().decode()}")
+
+
+def chi2_point(prob, dof):
+    """The `prob` quantile of chi-square with `dof` degrees of freedom (aslam_chi2_point; host arithmetic, no device needed)."""
+    out = ctypes.c_double()
+    _chk(core_lib().aslam_chi2_point(float(prob), int(dof), ctypes.byref(out)))
+    return out.value
+
+
+def joint_gates(prob, m_max):
+    """The table aslam_joint_compat takes: [0, chi2(prob, 2), chi2(prob, 4), ..., chi2(prob, 2 m_max)] -- entry m bounds D2 of m pairings."""
+    return np.array([0.0] + [chi2_point(prob, 2 * m) for m in range(1, int(m_max) + 1)], np.float64)
 
 
 SCAN_SYMBOLS = ("aslam_scan_landmarks",)
@@ -893,6 +910,57 @@ class Core:
         _chk(core_lib().aslam_gate_observations(self._h, obs_ptr, int(ldo), 1 if is_device else 0, _ptr(k, ctypes.c_int32), _ptr(g, ctypes.c_double),
                                                 assoc_ptr, mdist_ptr, stream))
 
+    # ---- joint compatibility of the gated pairings (aslam_joint_compat)
+    def joint_compat(self, obs, n_obs, cand=None, prob=0.99, ic_gate=9.21, stream=None):
+        """The sequential joint-compatibility test of aslam_joint_compat on the candidates `cand` ([batch, ldo] int32, a NumPy array or a device
+        tensor; None: aslam_gate_observations at `ic_gate` runs first and the joint test takes its output in place, on the device).  `obs`,
+        `n_obs`: as for gate_observations, ldo <= 64.  `prob`: the chi-square probability of the bounds (joint_gates), None = evaluate mode
+        (every usable candidate is accepted, the call reports the numbers of the given hypothesis).  Returns (assoc [batch, ldo] int32,
+        incr [batch, ldo] float64, D2 [batch], logdet [batch], accepted [batch], refused [batch]).  The decisions depend on the message order.
+        Reads the filters, changes nothing."""
+        import torch
+
+        if hasattr(obs, "data_ptr"):
+            if obs.dim() != 3 or obs.shape[0] != self.batch or obs.shape[2] != 2 or obs.dtype != torch.float32 or not obs.is_contiguous():
+                raise ValueError("a device obs is a contiguous [batch, ldo, 2] float32 tensor")
+            ptr, ldo, dev = obs.data_ptr(), obs.shape[1], True
+        else:
+            obs = np.ascontiguousarray(obs, np.float32)
+            if obs.ndim != 3 or obs.shape[0] != self.batch or obs.shape[2] != 2:
+                raise ValueError("`obs` is [batch, ldo, 2]")
+            ptr, ldo, dev = obs.ctypes.data, obs.shape[1], False
+        shape = (self.batch, max(ldo, 1))
+        if cand is None:
+            assoc = torch.empty(shape, dtype=torch.int32, device="cuda")
+            self.gate_observations_ptr(ptr, ldo, dev, n_obs, ic_gate, assoc.data_ptr(), None, stream)
+        elif hasattr(cand, "data_ptr"):
+            if tuple(cand.shape) != shape or cand.dtype != torch.int32 or not cand.is_contiguous():
+                raise ValueError("a device cand is a contiguous [batch, ldo] int32 tensor")
+            assoc = cand.clone()
+        else:
+            cand = np.ascontiguousarray(cand, np.int32)
+            if cand.shape != shape:
+                raise ValueError("`cand` is [batch, ldo]")
+            assoc = torch.from_numpy(cand).cuda()
+        incr = torch.empty(shape, dtype=torch.float64, device="cuda")
+        joint = torch.empty((self.batch, 2), dtype=torch.float64, device="cuda")
+        count = torch.empty((self.batch, 2), dtype=torch.int32, device="cuda")
+        tab = None if prob is None else joint_gates(prob, ldo)
+        self.joint_compat_ptr(ptr, ldo, dev, n_obs, assoc.data_ptr(), tab, assoc.data_ptr(), incr.data_ptr(), joint.data_ptr(), count.data_ptr(), stream)
+        self.sync(stream)
+        joint, count = joint.cpu().numpy(), count.cpu().numpy()
+        return assoc.cpu().numpy(), incr.cpu().numpy(), joint[:, 0].copy(), joint[:, 1].copy(), count[:, 0].copy(), count[:, 1].copy()
+
+    def joint_compat_ptr(self, obs_ptr, ldo, is_device, n_obs, cand_ptr, gate_tab, assoc_ptr, incr_ptr, joint_ptr, count_ptr, stream=None):
+        """aslam_joint_compat as it is: raw pointers (ints) to obs [batch][ldo][2] f32, to the device candidates and outputs; n_obs [batch] and
+        gate_tab ([ldo + 1] float64, or None for evaluate mode) are host values.  Asynchronous on `stream`."""
+        k = None if n_obs is None else np.ascontiguousarray(np.broadcast_to(np.asarray(n_obs, np.int32), (self.batch,)))
+        g = None if gate_tab is None else np.ascontiguousarray(gate_tab, np.float64)
+        if g is not None and g.shape != (int(ldo) + 1,) and int(ldo) >= 1:
+            raise ValueError("`gate_tab` is [ldo + 1]")
+        _chk(core_lib().aslam_joint_compat(self._h, obs_ptr, int(ldo), 1 if is_device else 0, _ptr(k, ctypes.c_int32), cand_ptr, _ptr(g, ctypes.c_double),
+                                           assoc_ptr, incr_ptr, joint_ptr, count_ptr, stream))
+
     # ---- the same gate inside the replay seam (aslam_set_replay_gate)
     def set_replay_gate(self, gate, traj=None):
         """Associate by the Mahalanobis gate inside replay() / replay_stats() for filter `traj` (None: every filter): 0 = the Euclidean rule (the
@@ -1077,6 +1145,17 @@ class Node:
         freedom); 0, the default, keeps the reference's Euclidean rule.  A negative or NaN value is refused."""
         if node_lib().aslam_node_set_assoc_gate(self._h, float(gate)) != 0:
             raise AslamError(node_lib().aslam_node_error().decode())
+
+    def set_joint_prob(self, prob):
+        """FilterNode::setJointProb: behind the Mahalanobis gate (set_assoc_gate > 0), test the gated pairings of every message jointly
+        (aslam_joint_compat) at the chi-square probability `prob` in (0, 1); 0 = off, the default.  A pairing the joint test refuses is dropped and
+        counted in joint_rejected().  AslamError on any other value."""
+        if node_lib().aslam_node_set_joint_prob(self._h, float(prob)) != 0:
+            raise AslamError(node_lib().aslam_node_error().decode())
+
+    def joint_rejected(self):
+        """FilterNode::jointRejected: pairings the individual gate accepted and the joint test refused."""
+        return int(node_lib().aslam_node_joint_rejected(self._h))
 
     def assoc_rejected(self):
         """FilterNode::assocRejected: observations dropped because the gate refused them while the Euclidean rule would have associated them."""

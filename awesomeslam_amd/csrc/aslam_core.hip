@@ -29,6 +29,7 @@
 #include "merge.h"
 #include "join.h"
 #include "assoc.h"
+#include "joint.h"
 #if ASLAM_HAVE_UKF
 #include "ukf_small.h"
 #include "ukf_large.h"
@@ -2049,6 +2050,152 @@ int aslam_gate_observations(aslam_ctx *c, const float *obs, int ldo, int is_devi
         hipLaunchKernelGGL(assoc_gate, dim3((unsigned)B), dim3(ASSOC_WG), 0, st, (const double *)c->dv.X, (const double *)(c->large ? c->largeP : c->dv.P),
                            (const int *)c->dv.n, c->NP, (const aslam_params *)c->params_dev, odev, ldo, (const int32_t *)s.at<int32_t>(o_n),
                            (const double *)s.at<double>(o_gate), assoc_dev, mdist_dev);
+        HIP_TRY(hipGetLastError());
+        return ASLAM_OK;
+}
+
+/* ---- joint compatibility (joint.h) ------------------------------------------------------------------------------------------ */
+namespace
+{
+/// the regularised lower incomplete gamma function P(a, x), a > 0, x >= 0: the series below a + 1, the continued fraction (modified Lentz) above
+double gamma_p(double a, double x)
+{
+        if (!(x > 0.0))
+                return 0.0;
+        const double lead = std::exp(-x + a * std::log(x) - std::lgamma(a));
+        if (x < a + 1.0)
+        {
+                double term = 1.0 / a, sum = term;
+                for (int k = 1; k < 10000; ++k)
+                {
+                        term *= x / (a + k);
+                        sum += term;
+                        if (std::fabs(term) < std::fabs(sum) * 1e-17)
+                                break;
+                }
+                return lead * sum;
+        }
+        const double tiny = 1e-300;
+        double bq = x + 1.0 - a, cq = 1.0 / tiny, dq = 1.0 / bq, h = dq;
+        for (int k = 1; k < 10000; ++k)
+        {
+                const double an = -(double)k * ((double)k - a);
+                bq += 2.0;
+                dq = an * dq + bq;
+                dq = std::fabs(dq) < tiny ? tiny : dq;
+                cq = bq + an / cq;
+                cq = std::fabs(cq) < tiny ? tiny : cq;
+                dq = 1.0 / dq;
+                const double del = dq * cq;
+                h *= del;
+                if (std::fabs(del - 1.0) < 1e-16)
+                        break;
+        }
+        return 1.0 - lead * h;
+}
+
+/// whether the byte ranges [p, p + np) and [q, q + nq) share a byte (a null pointer shares none)
+bool ranges_overlap(const void *p, size_t np, const void *q, size_t nq)
+{
+        const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+        return p && q && a < b + nq && b < a + np;
+}
+} // namespace
+
+int aslam_chi2_point(double prob, int dof, double *out)
+{
+        const std::string who = "aslam_chi2_point: ";
+        if (!out)
+                return fail(ASLAM_ERR_ARG, who + "null out");
+        if (!(prob > 0.0 && prob < 1.0))
+                return fail(ASLAM_ERR_ARG, who + "prob must lie inside (0, 1)");
+        if (dof < 1)
+                return fail(ASLAM_ERR_ARG, who + "dof must be at least 1");
+        const double a = 0.5 * dof;
+        double lo = 0.0, hi = 2.0 * a + 10.0; // (x = 2 * the gamma variable)
+        for (int k = 0; k < 64 && gamma_p(a, 0.5 * hi) < prob; ++k)
+                lo = hi, hi *= 2.0;
+        for (int k = 0; k < 200; ++k)
+        {
+                const double mid = 0.5 * (lo + hi);
+                if (!(lo < mid && mid < hi))
+                        break;
+                (gamma_p(a, 0.5 * mid) < prob ? lo : hi) = mid;
+        }
+        *out = 0.5 * (lo + hi);
+        return ASLAM_OK;
+}
+
+int aslam_joint_compat(aslam_ctx *c, const float *obs, int ldo, int is_device, const int32_t *n_obs, const int32_t *cand_dev, const double *gate_tab,
+                       int32_t *assoc_dev, double *incr_dev, double *joint_dev, int32_t *count_dev, void *stream)
+{
+        static_assert(JOINT_MAX_OBS == ASLAM_JC_MAX_OBS, "joint.h and aslam_core.h name one cap");
+        const std::string who = "aslam_joint_compat: ";
+        if (!c)
+                return fail(ASLAM_ERR_ARG, who + "null context");
+        const struct
+        {
+                const char *name;
+                const void *p;
+                size_t per_filter; // bytes, in units of ldo where `per_obs`
+                bool per_obs, device, required;
+        } arg[] = {{"obs", obs, sizeof(float) * 2, true, is_device != 0, true},
+                   {"n_obs", n_obs, 0, false, false, true},
+                   {"cand_dev", cand_dev, sizeof(int32_t), true, true, true},
+                   {"assoc_dev", assoc_dev, sizeof(int32_t), true, true, true},
+                   {"incr_dev", incr_dev, sizeof(double), true, true, false},
+                   {"joint_dev", joint_dev, sizeof(double) * 2, false, true, true},
+                   {"count_dev", count_dev, sizeof(int32_t) * 2, false, true, true}};
+        for (const auto &a : arg)
+                if (a.required && !a.p)
+                        return fail(ASLAM_ERR_ARG, who + "null " + a.name);
+        if (ldo < 1)
+                return fail(ASLAM_ERR_ARG, who + "ldo must be at least 1");
+        if (ldo > ASLAM_JC_MAX_OBS)
+                return fail(ASLAM_ERR_UNSUPPORTED, who + "ldo = " + std::to_string(ldo) + " is beyond ASLAM_JC_MAX_OBS = " + std::to_string(ASLAM_JC_MAX_OBS));
+        const int B = c->cfg.batch;
+        for (int b = 0; b < B; ++b)
+                if (n_obs[b] < 0 || n_obs[b] > ldo)
+                        return fail(ASLAM_ERR_ARG, who + "n_obs[" + std::to_string(b) + "] = " + std::to_string(n_obs[b]) + " is outside 0 .. ldo (filter " +
+                                                       std::to_string(b) + ")");
+        for (int m = 1; gate_tab && m <= ldo; ++m)
+                if (!(gate_tab[m] > 0.0))
+                        return fail(ASLAM_ERR_ARG, who + "gate_tab[" + std::to_string(m) + "] must be positive");
+        for (const auto &a : arg)
+                if (a.device && ((uintptr_t)a.p & 15))
+                        return fail(ASLAM_ERR_ARG, who + (&a == &arg[0] ? "a device obs" : a.name) + " must be 16-byte aligned");
+        // two device arrays may not share a byte, but for assoc_dev == cand_dev exactly (the chain gate -> joint runs in place)
+        auto bytes = [&](const auto &a) { return a.per_filter * (size_t)B * (a.per_obs ? (size_t)ldo : 1); };
+        for (const auto &a : arg)
+                for (const auto &o : arg)
+                        if (&a < &o && a.device && o.device && ranges_overlap(a.p, bytes(a), o.p, bytes(o)) &&
+                            !(&a == &arg[2] && &o == &arg[3] && a.p == o.p))
+                                return fail(ASLAM_ERR_ARG, who + a.name + " and " + o.name + " overlap");
+        int rc = sync_ctx(c);
+        // staging: the gate table | n_obs | a host array's copy
+        const size_t obs_bytes = sizeof(float) * 2 * (size_t)B * ldo;
+        Staging s{c};
+        const size_t o_tab = s.take(gate_tab ? sizeof(double) * (ldo + 1) : 0), o_n = s.take(sizeof(int32_t) * B), o_obs = s.take(is_device ? 0 : obs_bytes);
+        if (rc == ASLAM_OK)
+                rc = s.reserve();
+        if (rc != ASLAM_OK)
+                return rc;
+        if (gate_tab)
+                HIP_TRY(hipMemcpy(s.at<double>(o_tab), gate_tab, sizeof(double) * (ldo + 1), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s.at<int32_t>(o_n), n_obs, sizeof(int32_t) * B, hipMemcpyHostToDevice));
+        const float *odev = obs;
+        if (!is_device)
+        {
+                HIP_TRY(hipMemcpy(s.at<float>(o_obs), obs, obs_bytes, hipMemcpyHostToDevice));
+                odev = s.at<float>(o_obs);
+        }
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        c->last_stream = st;
+        const size_t lds = JointLds{ldo}.bytes();
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(joint_compat), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(joint_compat, dim3((unsigned)B), dim3(JOINT_WG), lds, st, (const double *)c->dv.X, (const double *)(c->large ? c->largeP : c->dv.P),
+                           (const int *)c->dv.n, c->NP, (const aslam_params *)c->params_dev, odev, ldo, (const int32_t *)s.at<int32_t>(o_n), cand_dev,
+                           gate_tab ? (const double *)s.at<double>(o_tab) : nullptr, assoc_dev, incr_dev, joint_dev, count_dev);
         HIP_TRY(hipGetLastError());
         return ASLAM_OK;
 }

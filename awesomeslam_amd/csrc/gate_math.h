@@ -60,6 +60,22 @@ __device__ __forceinline__ GateLandmark gate_landmark(double px, double py, doub
         return {rh, atan2(dy, dx) - th, s00, s10, s11, valid ? det : 0.0};
 }
 
+/// the Jacobian alone, for the joint test (joint.h): H_k (2 x 5 over the columns 0, 1, 2, a0, a1), q and the predicted reading, from the
+/// same expressions as gate_landmark (which keeps its own text: the replay seam's bit-for-bit guarantees hang on its rounding sequence)
+struct GateJacobian
+{
+        double h[2][5];
+        double q, rh, bh;
+};
+
+__device__ __forceinline__ GateJacobian gate_jacobian(double px, double py, double th, double lx, double ly)
+{
+        const double dx = lx - px, dy = ly - py;
+        const double q = dx * dx + dy * dy;
+        const double rh = sqrt(q);
+        return {{{-dx / rh, -dy / rh, 0.0, dx / rh, dy / rh}, {dy / q, -dx / q, -1.0, -dy / q, dx / q}}, q, rh, atan2(dy, dx) - th};
+}
+
 /// m of observation (r, beta) against a landmark's terms (det > 0 is the caller's test)
 __device__ __forceinline__ double gate_pair(double r, double beta, double rh, double bh, double s00, double s10, double s11, double det)
 {

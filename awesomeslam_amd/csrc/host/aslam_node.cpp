@@ -369,6 +369,9 @@ int FilterNode::mergeDuplicates(double gate, double max_dist, double noise_var)
 // -- hipError_t and hipMemcpyKind are int-sized enums -- and bound weakly too, so that the mirror still links where no HIP runtime is.
 extern "C" {
 int aslam_gate_observations(aslam_ctx *, const float *, int, int, const int32_t *, const double *, int32_t *, double *, void *) __attribute__((weak));
+int aslam_joint_compat(aslam_ctx *, const float *, int, int, const int32_t *, const int32_t *, const double *, int32_t *, double *, double *, int32_t *,
+                       void *) __attribute__((weak));
+int aslam_chi2_point(double, int, double *) __attribute__((weak));
 int hipMalloc(void **, size_t) __attribute__((weak));
 int hipFree(void *) __attribute__((weak));
 int hipMemcpy(void *, const void *, size_t, int) __attribute__((weak));
@@ -379,6 +382,23 @@ void FilterNode::setAssocGate(double gate)
         if (!(gate >= 0.0))
                 throw std::runtime_error("setAssocGate: the gate must be positive, or 0 for off");
         assoc_gate = gate;
+}
+
+void FilterNode::setJointProb(double prob)
+{
+        if (!(prob >= 0.0 && prob < 1.0))
+                throw std::runtime_error("setJointProb: the probability must lie inside (0, 1), or be 0 for off");
+        std::vector<double> tab;
+        if (prob > 0.0)
+        {
+                if (!aslam_joint_compat || !aslam_chi2_point)
+                        throw std::runtime_error("this core has no joint-compatibility test");
+                tab.assign(ASLAM_JC_MAX_OBS + 1, 0.0);
+                for (int m = 1; m <= ASLAM_JC_MAX_OBS; ++m)
+                        check(aslam_chi2_point(prob, 2 * m, &tab[m]), "aslam_chi2_point");
+        }
+        joint_prob = prob;
+        joint_tab.swap(tab);
 }
 
 /// updateZ's association with the gate on and `mapped` > 0 landmarks: one aslam_gate_observations call for the stored message, then the
@@ -396,6 +416,11 @@ void FilterNode::associateGated(uint32_t mapped, std::vector<uint8_t> &sighted)
                 ob[2 * j] = obs.range;
                 ob[2 * j + 1] = obs.bearing;
         }
+        // the device array: the indices of the message, and behind them (with the joint test on) D2 and log det C, the two counters, and the
+        // increment of every pairing -- finite where the joint test saw a usable candidate, so finite and -1 names a pairing it refused
+        const bool joint = joint_prob > 0.0;
+        const size_t idx_bytes = (sizeof(int32_t) * count + 15) / 16 * 16;
+        const size_t tail = joint ? 32 + sizeof(double) * count : 0; // [2] f64 | [2] i32 and padding | [count] f64
         if (count > gate_cap)
         {
                 if (gate_dev)
@@ -403,16 +428,29 @@ void FilterNode::associateGated(uint32_t mapped, std::vector<uint8_t> &sighted)
                 gate_dev = nullptr;
                 gate_cap = 0;
                 const size_t cap = std::max<size_t>(64, 2 * count);
-                if (hipMalloc(&gate_dev, sizeof(int32_t) * cap) != 0)
+                if (hipMalloc(&gate_dev, (sizeof(int32_t) + sizeof(double)) * cap + 48) != 0) // (room for the joint test's tail at any count <= cap)
                         throw std::runtime_error("associateGated: hipMalloc failed");
                 gate_cap = cap;
         }
         const int32_t n_obs = (int32_t)count;
-        std::vector<int32_t> assoc(count, -1);
+        std::vector<unsigned char> back(idx_bytes + tail);
         check(aslam_gate_observations(ctx, ob.data(), (int)count, 0, &n_obs, &assoc_gate, static_cast<int32_t *>(gate_dev), nullptr, nullptr),
               "aslam_gate_observations");
-        if (hipMemcpy(assoc.data(), gate_dev, sizeof(int32_t) * count, 2 /* hipMemcpyDeviceToHost: waits for the launch on the default stream */) != 0)
+        if (joint)
+        {
+                char *tail_dev = static_cast<char *>(gate_dev) + idx_bytes;
+                int32_t *idx = static_cast<int32_t *>(gate_dev);
+                check(aslam_joint_compat(ctx, ob.data(), (int)count, 0, &n_obs, idx, joint_tab.data(), idx, reinterpret_cast<double *>(tail_dev + 32),
+                                         reinterpret_cast<double *>(tail_dev), reinterpret_cast<int32_t *>(tail_dev + 16), nullptr),
+                      "aslam_joint_compat");
+        }
+        if (hipMemcpy(back.data(), gate_dev, back.size(), 2 /* hipMemcpyDeviceToHost: waits for the launches on the default stream */) != 0)
                 throw std::runtime_error("associateGated: hipMemcpy failed");
+        std::vector<int32_t> assoc(count, -1);
+        std::vector<double> incr(count, INFINITY);
+        std::memcpy(assoc.data(), back.data(), sizeof(int32_t) * count);
+        if (joint)
+                std::memcpy(incr.data(), back.data() + idx_bytes + 32, sizeof(double) * count);
         for (size_t j = 0; j < count; ++j)
         {
                 const LaserData &obs = sensor_landmark[j];
@@ -421,6 +459,11 @@ void FilterNode::associateGated(uint32_t mapped, std::vector<uint8_t> &sighted)
                         param_Z[3 + 2 * assoc[j]] = obs.range;
                         param_Z[4 + 2 * assoc[j]] = obs.bearing;
                         sighted[assoc[j]] = 1;
+                        continue;
+                }
+                if (std::isfinite(incr[j]))
+                {
+                        joint_rejected += 1; // dropped: the gate paired it, the joint test refuses the pairing beside the ones before it
                         continue;
                 }
                 // the reference's own test (updateZ below), for the verdict alone
@@ -865,6 +908,27 @@ int aslam_node_set_assoc_gate(aslam_node *n, double gate)
 uint64_t aslam_node_assoc_rejected(const aslam_node *n)
 {
         return n->impl->assocRejected();
+}
+
+int aslam_node_set_joint_prob(aslam_node *n, double prob)
+{
+        try
+        {
+                if (!n)
+                        throw std::runtime_error("null argument");
+                n->impl->setJointProb(prob);
+                return 0;
+        }
+        catch (const std::exception &e)
+        {
+                g_node_err = e.what();
+                return -1;
+        }
+}
+
+uint64_t aslam_node_joint_rejected(const aslam_node *n)
+{
+        return n->impl->jointRejected();
 }
 
 int aslam_node_get_sightings(const aslam_node *n, uint32_t *last_seen, uint32_t *hits, int cap, uint32_t *clock)

@@ -177,12 +177,32 @@ class FilterNode
         {
                 return assoc_rejected;
         }
+        /// Joint compatibility behind the gate (aslam_joint_compat of aslam_core.h).  prob = 0, the default: off.  prob in (0, 1), while the
+        /// gate above is > 0: the pairings the gate accepted for a message are tested as a set, in message order, in place on the same device
+        /// array (aslam_gate_observations -> aslam_joint_compat, one copy back), against the chi-square points of probability `prob` for 2, 4,
+        /// ... degrees of freedom (aslam_chi2_point; the table is rebuilt by this call, not per callback).  A pairing the joint test refuses
+        /// is handled like one the gate refuses within assoc_dist: DROPPED, neither a match nor wait-list evidence, and counted in
+        /// jointRejected().  The decisions depend on the order of the message.  Messages of more than ASLAM_JC_MAX_OBS observations are
+        /// refused by the core (the callback throws).  With the joint test off the mirror computes bit for bit what it did without it.
+        /// Throws on a prob outside [0, 1) or NaN, and with a core that lacks the entry points (bound weakly, like the gate's).
+        void setJointProb(double prob);
+        double jointProb() const
+        {
+                return joint_prob;
+        }
+        uint64_t jointRejected() const
+        {
+                return joint_rejected;
+        }
 
       private:
         void compactHost(const std::vector<uint8_t> &mask);
         void associateGated(uint32_t mapped, std::vector<uint8_t> &sighted);
         double assoc_gate = 0.0;
         uint64_t assoc_rejected = 0;
+        double joint_prob = 0.0;
+        uint64_t joint_rejected = 0;
+        std::vector<double> joint_tab; // [ASLAM_JC_MAX_OBS + 1] chi-square points of joint_prob, entry m for m pairings
         void *gate_dev = nullptr; // device [gate_cap] i32: the indices of one gated message
         size_t gate_cap = 0;
         int filter;
@@ -274,6 +294,10 @@ int aslam_node_join_map(aslam_node *n, const void *blob, int64_t bytes, int reco
 int aslam_node_set_assoc_gate(aslam_node *n, double gate);
 /* FilterNode::assocRejected: observations the gate dropped although the Euclidean rule would have associated them. */
 uint64_t aslam_node_assoc_rejected(const aslam_node *n);
+/* FilterNode::setJointProb (0 = off, the default): 0, or -1 with aslam_node_error() (a value outside [0, 1), a core without the entry points). */
+int aslam_node_set_joint_prob(aslam_node *n, double prob);
+/* FilterNode::jointRejected: pairings the gate accepted and the joint test refused. */
+uint64_t aslam_node_joint_rejected(const aslam_node *n);
 /* Narrow `count` recorded odometry messages ([count][8]: px,py,qw,qx,qy,qz,vx,wz) the way cbOdom/updateZandA do
  * (ekf.cpp:139-142): pose[count][2], yaw[count] = quat2euler(...) as binary32, twist[count][2]. */
 void aslam_host_narrow_odom(int64_t count, const double *odom, double *pose, float *yaw, double *twist);

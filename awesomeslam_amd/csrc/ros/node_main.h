@@ -107,8 +107,13 @@ template <class Filter> int node_main(int argc, char **argv, const char *node_na
         // freedom) and drop the observations it refuses although they lie within assoc_dist.  0, the default: the reference's Euclidean rule
         double assoc_gate = 0.0;
         ros::param::param("~assoc_gate", assoc_gate, 0.0);
+        // ~joint_prob: behind the gate, test the gated pairings of a message jointly (FilterNode::setJointProb) at this chi-square probability
+        // and drop the ones the set refuses.  0, the default: off; values outside (0, 1) are taken as 0.  No effect while ~assoc_gate is 0
+        double joint_prob = 0.0;
+        ros::param::param("~joint_prob", joint_prob, 0.0);
         Node<Filter> a(max_landmark_count, queue_size);
         a.filter.setAssocGate(assoc_gate > 0.0 ? assoc_gate : 0.0);
+        a.filter.setJointProb(joint_prob > 0.0 && joint_prob < 1.0 ? joint_prob : 0.0);
         a.merge_gate = merge_gate > 0.0 ? merge_gate : 0.0;
         a.merge_dist = merge_dist > 0.0 ? merge_dist : 1.0;
         a.merge_period = merge_period < 1 ? 1u : (uint32_t)merge_period;

@@ -341,6 +341,46 @@ int aslam_select_duplicates(aslam_ctx *ctx, const double *gate, const double *ma
 int aslam_gate_observations(aslam_ctx *ctx, const float *obs, int ldo, int is_device, const int32_t *n_obs, const double *gate, int32_t *assoc_dev,
                             double *mdist_dev, void *stream);
 
+/* ---- joint compatibility of a hypothesis of pairings --------------------------------------------------- */
+/* The gate above decides each pairing alone.  The landmarks of a map are correlated through the pose, so pairings that each pass it can be
+   inconsistent as a set.  This call tests a hypothesis jointly, where P lives: the sequential compatibility nearest neighbour rule (Neira &
+   Tardos 2001 without the branch and bound).  Evaluated at the X and P the last callback left, all binary64, lower-triangle entries of P only
+   (entry (r, c) is read as P[max(r,c)][min(r,c)]).
+   The observations j = 0 .. n_obs[b]-1 are taken in message order, each with its candidate landmark cand[b][j] (normally the assoc_dev output of
+   aslam_gate_observations).  A candidate k is usable iff 0 <= k < L_b and q > 0; dx, dy, q, rh, bh and H_k are the gate's, and
+   nu_j = (r - rh, remainder(beta - bh, 2 pi)).  With A the ordered list of the pairings accepted so far, m = |A|:
+       C_A = the stack of H_i P(idx_i, idx_i') H_i'^T, + diag(r_range, r_bearing) of the filter's own aslam_params on the diagonal blocks
+       L_A = its lower Cholesky factor (2m x 2m)     z_A = L_A^-1 nu_A     D2 = |z_A|^2     logdet = 2 sum log L_A(ii)
+   and for a usable candidate j, by bordering:
+       c (2 x 2m) = the cross blocks H_j P(idx_j, idx_i) H_i^T, i in A       Y = c L_A^-T (forward substitution)       T = C_jj - Y Y^T
+       t00 = sqrt(T00)    t10 = T10 / t00    d = T11 - t10^2    t11 = sqrt(d)
+       w = nu_j - Y z_A   z0 = w0 / t00      z1 = (w1 - t10 z0) / t11      dd_j = z0^2 + z1^2
+   The candidate becomes unusable if T00 is not > 0, d is not > 0 or dd_j is not finite (a NaN fails every comparison).  It is accepted iff
+   D2 + dd_j < gate_tab[m + 1]: the two rows (Y | t00; t10 t11) join L_A, z0 and z1 join z_A, D2 += dd_j, logdet += 2 log(t00 t11), m += 1.
+   Otherwise it is refused by the joint test: nothing is appended, the refused counter goes up by one.  Two observations with one candidate may
+   both be accepted (R keeps C positive definite).  With gate_tab == NULL (evaluate mode) every usable candidate is accepted: the call reports
+   D2, log det C and the increments of the given hypothesis.  The rule is deterministic, O(m^3), and DEPENDS ON THE MESSAGE ORDER; there is no
+   search over alternative candidates.
+   obs, ldo, is_device, n_obs: as for aslam_gate_observations, ldo <= ASLAM_JC_MAX_OBS.  cand_dev: device [batch][ldo] i32.  gate_tab: host
+   [ldo + 1] f64 or NULL; gate_tab[m] bounds D2 of m pairings (the chi-square point of 2m degrees of freedom: aslam_chi2_point), entry 0 is
+   ignored, one table serves the batch.  assoc_dev: device [batch][ldo] i32, the candidate where accepted, else -1, -1 from n_obs[b] on;
+   assoc_dev == cand_dev exactly is allowed (the chain gate -> joint runs in place), every other overlap of two device arrays is refused.
+   incr_dev: device [batch][ldo] f64 or NULL: dd_j of every usable candidate, accepted or refused, +inf for an unusable or absent candidate and
+   from n_obs[b] on.  joint_dev: device [batch][2] f64 (D2, log det C_A; 0, 0 for an empty hypothesis).  count_dev: device [batch][2] i32
+   (accepted, refused by the joint test).  Every device pointer 16-byte aligned.
+   ASLAM_ERR_ARG, with a message that names the argument (and the filter, where there is one): a null obs, n_obs, cand_dev, assoc_dev,
+   joint_dev or count_dev, ldo < 1, an n_obs[b] outside 0 .. ldo, a gate_tab[m], m >= 1, that is not > 0 (infinity is allowed), a misaligned
+   or partially overlapping device pointer.  ASLAM_ERR_UNSUPPORTED: ldo > ASLAM_JC_MAX_OBS.  A refused call launches nothing.
+   Synchronises the context first, then runs on `stream` (one launch, one workgroup per filter), so a cand_dev written by
+   aslam_gate_observations on the same stream is in order.  Works on every kind of context (for the UKF it is this linearised test); writes
+   nothing a filter owns. */
+#define ASLAM_JC_MAX_OBS 64
+int aslam_joint_compat(aslam_ctx *ctx, const float *obs, int ldo, int is_device, const int32_t *n_obs, const int32_t *cand_dev, const double *gate_tab,
+                       int32_t *assoc_dev, double *incr_dev, double *joint_dev, int32_t *count_dev, void *stream);
+/* host only: *out = the `prob` quantile of chi-square with `dof` degrees of freedom (bisection on the regularised incomplete gamma function).
+   ASLAM_ERR_ARG for a null out, prob outside (0, 1) or dof < 1. */
+int aslam_chi2_point(double prob, int dof, double *out);
+
 /* The same gate inside the replay seam (aslam_replay[_stats]): per filter, off by default.  A callback of a filter whose gate is > 0, that
    starts with landmarks (n0 > 3) and has a non-empty stored message, associates as follows.  The evaluation point is the X and P the previous
    callback left (the motion of this odometry period is not added); bearings are normalised first, as ever.  For every observation j, m against
