@@ -3,9 +3,12 @@
 // The reference walks the 360 beams once, growing a cluster while consecutive points are closer than MIN_DIST_THRESH and
 // evaluating it when the chain breaks (:92-121).  As coded that is: clusters = maximal runs of "linked" beams
 // (link(t) = dist(p(t-1), p(t)) < thresh) that END BEFORE beam 359; the beam that breaks a chain belongs to no cluster
-// (`cluster.clear(); p1 = p2`, :113-120), except that beam 0 opens the first cluster (:84-85); a run that reaches beam 359
-// is never evaluated.  Runs are independent, so: links and run ends by ballots, one lane per run for the classifier
-// (:147-186) and the hyper fit (:192-298), outputs compacted in beam order.  binary32 where the reference computes in
+// (`cluster.clear(); p1 = p2`, :113-120), except that the beam the walk starts at opens the first cluster (:84-85); a run that
+// reaches beam 359 is never evaluated.  The walk starts at beam 0 unless beams 0 and 359 are linked: then the reference first
+// walks from beam 0 while a point compares closer than the threshold with ITSELF (:73-78) -- true for a finite point, false for
+// a beam without a return (inf - inf is NaN) -- and the walk proper starts one past the first such beam; only a scan without
+// one before beam 358 fails its assert(theta < 359).  Runs are independent, so: links and run ends by ballots, one lane per
+// run for the classifier (:147-186) and the hyper fit (:192-298), outputs compacted in beam order.  binary32 where the reference computes in
 // `float` (-ffp-contract=off); the 4x4 algebra of the fit in fp64.
 //
 // The fit: the reference takes the SVD Z = U S V^T of the n x 4 data matrix, Y = V S V^T, Q = Y Hinv Y, the eigenvector A*
@@ -285,12 +288,17 @@ __global__ __launch_bounds__(64) void scan_landmarks_kernel(const float *ranges,
         __syncthreads();
         // links between consecutive beams and ends of runs that stop before beam 359
         unsigned long long lm[6], em[6];
+        int first_open = SCAN_BEAMS; // the first beam whose point is not closer than the threshold to itself (inf or NaN)
 #pragma unroll
         for (int k = 0; k < 6; ++k)
         {
                 const int t = lane + 64 * k;
                 const bool link = (t >= 1 && t < SCAN_BEAMS) && eulerDistance(px[t - 1], py[t - 1], px[t], py[t]) < SCAN_LINK_DIST;
                 lm[k] = __ballot(link);
+                const bool open = t < SCAN_BEAMS && !(eulerDistance(px[t], py[t], px[t], py[t]) < SCAN_LINK_DIST);
+                const unsigned long long om = __ballot(open);
+                if (om && first_open == SCAN_BEAMS)
+                        first_open = 64 * k + __ffsll((long long)om) - 1;
         }
         if (lane == 0)
         {
@@ -302,8 +310,11 @@ __global__ __launch_bounds__(64) void scan_landmarks_kernel(const float *ranges,
         auto linked = [&](int t) -> bool { return (linkm[t >> 6] >> (t & 63)) & 1ull; };
         uint32_t status = 0;
         int nout = 0;
-        if (eulerDistance(px[0], py[0], px[SCAN_BEAMS - 1], py[SCAN_BEAMS - 1]) < SCAN_LINK_DIST)
-                status = 1u; // ASLAM_SCAN_REF_ABORT: the reference's assert(theta < 359), :69-81
+        // beams 0 and 359 linked: first_cluster takes beams 0 .. first_open and theta ends one past it (:69-79)
+        const bool wrapped = eulerDistance(px[0], py[0], px[SCAN_BEAMS - 1], py[SCAN_BEAMS - 1]) < SCAN_LINK_DIST;
+        const int start = wrapped ? first_open + 1 : 0;
+        if (start >= SCAN_BEAMS - 1)
+                status = 1u; // ASLAM_SCAN_REF_ABORT: the reference's assert(theta < 359), :82
         else
         {
                 int nruns = 0;
@@ -311,7 +322,7 @@ __global__ __launch_bounds__(64) void scan_landmarks_kernel(const float *ranges,
                 for (int k = 0; k < 6; ++k)
                 {
                         const int t = lane + 64 * k;
-                        const bool isend = t >= 1 && t + 1 < SCAN_BEAMS && linked(t) && !linked(t + 1);
+                        const bool isend = t >= start + 1 && t + 1 < SCAN_BEAMS && linked(t) && !linked(t + 1);
                         em[k] = __ballot(isend);
                         if (isend)
                                 ends[nruns + __popcll(em[k] & ((1ull << lane) - 1ull))] = (short)t;
@@ -327,14 +338,20 @@ __global__ __launch_bounds__(64) void scan_landmarks_kernel(const float *ranges,
                         {
                                 const int e = ends[j];
                                 int s = e;
-                                while (s - 1 >= 1 && linked(s - 1))
+                                while (s - 1 >= start + 1 && linked(s - 1))
                                         --s;
-                                const int s0 = (s == 1) ? 0 : s; // beam 0 opens the first cluster (:84-85)
+                                const int s0 = (s == start + 1) ? start : s; // the beam the walk starts at opens the first cluster (:84-85)
                                 const int n = e - s0 + 1;
                                 ScanPts c = {px, py, s0};
                                 if (n > SCAN_MIN_CLUSTER_POINTS && scan_classify(c, n))
                                 {
-                                        scan_fit(c, n, rg, bg);
+                                        if (wrapped && e == SCAN_BEAMS - 2)
+                                                // broken by beam 359 (theta == 360): the reference joins first_cluster, which ends with the
+                                                // non-finite point, before the fit (:103-111).  A landmark is published; what the dense
+                                                // solvers make of inf/NaN input is not pinned: NaN
+                                                rg = bg = __builtin_nanf("");
+                                        else
+                                                scan_fit(c, n, rg, bg);
                                         valid = true;
                                 }
                         }

@@ -21,8 +21,9 @@ extern "C" {
 #endif
 
 #define ASLAM_SCAN_BEAMS 360
-/* beams 0 and 359 are closer than MIN_DIST_THRESH: the reference walks theta off the scan and fails assert(theta < 359)
- * (sensor_landmark.cpp:69-81); no landmarks are produced for such a scan */
+/* beams 0 and 359 are closer than MIN_DIST_THRESH and no beam before 358 lacks a return (inf / NaN): the reference walks
+ * theta off the scan and fails assert(theta < 359) (sensor_landmark.cpp:69-82); no landmarks are produced for such a scan.
+ * With a beam without a return the walk ends there and the scan is processed from the next beam on. */
 #define ASLAM_SCAN_REF_ABORT 1u
 /* more than max_out landmarks: the list is truncated */
 #define ASLAM_SCAN_OVERFLOW 2u

@@ -1,9 +1,9 @@
 /*
  * aslam_oracle.cpp -- CPU oracle: Eigen-free, ROS-free restatement of the reference filter nodes.
  *
- * TEST INFRASTRUCTURE ONLY (see aslam_oracle.h).  "parity unpinned" by the reference: it has no
- * tests or golden vectors and cannot be built here; this file is pinned by oracle/np_oracle.py and
- * tests/golden/.
+ * TEST INFRASTRUCTURE ONLY (see aslam_oracle.h).  The reference has no tests or golden vectors; this
+ * file is pinned by the reference's own nodes compiled over ref_shim/ (ref_ekf.cpp, ref_ukf.cpp,
+ * tests/test_reference_parity.py, tests/golden/reference/), by oracle/np_oracle.py and by tests/golden/.
  *
  * Every function names the reference lines it restates (paths relative to /root/reference/awesome_slam).
  * The arithmetic keeps the reference's float/double mixing: wherever the reference

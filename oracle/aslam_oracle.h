@@ -9,11 +9,13 @@
  * check / time the HIP product path against the reference arithmetic.  Nothing under
  * awesomeslam_amd/ may include, link or call it.
  *
- * PARITY STATUS: "parity unpinned" by the reference -- the reference ships no tests,
- * fixtures or golden vectors and cannot be compiled here (Eigen and ROS
- * are absent).  The pins are this repo's own: an independent NumPy
- * restatement (oracle/np_oracle.py) must agree with this file, and committed fixtures under
- * tests/golden/ freeze both.
+ * PARITY STATUS: pinned to the reference's own source text.  The reference ships no tests,
+ * fixtures or golden vectors, and Eigen and ROS are absent; its
+ * nodes are compiled unmodified over oracle/ref_shim (Makefile target `ref`) behind this same
+ * interface (ref_ekf.cpp, ref_ukf.cpp -> _ref/libaslam_ref_{ekf,ukf}.so), and what they give is
+ * recorded under tests/golden/reference/.  tests/test_reference_parity.py holds this file and the
+ * independent NumPy restatement (oracle/np_oracle.py) against both; the self-generated fixtures
+ * under tests/golden/ freeze the larger configurations the reference's cap of 30 does not reach.
  *
  * The one sanctioned deviation from the reference: MAX_LANDMARK_COUNT (config.h:45) is a
  * run-time field (default 30) so that the 64- and 512-landmark configurations exist at all

@@ -6,7 +6,8 @@ import subprocess
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# ASLAM_ORACLE_LIB: another build of the same source (the Eigen-gated one, tests/test_oracle_eigen.py), loaded as it is
+# ASLAM_ORACLE_LIB: another library with the same interface -- the Eigen-gated build of the same source (tests/test_oracle_eigen.py)
+# or the reference's own node (oracle/_ref/libaslam_ref_{ekf,ukf}.so: one filter kind each, cap 30 only) -- loaded as it is
 _LIB = os.environ.get("ASLAM_ORACLE_LIB") or os.path.join(_HERE, "libaslam_oracle.so")
 
 EKF, UKF = 0, 1
@@ -25,41 +26,46 @@ def build(force=False):
 _lib = None
 
 
+def bind(path):
+    """Load one library that exports the orc_* interface of aslam_oracle.h and declare its signatures."""
+    L = ctypes.CDLL(path)
+    c_dp = ctypes.POINTER(ctypes.c_double)
+    c_fp = ctypes.POINTER(ctypes.c_float)
+    vp = ctypes.c_void_p
+    L.orc_create.restype = vp
+    L.orc_create.argtypes = [ctypes.c_int, ctypes.c_int]
+    L.orc_destroy.argtypes = [vp]
+    L.orc_sensor.argtypes = [vp, ctypes.c_int, c_dp, c_dp]
+    L.orc_odom.restype = ctypes.c_int
+    L.orc_odom.argtypes = [vp] + [ctypes.c_double] * 8 + [ctypes.c_float]
+    L.orc_slam.argtypes = [vp, ctypes.c_float, ctypes.c_float, ctypes.c_float]
+    L.orc_dim.restype = ctypes.c_int
+    L.orc_dim.argtypes = [vp]
+    L.orc_get.argtypes = [vp, c_dp, c_dp, c_dp]
+    L.orc_get_A.argtypes = [vp, c_dp, c_dp]
+    L.orc_set.argtypes = [vp, ctypes.c_int, c_dp, c_dp, c_dp, ctypes.c_double, ctypes.c_double]
+    L.orc_wait_size.restype = ctypes.c_int
+    L.orc_wait_size.argtypes = [vp]
+    L.orc_get_wait.argtypes = [vp, c_fp, c_fp, ctypes.POINTER(ctypes.c_uint32)]
+    L.orc_sensor_size.restype = ctypes.c_int
+    L.orc_sensor_size.argtypes = [vp]
+    L.orc_get_sensor.argtypes = [vp, c_fp, c_fp]
+    L.orc_get_weights.argtypes = [vp, c_dp, c_fp]
+    L.orc_replay.restype = ctypes.c_int64
+    L.orc_replay.argtypes = [vp, ctypes.c_int64, c_dp, c_fp, ctypes.POINTER(ctypes.c_uint8),
+                             ctypes.POINTER(ctypes.c_int32), c_dp, ctypes.c_int, c_dp,
+                             ctypes.POINTER(ctypes.c_int32)]
+    L.orc_normalize_angle.restype = ctypes.c_float
+    L.orc_normalize_angle.argtypes = [ctypes.c_float]
+    L.orc_quat2euler.restype = ctypes.c_float
+    L.orc_quat2euler.argtypes = [ctypes.c_float] * 4
+    return L
+
+
 def lib():
     global _lib
     if _lib is None:
-        L = ctypes.CDLL(build())
-        c_dp = ctypes.POINTER(ctypes.c_double)
-        c_fp = ctypes.POINTER(ctypes.c_float)
-        vp = ctypes.c_void_p
-        L.orc_create.restype = vp
-        L.orc_create.argtypes = [ctypes.c_int, ctypes.c_int]
-        L.orc_destroy.argtypes = [vp]
-        L.orc_sensor.argtypes = [vp, ctypes.c_int, c_dp, c_dp]
-        L.orc_odom.restype = ctypes.c_int
-        L.orc_odom.argtypes = [vp] + [ctypes.c_double] * 8 + [ctypes.c_float]
-        L.orc_slam.argtypes = [vp, ctypes.c_float, ctypes.c_float, ctypes.c_float]
-        L.orc_dim.restype = ctypes.c_int
-        L.orc_dim.argtypes = [vp]
-        L.orc_get.argtypes = [vp, c_dp, c_dp, c_dp]
-        L.orc_get_A.argtypes = [vp, c_dp, c_dp]
-        L.orc_set.argtypes = [vp, ctypes.c_int, c_dp, c_dp, c_dp, ctypes.c_double, ctypes.c_double]
-        L.orc_wait_size.restype = ctypes.c_int
-        L.orc_wait_size.argtypes = [vp]
-        L.orc_get_wait.argtypes = [vp, c_fp, c_fp, ctypes.POINTER(ctypes.c_uint32)]
-        L.orc_sensor_size.restype = ctypes.c_int
-        L.orc_sensor_size.argtypes = [vp]
-        L.orc_get_sensor.argtypes = [vp, c_fp, c_fp]
-        L.orc_get_weights.argtypes = [vp, c_dp, c_fp]
-        L.orc_replay.restype = ctypes.c_int64
-        L.orc_replay.argtypes = [vp, ctypes.c_int64, c_dp, c_fp, ctypes.POINTER(ctypes.c_uint8),
-                                 ctypes.POINTER(ctypes.c_int32), c_dp, ctypes.c_int, c_dp,
-                                 ctypes.POINTER(ctypes.c_int32)]
-        L.orc_normalize_angle.restype = ctypes.c_float
-        L.orc_normalize_angle.argtypes = [ctypes.c_float]
-        L.orc_quat2euler.restype = ctypes.c_float
-        L.orc_quat2euler.argtypes = [ctypes.c_float] * 4
-        _lib = L
+        _lib = bind(build())
     return _lib
 
 
@@ -70,34 +76,38 @@ def _p(a, ct):
 class CFilter:
     """EKFSlam / UKFSlam of the reference, ROS-free (C++ restatement)."""
 
-    def __init__(self, kind, max_landmark_count=30):
+    def __init__(self, kind, max_landmark_count=30, library=None):
+        """library: another binding of the same interface (bind()), e.g. the reference's own node (oracle/ref_oracle.py)"""
         self.kind = kind
-        self._h = lib().orc_create(_KIND[kind], int(max_landmark_count))
+        self._L = lib() if library is None else library
+        self._h = self._L.orc_create(_KIND[kind], int(max_landmark_count))
+        if not self._h:
+            raise ValueError(f"this library has no {kind} filter with max_landmark_count={max_landmark_count}")
 
     def __del__(self):
         if getattr(self, "_h", None):
-            lib().orc_destroy(self._h)
+            self._L.orc_destroy(self._h)
             self._h = None
 
     def sensor_msg(self, xs, ys):
         xs = np.ascontiguousarray(xs, np.float64)
         ys = np.ascontiguousarray(ys, np.float64)
-        lib().orc_sensor(self._h, len(xs), _p(xs, ctypes.c_double), _p(ys, ctypes.c_double))
+        self._L.orc_sensor(self._h, len(xs), _p(xs, ctypes.c_double), _p(ys, ctypes.c_double))
 
     def odom_msg(self, px, py, qw, qx, qy, qz, vx, wz, dt):
-        return lib().orc_odom(self._h, px, py, qw, qx, qy, qz, vx, wz, float(np.float32(dt)))
+        return self._L.orc_odom(self._h, px, py, qw, qx, qy, qz, vx, wz, float(np.float32(dt)))
 
     def slam(self, vx, az, dt):
-        lib().orc_slam(self._h, float(np.float32(vx)), float(np.float32(az)), float(np.float32(dt)))
+        self._L.orc_slam(self._h, float(np.float32(vx)), float(np.float32(az)), float(np.float32(dt)))
 
     @property
     def N(self):
-        return lib().orc_dim(self._h)
+        return self._L.orc_dim(self._h)
 
     def state(self):
         n = self.N
         X, Z, P = np.empty(n), np.empty(n), np.empty((n, n))
-        lib().orc_get(self._h, _p(X, ctypes.c_double), _p(Z, ctypes.c_double), _p(P, ctypes.c_double))
+        self._L.orc_get(self._h, _p(X, ctypes.c_double), _p(Z, ctypes.c_double), _p(P, ctypes.c_double))
         return X, Z, P
 
     @property
@@ -114,34 +124,34 @@ class CFilter:
 
     def A(self):
         a, b = ctypes.c_double(), ctypes.c_double()
-        lib().orc_get_A(self._h, ctypes.byref(a), ctypes.byref(b))
+        self._L.orc_get_A(self._h, ctypes.byref(a), ctypes.byref(b))
         return a.value, b.value
 
     def set_state(self, N, X, Z, P, a00=1.0, a10=0.0):
         X = np.ascontiguousarray(X, np.float64)
         Z = np.ascontiguousarray(Z, np.float64)
         P = np.ascontiguousarray(P, np.float64)
-        lib().orc_set(self._h, int(N), _p(X, ctypes.c_double), _p(Z, ctypes.c_double), _p(P, ctypes.c_double),
+        self._L.orc_set(self._h, int(N), _p(X, ctypes.c_double), _p(Z, ctypes.c_double), _p(P, ctypes.c_double),
                       float(a00), float(a10))
 
     def wait_list(self):
-        k = lib().orc_wait_size(self._h)
+        k = self._L.orc_wait_size(self._h)
         r, b, c = np.empty(k, np.float32), np.empty(k, np.float32), np.empty(k, np.uint32)
         if k:
-            lib().orc_get_wait(self._h, _p(r, ctypes.c_float), _p(b, ctypes.c_float), _p(c, ctypes.c_uint32))
+            self._L.orc_get_wait(self._h, _p(r, ctypes.c_float), _p(b, ctypes.c_float), _p(c, ctypes.c_uint32))
         return r, b, c
 
     def sensor_list(self):
-        k = lib().orc_sensor_size(self._h)
+        k = self._L.orc_sensor_size(self._h)
         r, b = np.empty(k, np.float32), np.empty(k, np.float32)
         if k:
-            lib().orc_get_sensor(self._h, _p(r, ctypes.c_float), _p(b, ctypes.c_float))
+            self._L.orc_get_sensor(self._h, _p(r, ctypes.c_float), _p(b, ctypes.c_float))
         return r, b
 
     def weights(self):
         w = np.empty(2 * self.N + 5)
         lam = ctypes.c_float()
-        lib().orc_get_weights(self._h, _p(w, ctypes.c_double), ctypes.byref(lam))
+        self._L.orc_get_weights(self._h, _p(w, ctypes.c_double), ctypes.byref(lam))
         return w, np.float32(lam.value)
 
     def replay(self, traj, T=None):
@@ -154,7 +164,7 @@ class CFilter:
         obs = np.ascontiguousarray(traj.obs[:T], np.float64)
         poses = np.zeros((T, 3))
         dims = np.zeros(T, np.int32)
-        lib().orc_replay(self._h, T, _p(odom, ctypes.c_double), _p(dt, ctypes.c_float), _p(on, ctypes.c_uint8),
+        self._L.orc_replay(self._h, T, _p(odom, ctypes.c_double), _p(dt, ctypes.c_float), _p(on, ctypes.c_uint8),
                          _p(no, ctypes.c_int32), _p(obs, ctypes.c_double), traj.max_obs,
                          _p(poses, ctypes.c_double), _p(dims, ctypes.c_int32))
         return poses, dims

@@ -3,10 +3,11 @@
 TEST INFRASTRUCTURE ONLY.  Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may
 import this module; nothing under awesomeslam_amd/ does.
 
-"parity unpinned" by the reference: iamarkaj/AwesomeSLAM has no tests, fixtures or golden vectors and
-cannot be compiled in this image (no Eigen, no ROS).  This file and oracle/aslam_oracle.cpp were written
-separately from the same reference text; tests/test_oracle_cross.py requires them to agree and
-tests/golden/ freezes their outputs.
+iamarkaj/AwesomeSLAM has no tests, fixtures or golden vectors.  This file and oracle/aslam_oracle.cpp were
+written separately from the same reference text; tests/test_oracle_cross.py requires them to agree,
+tests/golden/ freezes their outputs, and tests/test_reference_parity.py holds both against the reference's
+own nodes, compiled unmodified over oracle/ref_shim, and against their recorded outputs
+(tests/golden/reference/).
 
 It restates (paths relative to /root/reference/awesome_slam):
     src/ekf/ekf.cpp:49-311, src/ukf/ukf.cpp:49-392, src/ukf/ukf.h:56-82,

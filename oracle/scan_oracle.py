@@ -1,13 +1,16 @@
 """TEST INFRASTRUCTURE ONLY -- NumPy restatement of the reference's scan -> (range, bearing) front end
 (`src/sensor_landmark/sensor_landmark.cpp:59-298`), as coded, binary32 where the reference computes in
-`float`.  Never imported by the product path.  Parity unpinned: the reference has no tests and cannot be built here
-(Eigen + ROS); the dense pieces (JacobiSVD, SelfAdjointEigenSolver, colPivHouseholderQr) are LAPACK's here.
+`float`.  Never imported by the product path.  Held against the reference's own node, compiled over oracle/ref_shim
+(tests/test_reference_parity.py, tests/golden/reference/scan.npz); the dense pieces (JacobiSVD, SelfAdjointEigenSolver,
+colPivHouseholderQr) are LAPACK's here.
 
 As-coded behaviour that is kept (each cited below): the point that ends a cluster is not part of the next one; a cluster
 that runs up to beam 359 is never evaluated; `std` divides by 5.0 whatever the cluster size; M is formed and not used.
-If beams 0 and 359 are closer than MIN_DIST_THRESH the reference walks `theta` to 360 (after `p1 = p2` the loop condition
-compares a point with itself) and fails `assert(theta < 359)` (`:81`; no NDEBUG in its CMakeLists): `scan()` reports that
-as status REF_ABORT with no landmarks.
+If beams 0 and 359 are closer than MIN_DIST_THRESH the reference first walks `theta` on from beam 0 while a point is closer
+than the threshold to ITSELF (after `p1 = p2`): true for a finite point, false (NaN) for a beam without a return.  The main
+loop starts one past the first such beam; only a scan without one before beam 358 fails `assert(theta < 359)` (`:82`; no
+NDEBUG in its CMakeLists), which `scan()` reports as status REF_ABORT with no landmarks.  `bearing2pose(theta,
+msg->ranges[theta++])` is read left to right (beam theta with table entry theta; see oracle/Makefile).
 """
 import numpy as np
 
@@ -111,17 +114,29 @@ def to_laser(cx, cy):
 def scan(ranges, detail=False):
     """callback(), sensor_landmark.cpp:59-132 -> (status, range[], bearing[]) [+ the clusters that were fitted]"""
     p = points_of(ranges)
+    start, first = 0, None
     if dist(p[0], p[359]) < MIN_DIST_THRESH:
-        return (ST_REF_ABORT, np.zeros(0, F), np.zeros(0, F)) + (([],) if detail else ())
+        # :69-79.  After `p1 = p2` the loop condition compares a point with itself: 0 for a finite point, NaN (inf - inf) for a
+        # beam without a return, which ends the walk.  theta is then one past the first such beam.
+        k = next((t for t in range(360) if not dist(p[t], p[t]) < MIN_DIST_THRESH), 359)
+        if k + 1 >= 359:                                  # assert(theta < 359), :82
+            return (ST_REF_ABORT, np.zeros(0, F), np.zeros(0, F)) + (([],) if detail else ())
+        first = [0] + list(range(k + 1))                  # p(0) twice, then every beam walked, the non-finite one included
+        start = k + 1
     out_r, out_b, fitted = [], [], []
-    cluster = [0]
-    p1 = 0
-    for th in range(1, 360):
+    cluster = [start]
+    p1 = start
+    for th in range(start + 1, 360):
         if dist(p[p1], p[th]) < MIN_DIST_THRESH:
             cluster.append(th)
         elif len(cluster) > MIN_CLUSTER_POINTS and classify([p[i] for i in cluster]):
-            cx, cy = fit([p[i] for i in cluster])    # (theta == 360 would join first_cluster: empty on this path)
-            r, b = to_laser(cx, cy)
+            if th == 359 and first is not None:
+                # :103-111 joins first_cluster, which ends with a non-finite point: the fit's outcome is whatever the dense
+                # solvers make of inf/NaN input.  A landmark is published; its values are not pinned (NaN here).
+                r, b = F(np.nan), F(np.nan)
+            else:
+                cx, cy = fit([p[i] for i in cluster])
+                r, b = to_laser(cx, cy)
             out_r.append(r)
             out_b.append(b)
             fitted.append((cluster[0], cluster[-1]))

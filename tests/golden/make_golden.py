@@ -1,9 +1,11 @@
 """Generate the committed golden fixtures from the CPU oracles.
 
-The reference (iamarkaj/AwesomeSLAM) ships no tests, fixtures or golden vectors and cannot be built in this
-image (no Eigen, no ROS), so these vectors are SELF-GENERATED: they freeze the outputs of the two
-independent restatements (oracle/aslam_oracle.cpp and oracle/np_oracle.py, which must agree to 1e-9 here)
-on small seeded traces.  A fixture is data only: the input trace and the expected outputs.
+The reference (iamarkaj/AwesomeSLAM) ships no tests, fixtures or golden vectors.  These vectors are SELF-GENERATED:
+they freeze the outputs of the two independent restatements (oracle/aslam_oracle.cpp and oracle/np_oracle.py, which
+must agree to 1e-9 here) on small seeded traces, the configurations beyond the reference's cap of 30 included.  The
+restatements themselves are held against the reference's own nodes by make_reference_golden.py and
+tests/test_reference_parity.py (fixtures under tests/golden/reference/).  A fixture is data only: the input trace and
+the expected outputs.
 
     python tests/golden/make_golden.py        (re-run only when the oracle or the generator changes on purpose)
 """

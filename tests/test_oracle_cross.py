@@ -1,5 +1,6 @@
 """The two independent CPU restatements (C++ and NumPy) must agree, and the algebra the filters rely on
-must hold (SURVEY.md 8c pins i and iii).  "parity unpinned" by the reference: it has no tests of its own."""
+must hold (SURVEY.md 8c pins i and iii).  The reference has no tests of its own; both restatements are held against its
+compiled source text in tests/test_reference_parity.py."""
 import numpy as np
 import pytest
 

@@ -1,7 +1,8 @@
 """Compile-gated verbatim-Eigen check of the oracle.  `make -C oracle eigen` builds oracle/aslam_oracle.cpp a second
 time with its matrix products, `inverse()` and `llt().matrixL()` evaluated by Eigen itself (the library the reference links:
-ekf.cpp:297,300-301,309-310; ukf.cpp:280,378,391) -- only where <eigen3/Eigen/Dense> exists.  This image has no Eigen: the test
-then SKIPS, and parity stays "unpinned" (DESIGN.md section 3).  On a box with Eigen it replays the same seeded traces through both
+ekf.cpp:297,300-301,309-310; ukf.cpp:280,378,391) -- only where <eigen3/Eigen/Dense> exists; elsewhere the test SKIPS.  The
+reference's own text is held against the oracle without Eigen, over a header shim (tests/test_reference_parity.py, DESIGN.md
+section 3); this test adds Eigen's own blocked kernels on a box that has them.  It replays the same seeded traces through both
 builds in separate processes and compares state, covariance, dimensions and pose stream."""
 import os
 import subprocess
@@ -42,7 +43,7 @@ def replay(lib, kind, L, T, seed, tmp_path, tag):
 def test_restatement_against_eigen(kind, L, T, tmp_path):
     subprocess.call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "eigen"])
     if not os.path.exists(EIGEN_LIB):
-        pytest.skip("no <eigen3/Eigen/Dense> in this image: the Eigen-gated oracle build does not exist (parity unpinned)")
+        pytest.skip("no <eigen3/Eigen/Dense>: the Eigen-gated oracle build does not exist (tests/test_reference_parity.py pins the oracle without it)")
     a = replay(None, kind, L, T, 5, tmp_path, "plain")
     b = replay(EIGEN_LIB, kind, L, T, 5, tmp_path, "eigen")
     assert np.array_equal(a["dims"], b["dims"]) and np.array_equal(a["Z"], b["Z"])

@@ -4,21 +4,7 @@ import numpy as np
 import pytest
 
 from oracle import scan_oracle as so
-
-
-def cylinder_scan(cyls, noise=0.0, seed=0):
-    """exact ray casting of 1-degree beams against circles (cx, cy, r); inf = no return"""
-    rng = np.random.default_rng(seed)
-    th = np.deg2rad(np.arange(360.0))
-    dx, dy = np.cos(th), np.sin(th)
-    best = np.full(360, np.inf)
-    for cx, cy, r in cyls:
-        bq = dx * cx + dy * cy
-        disc = bq * bq - (cx * cx + cy * cy - r * r)
-        t = np.where((disc > 0) & (bq > 0), bq - np.sqrt(np.maximum(disc, 0)), np.inf)
-        best = np.minimum(best, t)
-    best = np.where(np.isfinite(best), best + rng.normal(0, noise, 360), np.inf)
-    return best.astype(np.float32)
+from reference_cases import cylinder_scan
 
 
 def test_oracle_recovers_cylinder_centres():
@@ -29,8 +15,13 @@ def test_oracle_recovers_cylinder_centres():
 
 
 def test_oracle_as_coded_quirks():
-    # an obstacle dead ahead links beams 0 and 359: the reference asserts (sensor_landmark.cpp:69-81)
+    # an obstacle dead ahead links beams 0 and 359: the reference walks on from beam 0 while a point is closer than the threshold
+    # to itself (sensor_landmark.cpp:69-79), i.e. up to the first beam without a return (inf - inf is NaN); the beams walked are
+    # in no cluster.  Only a scan with a return on every beam up to 358 fails its assert(theta < 359) (:82).  Recorded from the
+    # reference itself in tests/golden/reference/scan.npz (tests/test_reference_parity.py).
     st, r, b = so.scan(cylinder_scan([(2.0, 0.0, 0.3)]))
+    assert st == so.ST_OK and len(r) == 0
+    st, r, b = so.scan(np.full(360, 2.0, np.float32))
     assert st == so.ST_REF_ABORT and len(r) == 0
     # a cluster that runs up to beam 359 is never evaluated (the loop ends without a breaking beam, :92-121) ...
     c = 2.0 * np.cos(np.deg2rad(353.0)), 2.0 * np.sin(np.deg2rad(353.0))
@@ -71,8 +62,10 @@ def test_gpu_scan_parity(built):
         ost, orr, ob = so.scan(s)
         assert st[i] == ost and n[i] == len(orr), i
         if len(orr):
-            worst_r = max(worst_r, float(np.max(np.abs(rg[i, :n[i]] - orr) / orr)))
-            worst_b = max(worst_b, float(np.max(np.abs(bg[i, :n[i]] - ob))))
+            fin = np.isfinite(orr)   # (a cluster joined with first_cluster holds a non-finite point: published, values NaN)
+            assert np.array_equal(np.isfinite(rg[i, :n[i]]), fin) and np.array_equal(np.isfinite(bg[i, :n[i]]), fin), i
+            worst_r = max(worst_r, float(np.max(np.abs(rg[i, :n[i]][fin] - orr[fin]) / orr[fin], initial=0.0)))
+            worst_b = max(worst_b, float(np.max(np.abs(bg[i, :n[i]][fin] - ob[fin]), initial=0.0)))
             tot += len(orr)
     print(f"scan parity: {len(scans)} scans, {int((st == 1).sum())} reference aborts, {tot} landmarks, "
           f"max rel err range {worst_r:.2e}, max abs err bearing {worst_b:.2e} rad")
@@ -87,8 +80,10 @@ def test_gpu_scan_edge_cases(built):
     ahead = cylinder_scan([(2.0, 0.0, 0.3)])[None]
     many = cylinder_scan([(2.0 * np.cos(a), 2.0 * np.sin(a), 0.2) for a in np.deg2rad(np.arange(20.0, 340.0, 30.0))])[None]
     nan = np.full((1, 360), np.nan, np.float32)
-    n, rg, bg, st = scan_landmarks(np.concatenate([empty, ahead, many, nan]), max_out=4)
-    assert list(n[:2]) == [0, 0] and st[0] == 0 and st[1] == SCAN_REF_ABORT
+    ring = np.full((1, 360), 2.0, np.float32)      # a return on every beam: the reference's assert(theta < 359) fails
+    n, rg, bg, st = scan_landmarks(np.concatenate([empty, ahead, many, nan, ring]), max_out=4)
+    assert list(n[:2]) == [0, 0] and st[0] == 0 and st[1] == 0    # dead ahead with free space beside it: walked, not aborted
+    assert n[4] == 0 and st[4] == SCAN_REF_ABORT
     ost, orr, ob = so.scan(many[0])
     assert len(orr) > 4 and n[2] == 4 and st[2] == SCAN_OVERFLOW and np.allclose(rg[2], orr[:4], rtol=1e-5)
     assert n[3] == 0 and st[3] == 0
