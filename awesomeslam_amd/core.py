@@ -319,9 +319,9 @@ SCAN_BEAMS = 360
 SCAN_REF_ABORT, SCAN_OVERFLOW = 1, 2
 
 
-def scan_landmarks(ranges, max_out=64, device=0):
+def scan_landmarks(ranges, max_out=64, device=0, stream=None):
     """include/aslam_scan.h on host arrays: ranges [count, 360] f32 -> (n [count] i32, range [count, max_out] f32,
-    bearing [count, max_out] f32, status [count] u32).  Runs on the GPU; there is no CPU fallback."""
+    bearing [count, max_out] f32, status [count] u32).  Runs on the GPU (on `stream`, which it synchronises); there is no CPU fallback."""
     r = np.ascontiguousarray(ranges, np.float32)
     if r.ndim != 2 or r.shape[1] != SCAN_BEAMS:
         raise ValueError("ranges must be [count, 360]")
@@ -334,7 +334,7 @@ def scan_landmarks(ranges, max_out=64, device=0):
     lib = core_lib()
     lib.aslam_scan_landmarks.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-    _chk(lib.aslam_scan_landmarks(vp(r), cnt, 0, int(max_out), vp(rg), vp(bg), vp(n), vp(st), int(device), None))
+    _chk(lib.aslam_scan_landmarks(vp(r), cnt, 0, int(max_out), vp(rg), vp(bg), vp(n), vp(st), int(device), stream))
     return n, rg, bg, st
 
 

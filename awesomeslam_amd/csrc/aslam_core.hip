@@ -95,6 +95,11 @@ struct aslam_ctx
         // the staging block of the maintenance calls (Staging below): descriptors, reports, staged host arrays, records (grown on demand, not state)
         char *snap_dev = nullptr;
         size_t snap_cap = 0;
+        // the pinned host mirror the HOST arguments of the asynchronous maintenance calls pass through on their way to the staging block
+        // (stage_host below): free whenever the context is synchronised; blocks it has outgrown wait in stage_old for that moment
+        char *stage_pin = nullptr;
+        size_t stage_cap = 0, stage_used = 0;
+        std::vector<void *> stage_old;
 };
 
 namespace
@@ -157,6 +162,51 @@ int check_traj(aslam_ctx *c, int traj)
 int sync_ctx(aslam_ctx *c)
 {
         HIP_TRY(hipStreamSynchronize(c->last_stream));
+        c->stage_used = 0; // (nothing reads the pinned mirror any more)
+        // (hipHostFree may synchronise the whole device, not this context's stream alone: it runs only in the first synchronisation after the
+        // mirror has outgrown a block, which a context's first few maintenance calls can cause and its steady state does not)
+        for (void *p : c->stage_old)
+                (void)hipHostFree(p);
+        c->stage_old.clear();
+        return ASLAM_OK;
+}
+
+/// `bytes` of a HOST argument of a maintenance call to `dst` in the staging block, enqueued on `st`, the call's own stream, through the
+/// context's pinned mirror -- not a blocking copy through the null stream: that one waits for whatever unrelated stream shares its hardware
+/// queue, and is on no stream the caller can order against.  `src` may go when the call returns.  The context is synchronised when a call
+/// begins, so the mirror starts empty; a mirror that has to grow mid-call leaves the old block alive until the next synchronisation.
+int stage_host(aslam_ctx *c, void *dst, const void *src, size_t bytes, hipStream_t st)
+{
+        if (!bytes)
+                return ASLAM_OK;
+        const size_t need = (bytes + 63) & ~(size_t)63;
+        if (c->stage_used + need > c->stage_cap)
+        {
+                const size_t cap = std::max<size_t>(2 * (c->stage_used + need), 4096);
+                void *q = nullptr;
+                HIP_TRY(hipHostMalloc(&q, cap, hipHostMallocDefault));
+                if (c->stage_pin)
+                        c->stage_old.push_back(c->stage_pin);
+                c->stage_pin = static_cast<char *>(q), c->stage_cap = cap, c->stage_used = 0;
+        }
+        char *h = c->stage_pin + c->stage_used;
+        c->stage_used += need;
+        std::memcpy(h, src, bytes);
+        HIP_TRY(hipMemcpyAsync(dst, h, bytes, hipMemcpyHostToDevice, st));
+        return ASLAM_OK;
+}
+
+/// A call of the launching seams (steps, replay) enters on `st`: on a CHANGE of stream the context's last stream is waited for first, as the
+/// maintenance entries wait for it in every call (the contract in include/aslam_core.h: the context orders its own work across a change of
+/// stream).  With the stream unchanged this is one comparison: nothing is enqueued, nothing is waited for.
+int enter_stream(aslam_ctx *c, hipStream_t st)
+{
+        if (st != c->last_stream)
+        {
+                if (int rc = sync_ctx(c); rc != ASLAM_OK)
+                        return rc;
+                c->last_stream = st;
+        }
         return ASLAM_OK;
 }
 
@@ -595,6 +645,10 @@ int aslam_destroy(aslam_ctx *c)
                 (void)hipFree(p);
         if (c->snap_dev)
                 (void)hipFree(c->snap_dev);
+        if (c->stage_pin)
+                (void)hipHostFree(c->stage_pin);
+        for (void *p : c->stage_old)
+                (void)hipHostFree(p);
         for (hipStream_t q : c->lh.aux)
                 if (q)
                         (void)hipStreamDestroy(q);
@@ -791,7 +845,8 @@ int step_one(aslam_ctx *c, int filter, int traj, float vx, float az, float dt, c
         if (!Z)
                 return fail(ASLAM_ERR_ARG, "Z is required");
         hipStream_t st = static_cast<hipStream_t>(stream);
-        c->last_stream = st;
+        if ((rc = enter_stream(c, st)) != ASLAM_OK) // (before n is read: a growth may still be in flight on the last stream)
+                return rc;
         DevView &d = c->dv;
         int n = 0;
         HIP_TRY(hipMemcpyAsync(&n, d.n + traj, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -848,7 +903,8 @@ int step_batch(aslam_ctx *c, int filter, const float *vx, const float *az, const
         if (ldz < 3 || (X_out && ldx < 3))
                 return fail(ASLAM_ERR_ARG, "row strides must cover the state");
         hipStream_t st = static_cast<hipStream_t>(stream);
-        c->last_stream = st;
+        if (int rc = enter_stream(c, st); rc != ASLAM_OK)
+                return rc;
         DevView &d = c->dv;
         HIP_TRY(hipMemcpyAsync(c->step_in, vx, sizeof(float) * B, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(c->step_in + B, az, sizeof(float) * B, hipMemcpyHostToDevice, st));
@@ -972,7 +1028,8 @@ int aslam_replay_stats(aslam_ctx *c, int64_t t0, int64_t nsteps, double *poses_o
         if (t0 < 0 || nsteps < 1 || t0 + nsteps > c->dv.T || nsteps > 0x7fffffff)
                 return fail(ASLAM_ERR_ARG, "step range outside the bound trace");
         hipStream_t st = static_cast<hipStream_t>(stream);
-        c->last_stream = st;
+        if (int rc = enter_stream(c, st); rc != ASLAM_OK)
+                return rc;
         StepArgs sa{0, 0.f, 0.f, 0.f};
         StatsView sv = innovation_view(c);
         sv.nis = nis_out, sv.logdet = logdet_out, sv.pcov = pose_cov_out;
@@ -1682,9 +1739,10 @@ int aslam_select_beyond(aslam_ctx *c, const double *max_range, uint8_t *mask_dev
                 rc = snap_reserve(c, (size_t)snap_pad64(8 * (int64_t)B));
         if (rc != ASLAM_OK)
                 return rc;
-        HIP_TRY(hipMemcpy(c->snap_dev, r2.data(), sizeof(double) * B, hipMemcpyHostToDevice));
         hipStream_t st = static_cast<hipStream_t>(stream);
         c->last_stream = st;
+        if ((rc = stage_host(c, c->snap_dev, r2.data(), sizeof(double) * B, st)) != ASLAM_OK)
+                return rc;
         hipLaunchKernelGGL(prune_select_beyond, dim3((unsigned)B), dim3(PRUNE_WAVE), 0, st, (const double *)c->dv.X, (const int *)c->dv.n, c->NP,
                            reinterpret_cast<const double *>(c->snap_dev), mask_dev, ld);
         HIP_TRY(hipGetLastError());
@@ -1703,9 +1761,10 @@ int aslam_select_stale(aslam_ctx *c, const uint32_t *max_age, uint8_t *mask_dev,
                 rc = snap_reserve(c, (size_t)snap_pad64(4 * (int64_t)B));
         if (rc != ASLAM_OK)
                 return rc;
-        HIP_TRY(hipMemcpy(c->snap_dev, max_age, sizeof(uint32_t) * B, hipMemcpyHostToDevice));
         hipStream_t st = static_cast<hipStream_t>(stream);
         c->last_stream = st;
+        if ((rc = stage_host(c, c->snap_dev, max_age, sizeof(uint32_t) * B, st)) != ASLAM_OK)
+                return rc;
         hipLaunchKernelGGL(prune_select_stale, dim3((unsigned)B), dim3(PRUNE_WAVE), 0, st, (const uint32_t *)c->dv.clock, (const uint32_t *)c->dv.lm_seen,
                            (const int *)c->dv.n, c->NP, reinterpret_cast<const uint32_t *>(c->snap_dev), mask_dev, ld);
         HIP_TRY(hipGetLastError());
@@ -1982,9 +2041,10 @@ int aslam_select_duplicates(aslam_ctx *c, const double *gate, const double *max_
                 rc = s.reserve();
         if (rc != ASLAM_OK)
                 return rc;
-        HIP_TRY(hipMemcpy(s.at<double>(o_par), par.data(), sizeof(double) * 2 * B, hipMemcpyHostToDevice));
         hipStream_t st = static_cast<hipStream_t>(stream);
         c->last_stream = st;
+        if ((rc = stage_host(c, s.at<double>(o_par), par.data(), sizeof(double) * 2 * B, st)) != ASLAM_OK)
+                return rc;
         const double *pd = s.at<double>(o_par);
         int32_t *partner = s.at<int32_t>(o_partner);
         const int wpb = MERGE_WG / PRUNE_WAVE;
@@ -2037,16 +2097,18 @@ int aslam_gate_observations(aslam_ctx *c, const float *obs, int ldo, int is_devi
                 rc = s.reserve();
         if (rc != ASLAM_OK)
                 return rc;
-        HIP_TRY(hipMemcpy(s.at<double>(o_gate), gate, sizeof(double) * B, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(s.at<int32_t>(o_n), n_obs, sizeof(int32_t) * B, hipMemcpyHostToDevice));
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        c->last_stream = st;
+        if ((rc = stage_host(c, s.at<double>(o_gate), gate, sizeof(double) * B, st)) != ASLAM_OK ||
+            (rc = stage_host(c, s.at<int32_t>(o_n), n_obs, sizeof(int32_t) * B, st)) != ASLAM_OK)
+                return rc;
         const float *odev = obs;
         if (!is_device)
         {
-                HIP_TRY(hipMemcpy(s.at<float>(o_obs), obs, obs_bytes, hipMemcpyHostToDevice));
+                if ((rc = stage_host(c, s.at<float>(o_obs), obs, obs_bytes, st)) != ASLAM_OK)
+                        return rc;
                 odev = s.at<float>(o_obs);
         }
-        hipStream_t st = static_cast<hipStream_t>(stream);
-        c->last_stream = st;
         hipLaunchKernelGGL(assoc_gate, dim3((unsigned)B), dim3(ASSOC_WG), 0, st, (const double *)c->dv.X, (const double *)(c->large ? c->largeP : c->dv.P),
                            (const int *)c->dv.n, c->NP, (const aslam_params *)c->params_dev, odev, ldo, (const int32_t *)s.at<int32_t>(o_n),
                            (const double *)s.at<double>(o_gate), assoc_dev, mdist_dev);
@@ -2180,17 +2242,19 @@ int aslam_joint_compat(aslam_ctx *c, const float *obs, int ldo, int is_device, c
                 rc = s.reserve();
         if (rc != ASLAM_OK)
                 return rc;
-        if (gate_tab)
-                HIP_TRY(hipMemcpy(s.at<double>(o_tab), gate_tab, sizeof(double) * (ldo + 1), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(s.at<int32_t>(o_n), n_obs, sizeof(int32_t) * B, hipMemcpyHostToDevice));
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        c->last_stream = st;
+        if (gate_tab && (rc = stage_host(c, s.at<double>(o_tab), gate_tab, sizeof(double) * (ldo + 1), st)) != ASLAM_OK)
+                return rc;
+        if ((rc = stage_host(c, s.at<int32_t>(o_n), n_obs, sizeof(int32_t) * B, st)) != ASLAM_OK)
+                return rc;
         const float *odev = obs;
         if (!is_device)
         {
-                HIP_TRY(hipMemcpy(s.at<float>(o_obs), obs, obs_bytes, hipMemcpyHostToDevice));
+                if ((rc = stage_host(c, s.at<float>(o_obs), obs, obs_bytes, st)) != ASLAM_OK)
+                        return rc;
                 odev = s.at<float>(o_obs);
         }
-        hipStream_t st = static_cast<hipStream_t>(stream);
-        c->last_stream = st;
         const size_t lds = JointLds{ldo}.bytes();
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(joint_compat), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(joint_compat, dim3((unsigned)B), dim3(JOINT_WG), lds, st, (const double *)c->dv.X, (const double *)(c->large ? c->largeP : c->dv.P),

@@ -10,10 +10,32 @@
  *
  * Conventions: plain C types, caller-owned buffers, `int` status returns (0 = ASLAM_OK, negative =
  * error, text via aslam_last_error()); no exceptions cross the seam.  A context owns all filter state
- * for `batch` independent filters ("trajectories") in HBM; matrices are row-major.  One HIP stream per
- * call (the `stream` argument is a hipStream_t passed as void*, NULL = the default stream); a context
- * is not re-entrant.  Everything is fp64 unless the context was created with ASLAM_F32 (EKF only: the UKF is
- * fp64 at every size -- the single-CU kernels up to N = 143, the ASLAM_CFG_UKF_LARGE launch chain beyond).
+ * for `batch` independent filters ("trajectories") in HBM; matrices are row-major.  Everything is fp64
+ * unless the context was created with ASLAM_F32 (EKF only: the UKF is fp64 at every size -- the single-CU
+ * kernels up to N = 143, the ASLAM_CFG_UKF_LARGE launch chain beyond).
+ *
+ * STREAMS (this header, aslam_snapshot.h and aslam_scan.h).  One HIP stream per call: the `stream` argument
+ * is a hipStream_t passed as void*, NULL = the default stream; blocking and non-blocking streams are alike.
+ *   - "Asynchronous on `stream`" means: every launch of the call, and every copy of a device input or output,
+ *     is enqueued on `stream` (the stream groups of a large-state batch fork from `stream` and join it again
+ *     inside the call).  Small host descriptors may be copied down synchronously by the entries that
+ *     synchronise inside (below); the entries that do not synchronise copy nothing outside `stream`.  DEVICE inputs -- a bound device trace, a device mask / into / cand / obs / blob / scan array --
+ *     are read in stream order, so a producer enqueued on `stream` before the call is in order; DEVICE
+ *     outputs are complete for whatever is enqueued on `stream` behind the call, and for the host once
+ *     `stream` is synchronised.  No device-wide synchronisation is needed or done.
+ *   - The context orders ITS OWN work across a change of stream: a call on another stream than the context's
+ *     last one first waits, on the host, for that last stream.  The maintenance entries and the getters
+ *     ("synchronises the context first") do so in every call; aslam_*_step, aslam_*_step_batch and
+ *     aslam_replay[_stats] only when the stream differs from the last one -- on an unchanged stream they add
+ *     nothing, neither a wait nor a launch.  `stream` then becomes the context's last stream.
+ *   - Entries that need a number from the device synchronise `stream` INSIDE the call, and say so:
+ *     aslam_*_step (the dimension; and X_out), aslam_remove_landmarks, aslam_merge_landmarks,
+ *     aslam_join_maps, aslam_snapshot (the counts), aslam_restore and aslam_join_maps of a device blob
+ *     (the headers), aslam_scan_landmarks on host arrays.
+ *   - The caller's duty: HOST arrays handed to an asynchronous entry (aslam_*_step_batch: inputs and X_out)
+ *     stay untouched / unread until the caller has synchronised `stream`; device buffers stay alive until
+ *     `stream` has passed the call; a producer or consumer on ANOTHER stream than the call's is the caller's to
+ *     order (an event); and a context is not re-entrant -- two host threads on one context need a lock.
  */
 #ifndef ASLAM_CORE_H
 #define ASLAM_CORE_H
